@@ -18,7 +18,14 @@ Workloads (`--workload`):
       weights) + cycle aggregation (8 novel views of all B images in one launch sequence, 8 re-predictions, in-place merge)
       + the 8 orbit views of every merged set + frame packing + the gather. A "step" = B x 8 final views.
 
-Every number of the JSON line is measured in THIS run except the `*_from_profiles` objects, which are read from the committed
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set-up (inputs, one calibration pass that
+sizes the workspaces), W warm-up steps, K timed steps of the loop `value` comes from, and the JSON line (`metric`, `value`, `unit`,
+`ms_per_step` = milliseconds per timed step, `higher_is_better`, `dtype`, the configuration). `--dump-outputs DIR` then writes what the
+last timed step computed (the float32 planes, the radii and, where the loop copies them to the host, the 8-bit frames) as DIR/*.npy;
+the inputs are seeded, so two builds run with the same arguments compare output for output. Everything below is measured with
+`--full` (C2; the other workloads measure what they always have).
+
+Every number of the --full JSON line is measured in THIS run except the `*_from_profiles` objects, which are read from the committed
 rocprofv3 PMC passes of the same command (profiles/<round>/traffic.json) and say so. Hardware counters cannot be read from inside
 the process: at N = 1 the C2 line's `roofline.traffic` comes from two child runs of the same workload under `rocprofv3 --pmc`
 (FETCH_SIZE, WRITE_SIZE; `roofline.traffic_live`; --no-pmc or F3DG_BENCH_PMC=0 skips them, a failure leaves null and says why). C2 at N = 1 runs three timed loops of K steps each: frames left in HBM (`value_in_hbm`), frames packed to 8-bit RGB
@@ -101,7 +108,18 @@ def parse():
     ap.add_argument("--d2h-workgroups", type=int, default=int(os.environ.get("F3DG_D2H_WG", "0")), help="direct path: workgroups of the pack kernel (0: 64)")
     ap.add_argument("--no-exact", action="store_true", help="skip the extra timed loop in the reference's arithmetic (value_exact / roofline_exact)")
     ap.add_argument("--cpu-sample-views", type=int, default=12)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="c2: everything beyond the headline figure -- the calibration pass on the reference's tile lists, the in-HBM and "
+                         "reference-arithmetic loops, the pack / copy legs and the float32 copy loop, the kernel's work counters, the copy "
+                         "bandwidth, the CPU baseline and the rocprofv3 --pmc child passes (each still subject to its --no-* switch); "
+                         "without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2: after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32; "
+                         "arrays over their share of 60 MB as a fixed, seeded sample of their elements)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.workload != "c2":
+        ap.error("--dump-outputs is implemented for --workload c2")
+    return args
 
 
 def setup_dist():
@@ -235,12 +253,15 @@ def run_c2(args, rank, world, dist, device, comm_device, f3d, L):
             radii=radii[a:b], save_aux=False, check=check, **call_opts)
         return ws
 
-    # calibration passes (untimed). First with the reference's tile lists: R_total = the reference's num_rendered, the unit count of
-    # SURVEY 8d's byte formulas (the workload's size, whatever the implementation then skips). Then in the benched configuration:
+    # calibration passes (untimed). With --full first with the reference's tile lists: R_total = the reference's num_rendered, the unit
+    # count of SURVEY 8d's byte formulas (the workload's size, whatever the implementation then skips). Then in the benched configuration:
     # sizes every chunk's workspace (capacity = max over chunks, +25 %) and counts the instances the launches really process.
-    call_opts["tile_cull"] = False
-    R_total = sum(render_chunk(a, b, check=True).num_rendered for a, b in chunks)
-    call_opts["tile_cull"] = None
+    full = args.full
+    R_total = list_stats = None
+    if full:
+        call_opts["tile_cull"] = False
+        R_total = sum(render_chunk(a, b, check=True).num_rendered for a, b in chunks)
+        call_opts["tile_cull"] = None
     counts = []
     for a, b in chunks:
         ws = render_chunk(a, b, check=True)
@@ -250,16 +271,17 @@ def run_c2(args, rank, world, dist, device, comm_device, f3d, L):
         workspaces[n] = f3d.diff_gof_rasterization.Workspace(P, RES, RES, n, cap, device)
     R_proc = sum(c[1] for c in counts)
     # length of the (view, tile) lists the compositing kernel is handed (last chunk's call: the ranges are still in its workspace)
-    a_, b_ = chunks[-1]
-    T_ = ((RES + 15) // 16) ** 2
-    rng_ = torch.zeros((b_ - a_) * T_ * 2, dtype=torch.int32, device=device)
-    _lib.check(L.f3dg_debug_export(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.c_void_p(ws.buffer.data_ptr()), P, RES, RES, b_ - a_,
-                                   ws.max_rendered, None, None, None, None, None, None, None, None, C.c_void_p(rng_.data_ptr()), None, None, None),
-               "f3dg_debug_export")
-    rr_ = rng_.reshape(-1, 2).cpu()
-    lens_ = (rr_[:, 1] - rr_[:, 0]).float()
-    list_stats = {"tile_list_mean": float(lens_.mean()), "tile_list_max": int(lens_.max()), "instances_per_view_and_gaussian": R_proc / float(V * P),
-                  "reference_instances_per_view_and_gaussian (R/P per view)": R_total / float(V * P)}
+    if full:
+        a_, b_ = chunks[-1]
+        T_ = ((RES + 15) // 16) ** 2
+        rng_ = torch.zeros((b_ - a_) * T_ * 2, dtype=torch.int32, device=device)
+        _lib.check(L.f3dg_debug_export(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.c_void_p(ws.buffer.data_ptr()), P, RES, RES, b_ - a_,
+                                       ws.max_rendered, None, None, None, None, None, None, None, None, C.c_void_p(rng_.data_ptr()), None, None, None),
+                   "f3dg_debug_export")
+        rr_ = rng_.reshape(-1, 2).cpu()
+        lens_ = (rr_[:, 1] - rr_[:, 0]).float()
+        list_stats = {"tile_list_mean": float(lens_.mean()), "tile_list_max": int(lens_.max()), "instances_per_view_and_gaussian": R_proc / float(V * P),
+                      "reference_instances_per_view_and_gaussian (R/P per view)": R_total / float(V * P)}
 
     gat = Gatherer(dist, world, rank, (V, RES, RES, 3), comm_device)
 
@@ -292,17 +314,32 @@ def run_c2(args, rank, world, dist, device, comm_device, f3d, L):
             f3d.diff_gof_rasterization.read_status(ws)
         return t, st, nc, launches, rows
 
+    def dump(render, frames=None):
+        """--dump-outputs: the headline loop's last step, taken before anything else renders into its buffers"""
+        if args.dump_outputs and rank == 0:
+            arrays = {"render": render, "radii": radii}
+            if frames is not None:
+                arrays["frames_rgb8"] = frames
+            dump_outputs(args.dump_outputs, arrays)
+
+    # the headline loop: (2) at N = 1 unless --no-d2h, else (1); --full runs both
+    d2h_loop = world == 1 and not args.no_d2h
+
     # (1) frames left in HBM (N > 1: + the RCCL gather of the packed frames)
-    elapsed_hbm, stage_ms, ncalls, nlaunch, rows = measure(step, args.warmup, args.steps)
-    kernel_name = L.f3dg_debug_last_render_kernel().decode()           # what the library launched, with its template arguments
-    elapsed_hbm = max_over_ranks(elapsed_hbm, dist, world, comm_device if world > 1 else device)
+    if full or not d2h_loop:
+        elapsed_hbm, stage_ms, ncalls, nlaunch, rows = measure(step, args.warmup, args.steps)
+        kernel_name = L.f3dg_debug_last_render_kernel().decode()           # what the library launched, with its template arguments
+        elapsed_hbm = max_over_ranks(elapsed_hbm, dist, world, comm_device if world > 1 else device)
+        elapsed = elapsed_hbm
+        if not d2h_loop:
+            dump(out, torch.stack(gat.buf) if gat.buf else None)
 
     # (2) N = 1, SURVEY 8d "views/s = views / wall time including the final D2H of RGB only": the frames leave the GPU as 8-bit RGB
     # (what the reference turns every frame into before it writes the video, visualize.py:407,416). Two output buffers: while
     # step i + 1 renders, a side stream packs step i's frames (f3dg_pack_frames) and copies them to pinned host memory; everything
-    # is waited for inside the timed region. Also timed: the float32 RGB planes, un-pipelined (the PCIe-heavy variant).
-    elapsed, d2h = elapsed_hbm, None
-    if world == 1 and not args.no_d2h:
+    # is waited for inside the timed region. Also timed (--full): the float32 RGB planes, un-pipelined (the PCIe-heavy variant).
+    d2h = None
+    if d2h_loop:
         import queue
         import threading
         side = torch.cuda.Stream(device=device)       # (stream priorities -1 / 0 on either side: no difference, notes/r06.md section 3)
@@ -383,7 +420,7 @@ def run_c2(args, rank, world, dist, device, comm_device, f3d, L):
         for k in range(2):
             copied[k].record()
             issued[k].set()
-        timed(step_d2h, d2h_barrier, 2, 0)
+        timed(step_d2h, d2h_barrier, 2 if full else args.warmup, 0)     # (--full: after loop (1)'s warm-up and timed steps)
         L.f3dg_profile_enable(1)
         L.f3dg_debug_launch_count(1)
         elapsed = timed(step_d2h, d2h_barrier, 0, args.steps)
@@ -394,7 +431,10 @@ def run_c2(args, rank, world, dist, device, comm_device, f3d, L):
             f3d.diff_gof_rasterization.read_status(ws)
         jobs.put(None)
         worker.join(timeout=10)
+        last = (state["i"] - 1) & 1
+        dump(outs[last], host[last])
 
+    if d2h_loop and full:
         # the pack + copy leg alone, nothing else on the device (what has to hide behind the next step)
         leg = []
         for _ in range(3):
@@ -443,7 +483,7 @@ def run_c2(args, rank, world, dist, device, comm_device, f3d, L):
 
     # (3) the same build in the reference's own arithmetic (float32 with the float64 island, forward.cu:511-579), frames left in HBM
     exact = None
-    if args.render_mode == "fast" and not args.no_exact:
+    if full and args.render_mode == "fast" and not args.no_exact:
         call_opts["exact"] = True
         e_x, st_x, nc_x, _, rows_x = measure(step, 1, args.steps)
         kernel_name_x = L.f3dg_debug_last_render_kernel().decode()
@@ -454,7 +494,7 @@ def run_c2(args, rank, world, dist, device, comm_device, f3d, L):
     # (4) what the compositing kernel did, counted by its counting variant in ONE untimed call sequence (option render_count): the
     # list entries it staged (a quadrant stops reading its tile's list once its 64 pixels are saturated), its phase-2 trips and lanes
     counts = None
-    if True:        # (every rank: at N > 1 a step ends in the collective gather)
+    if full:        # (every rank: at N > 1 a step ends in the collective gather)
         _lib.check(L.f3dg_set_option(b"render_count", 1), "f3dg_set_option")
         cbuf = (C.c_ulonglong * 16)()
         L.f3dg_debug_render_counts(cbuf, 1)
@@ -504,6 +544,39 @@ def run_c2(args, rank, world, dist, device, comm_device, f3d, L):
 
     if rank != 0:
         return None
+    caveat = ("fast = error-free float32 pairs for the float64 island + hardware exp/rcp/rsq; every channel within 1e-4 of the oracle "
+              "(RGB <= 3e-7), EXCEPT that the distortion channel (values 1e-7..1e-5 from cancelling float32 sums) moves by 3-17 % "
+              "relative (median) at sigma0 = 0.01 -- absolute <= 1e-6, the reference's own 1-ulp noise on that channel") \
+        if args.render_mode == "fast" else "exact = the reference's float32/float64 operation order"
+    result = {
+        "metric": "rendered views/sec at 256x256 (N Gaussians, K cams)",
+        "value": world * V * args.steps / elapsed,
+        "unit": "views/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32" if args.render_mode == "fast" else "f32 (+f64 islands, as the reference)",
+        "data": "synthetic" if args.data == "synthetic" else
+                "real image n01644373_4548.jpg + LeReS depth (tests/golden/real_image_256.npz) through this build's predictor + cycle "
+                "aggregation with formula weights (no checkpoint travels); cameras as the reference's orbit",
+        "config": {"workload": "%s: 1 image/GPU, %d Gaussians (%s), %d-view orbit @%dx%d, GOF forward raster only; timed region = "
+                               "%s; compositing arithmetic: %s" % (
+                                   "C2" if args.data == "synthetic" else "C2-shaped on the real merged set",
+                                   P, ("sigma0=%g" % args.sigma0) if args.data == "synthetic" else "9 x 65,536 predicted, sigma ~ 0.01", V, RES, RES,
+                                   "render + RCCL gather of the 8-bit frames to rank 0" if world > 1 else
+                                   ("render, frames left in HBM" if not d2h_loop else "render + 8-bit RGB frames copied to pinned host memory"),
+                                   caveat),
+                   "gaussians": P, "views": V, "resolution": RES, "sigma0": args.sigma0,
+                   "instances_processed_per_step": R_proc, "tile_cull": args.tile_cull,
+                   "views_per_call": args.views_per_call, "render_mode": args.render_mode, "channels": args.channels,
+                   "kernel_launches_per_call": nlaunch / float(ncalls),
+                   "parallelism": "image-sharded x%d + RCCL gather" % world if world > 1 else "single GPU"},
+        "dist_backend": (os.environ.get("F3DG_DIST_BACKEND", "nccl") if world > 1 else None),
+        "ranks_seen": (dist.get_world_size() if world > 1 else 1),
+    }
+    if not full:
+        return result
+
     copy_gbs = measured_copy_bandwidth(device)
     T = ((RES + 15) // 16) ** 2
     per = lambda ms, n=None: ms / (n or ncalls)
@@ -562,41 +635,14 @@ def run_c2(args, rank, world, dist, device, comm_device, f3d, L):
                "peak_measured_copy": copy_gbs,     # device-to-device copy on THIS box, read + write bytes
                "stage_ms_per_step": {"preprocess": stage_ms[0] / args.steps, "binning": stage_ms[1] / args.steps,
                                      "compositing": stage_ms[2] / args.steps}})
-    caveat = ("fast = error-free float32 pairs for the float64 island + hardware exp/rcp/rsq; every channel within 1e-4 of the oracle "
-              "(RGB <= 3e-7), EXCEPT that the distortion channel (values 1e-7..1e-5 from cancelling float32 sums) moves by 3-17 % "
-              "relative (median) at sigma0 = 0.01 -- absolute <= 1e-6, the reference's own 1-ulp noise on that channel") \
-        if args.render_mode == "fast" else "exact = the reference's float32/float64 operation order"
-    result = {
-        "metric": "rendered views/sec at 256x256 (N Gaussians, K cams)",
-        "value": world * V * args.steps / elapsed,
-        "unit": "views/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32" if args.render_mode == "fast" else "f32 (+f64 islands, as the reference)",
-        "data": "synthetic" if args.data == "synthetic" else
-                "real image n01644373_4548.jpg + LeReS depth (tests/golden/real_image_256.npz) through this build's predictor + cycle "
-                "aggregation with formula weights (no checkpoint travels); cameras as the reference's orbit",
-        "config": {"workload": "%s: 1 image/GPU, %d Gaussians (%s), %d-view orbit @%dx%d, GOF forward raster only; timed region = "
-                               "%s; compositing arithmetic: %s" % (
-                                   "C2" if args.data == "synthetic" else "C2-shaped on the real merged set",
-                                   P, ("sigma0=%g" % args.sigma0) if args.data == "synthetic" else "9 x 65,536 predicted, sigma ~ 0.01", V, RES, RES,
-                                   "render + RCCL gather of the 8-bit frames to rank 0" if world > 1 else
-                                   ("render, frames left in HBM" if d2h is None else "render + 8-bit RGB frames copied to pinned host memory"),
-                                   caveat),
-                   "gaussians": P, "views": V, "resolution": RES, "sigma0": args.sigma0, "instances_per_step": R_total, "lists": list_stats,
-                   "instances_processed_per_step": R_proc, "tile_cull": args.tile_cull,
-                   "views_per_call": args.views_per_call, "render_mode": args.render_mode, "channels": args.channels,
-                   "kernel_launches_per_call": nlaunch / float(ncalls),
-                   "parallelism": "image-sharded x%d + RCCL gather" % world if world > 1 else "single GPU"},
+    result["config"].update({"instances_per_step": R_total, "lists": list_stats})
+    result.update({
         "value_in_hbm": world * V * args.steps / elapsed_hbm, "ms_per_step_in_hbm": 1e3 * elapsed_hbm / args.steps,
         "call_ms_spread": {"note": "device time of one call (projection + binning + compositing, HIP events) over the calls of the timed "
                                    "loop `value` comes from: a box-to-box or run-to-run effect shows here, not only in the mean",
                            "slowest_call_index": (max(range(len(rows)), key=lambda i: sum(rows[i])) if rows else None),
                            "all_stages": spread(rows, None), "preprocess": spread(rows, 0), "binning": spread(rows, 1),
                            "compositing": spread(rows, 2)},
-        "dist_backend": (os.environ.get("F3DG_DIST_BACKEND", "nccl") if world > 1 else None),
-        "ranks_seen": (dist.get_world_size() if world > 1 else 1),
         "roofline": rf,
         "rooflines_other": {
             "preprocess_kernel": {"bound": "hbm", "algorithmic_bytes_per_launch": b_pre, "ms_per_launch": per(stage_ms[0]),
@@ -608,7 +654,7 @@ def run_c2(args, rank, world, dist, device, comm_device, f3d, L):
                 "achieved": gbs(b_bin, per(stage_ms[1])), "unit": "GB/s", "frac": gbs(b_bin, per(stage_ms[1])) / HBM_PEAK_GBS,
                 "formula": "this build's streams: 108 B x P x views + 18 B x instances_processed + 8 B x tiles x views",
                 "traffic_from_profiles": (prof.get("stages") or {}).get("binning")}},
-    }
+    })
     if d2h:
         result["with_d2h"] = d2h
     if exact:
@@ -669,7 +715,7 @@ def live_pmc_traffic(kernel_name, workload_args):
     if not sub:
         out["error"] = "no kernel name"
         return out
-    cmd_tail = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-pmc"] + list(workload_args)
+    cmd_tail = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-pmc"] + list(workload_args)
     env = dict(os.environ, TMPDIR="/tmp", F3DG_BENCH_PMC="0")
     vals = {}
     t0 = time.time()
@@ -956,6 +1002,26 @@ def run_c5(args, rank, world, dist, device, comm_device, f3d, L):
 
 
 # ---------------------------------------------------------------------------------------------------------------- helpers
+DUMP_BUDGET_BYTES = 60 << 20        # --dump-outputs: all arrays together, as float32
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs DIR: every array of `arrays` (name -> tensor) as DIR/<name>.npy in float32. One that fits its equal share of
+    DUMP_BUDGET_BYTES is written whole, in its shape; a larger one as the 1-D array of its elements at a fixed sample of flat indices
+    (sorted, drawn from a generator seeded by the name), so two runs with the same arguments compare element for element."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > share:
+            idx = np.unique(np.random.default_rng(zlib.crc32(name.encode())).integers(0, t.numel(), size=share))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(directory, name + ".npy"), t.float().cpu().numpy())
+
+
 def measured_copy_bandwidth(device, nbytes=1 << 30, reps=5):
     """GB/s (read + write) of a plain device-to-device copy of 1 GiB on this box: the practical HBM ceiling next to the
     8 TB/s nominal peak the roofline fraction is quoted against."""

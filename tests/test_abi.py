@@ -178,3 +178,28 @@ def test_bench_pmc_counter_mean_takes_the_largest_grid_dispatches(tmp_path):
     assert bench.pmc_counter_mean(str(tmp_path), "render3s_fwd_kernel", "FETCH_SIZE") == (105.0, 2)
     assert bench.pmc_counter_mean(str(tmp_path), "render3s_fwd_kernel", "WRITE_SIZE") == (7.0, 1)
     assert bench.pmc_counter_mean(str(tmp_path), "render5_bwd_kernel", "FETCH_SIZE") is None
+
+
+def test_bench_dump_outputs_is_seeded_and_bounded(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 .npy files, small arrays whole in their shape, large ones as the same seeded
+    sample in every run, all of them together under 64 MB."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    import torch
+    big = {"render": torch.rand(40, 9, 256, 256), "radii": torch.randint(0, 60, (120, 196608), dtype=torch.int32),
+           "frames_rgb8": torch.randint(0, 256, (120, 256, 256, 3), dtype=torch.uint8)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    total = 0
+    for name, t in big.items():
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        total += os.path.getsize(tmp_path / "a" / (name + ".npy"))
+        assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size < t.numel() and np.array_equal(a, b), name
+        assert a.min() >= float(t.min()) and a.max() <= float(t.max()), name
+    assert total < 64 << 20
+    small = torch.rand(3, 9, 8, 8)
+    bench.dump_outputs(str(tmp_path / "s"), {"render": small, "radii": torch.arange(6, dtype=torch.int32).reshape(2, 3)})
+    assert np.array_equal(np.load(tmp_path / "s" / "render.npy"), small.numpy())
+    assert np.load(tmp_path / "s" / "radii.npy").tolist() == [[0.0, 1.0, 2.0], [3.0, 4.0, 5.0]]

@@ -111,14 +111,16 @@ def main():
             pm = projection.expand([cam2w.shape[0], -1, -1]).unsqueeze(1).contiguous()
             fp = (wv[:, 0].bmm(pm[:, 0])).unsqueeze(1).contiguous()
             quat = torch.zeros_like(fp[:, 0:1, 0, :])
+            quat_in = v2w.clone()               # the matrices the quaternions are computed from (before or after the update)
             if quat_before:
                 for i in range(num_quat):
                     quat[i] = dio.matrix_to_quaternion(v2w[i, 0, :3, :3].transpose(0, 1).contiguous())
             wv, v2w, fp, cc, _ = dio.update_camera_pose(wv, v2w, fp, cc, inv_first, False)
             if not quat_before:
+                quat_in = v2w.clone()
                 for i in range(num_quat):
                     quat[i] = dio.matrix_to_quaternion(v2w[i, 0, :3, :3].transpose(0, 1).contiguous())
-            return wv, v2w, fp, cc, quat
+            return wv, v2w, fp, cc, quat, quat_in
 
         o8 = assemble(build(8, 0.25, 0.15), 8, False)
         cam2w129 = torch.cat([build(1, 0.0, 0.0), build(128, 0.25, 0.15)], 0)
@@ -126,8 +128,8 @@ def main():
         np.savez_compressed(
             os.path.join(OUT, "cameras.npz"), projection=npy(projection), inv_first=npy(inv_first),
             c_wv=npy(c_wv), c_v2w=npy(c_v2w), c_fp=npy(c_fp), c_cc=npy(c_cc), c_quat=npy(c_quat),
-            **{f"o8_{n}": npy(t) for n, t in zip(("wv", "v2w", "fp", "cc", "quat"), o8)},
-            **{f"o129_{n}": npy(t) for n, t in zip(("wv", "v2w", "fp", "cc", "quat"), o129)})
+            **{f"o8_{n}": npy(t) for n, t in zip(("wv", "v2w", "fp", "cc", "quat", "quat_in"), o8)},
+            **{f"o129_{n}": npy(t) for n, t in zip(("wv", "v2w", "fp", "cc", "quat", "quat_in"), o129)})
 
         # ------------------------------------------------------------------ splat head (gaussian_predictor.py:883-1007)
         cfg32 = copy.deepcopy(cfg)

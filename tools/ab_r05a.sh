@@ -7,10 +7,10 @@ tail -3 $O/pytest_packed.log
 B="--no-cpu-baseline --no-exact --no-d2h --steps 10 --warmup 3"
 for cfg in "3 32" "4 64" "4 48" "4 32" "4 24" "4 16" "4 8" "4 0"; do
   set -- $cfg
-  F3DG_RENDER_KERNEL=$1 F3DG_RENDER_PACK_TH=$2 python bench.py $B > $O/c2_k$1_th$2.log 2>&1
-  F3DG_RENDER_KERNEL=$1 F3DG_RENDER_PACK_TH=$2 python bench.py $B --data real > $O/real_k$1_th$2.log 2>&1
-  F3DG_RENDER_KERNEL=$1 F3DG_RENDER_PACK_TH=$2 python bench.py $B --render-mode exact > $O/c2x_k$1_th$2.log 2>&1
-  F3DG_RENDER_KERNEL=$1 F3DG_RENDER_PACK_TH=$2 python bench.py $B --render-mode exact --data real > $O/realx_k$1_th$2.log 2>&1
+  F3DG_RENDER_KERNEL=$1 F3DG_RENDER_PACK_TH=$2 python bench.py --full $B > $O/c2_k$1_th$2.log 2>&1
+  F3DG_RENDER_KERNEL=$1 F3DG_RENDER_PACK_TH=$2 python bench.py --full $B --data real > $O/real_k$1_th$2.log 2>&1
+  F3DG_RENDER_KERNEL=$1 F3DG_RENDER_PACK_TH=$2 python bench.py --full $B --render-mode exact > $O/c2x_k$1_th$2.log 2>&1
+  F3DG_RENDER_KERNEL=$1 F3DG_RENDER_PACK_TH=$2 python bench.py --full $B --render-mode exact --data real > $O/realx_k$1_th$2.log 2>&1
 done
 python - <<'PY'
 import json, glob, os

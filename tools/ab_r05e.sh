@@ -4,8 +4,8 @@ export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r05_hoist; mkdir -p $O; 
 timeout 300 python -m pytest tests/test_raster_forward_gpu.py -x -q -m gpu -k "hoist" 2>&1 | tail -2
 B="--no-cpu-baseline --no-exact --no-d2h --steps 10 --warmup 3"
 for i in 1 2 3; do for h in 0 1; do
-  F3DG_PRE_HOIST=$h timeout 200 python bench.py $B > $O/c2_h${h}_$i.log 2>&1
-  F3DG_PRE_HOIST=$h timeout 200 python bench.py $B --data real > $O/real_h${h}_$i.log 2>&1
+  F3DG_PRE_HOIST=$h timeout 200 python bench.py --full $B > $O/c2_h${h}_$i.log 2>&1
+  F3DG_PRE_HOIST=$h timeout 200 python bench.py --full $B --data real > $O/real_h${h}_$i.log 2>&1
 done; done
 python - <<'PY'
 import json, glob, os

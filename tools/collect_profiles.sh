@@ -3,8 +3,8 @@
 # (separate runs, PMC only) of the same bench command. Results under gpurun_out/<tag>/.
 TAG=${1:-prof}
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd /tmp
-python $R/bench.py > $O/bench_default.log 2>&1
-B="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+python $R/bench.py --full > $O/bench_default.log 2>&1
+B="python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B > $O/bench_under_rocprof.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o bench -- $B > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o bench -- $B > /dev/null 2>&1

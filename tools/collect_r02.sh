@@ -4,11 +4,11 @@
 # with its kernel stats and PMC passes, C4-shaped lines (fp32 / bf16 backbone), the parity report and the GPU test log.
 TAG=${1:-r02}
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd /tmp
-python $R/bench.py > $O/bench_default.log 2>&1
-python $R/bench.py --render-mode exact --no-cpu-baseline > $O/bench_exact.log 2>&1
-python $R/bench.py --tile-cull 0 --no-cpu-baseline > $O/bench_nocull.log 2>&1
+python $R/bench.py --full > $O/bench_default.log 2>&1
+python $R/bench.py --full --render-mode exact --no-cpu-baseline > $O/bench_exact.log 2>&1
+python $R/bench.py --full --tile-cull 0 --no-cpu-baseline > $O/bench_nocull.log 2>&1
 python $R/tools/bench_small_calls.py > $O/small_calls.log 2>&1
-B="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-d2h"
+B="python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-d2h"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B > $O/bench_under_rocprof.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o bench -- $B > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o bench -- $B > /dev/null 2>&1

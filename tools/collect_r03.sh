@@ -5,14 +5,14 @@
 # integrate, the parity report and the GPU test log.
 TAG=${1:-r03}
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd /tmp
-python $R/bench.py > $O/bench_default.log 2>&1
-python $R/bench.py --sigma0 0.05 --no-cpu-baseline > $O/bench_sigma005.log 2>&1
-python $R/bench.py --tile-cull 0 --no-cpu-baseline > $O/bench_nocull.log 2>&1
-python $R/bench.py --gaussians 589824 --views 128 --no-cpu-baseline > $O/bench_589k.log 2>&1
+python $R/bench.py --full > $O/bench_default.log 2>&1
+python $R/bench.py --full --sigma0 0.05 --no-cpu-baseline > $O/bench_sigma005.log 2>&1
+python $R/bench.py --full --tile-cull 0 --no-cpu-baseline > $O/bench_nocull.log 2>&1
+python $R/bench.py --full --gaussians 589824 --views 128 --no-cpu-baseline > $O/bench_589k.log 2>&1
 python $R/bench.py --workload dropin --views 60 > $O/bench_dropin.log 2>&1
 python $R/bench.py --workload dropin --views 60 --gaussians 589824 > $O/bench_dropin_589k.log 2>&1
 python $R/tools/bench_small_calls.py > $O/small_calls.log 2>&1
-B="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-d2h --no-exact"
+B="python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-d2h --no-exact"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B > $O/bench_under_rocprof.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o bench -- $B > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o bench -- $B > /dev/null 2>&1
@@ -21,18 +21,18 @@ rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_L
 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_grbm -o bench -- $B > /dev/null 2>&1
 rm -f $O/stats/bench_kernel_trace.csv
 # the exact-arithmetic kernel of the same workload
-BX="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-d2h --render-mode exact"
+BX="python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-d2h --render-mode exact"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_exact -o bench -- $BX > /dev/null 2>&1
 rm -f $O/stats_exact/bench_kernel_trace.csv
 # sigma0 = 0.05
-BS="python $R/bench.py --sigma0 0.05 --steps 3 --warmup 1 --no-cpu-baseline --no-d2h --no-exact"
+BS="python $R/bench.py --full --sigma0 0.05 --steps 3 --warmup 1 --no-cpu-baseline --no-d2h --no-exact"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s005_stats -o bench -- $BS > $O/s005_under_rocprof.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/s005_pmc_fetch -o bench -- $BS > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/s005_pmc_write -o bench -- $BS > /dev/null 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU --output-format csv -d $O/s005_pmc_sq -o bench -- $BS > /dev/null 2>&1
 rm -f $O/s005_stats/bench_kernel_trace.csv
 # larger set: kernel stats
-BL="python $R/bench.py --gaussians 589824 --views 128 --steps 3 --warmup 1 --no-cpu-baseline --no-d2h --no-exact"
+BL="python $R/bench.py --full --gaussians 589824 --views 128 --steps 3 --warmup 1 --no-cpu-baseline --no-d2h --no-exact"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/l589_stats -o bench -- $BL > /dev/null 2>&1
 rm -f $O/l589_stats/bench_kernel_trace.csv
 # small call: kernel stats of the one-view path

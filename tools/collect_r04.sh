@@ -9,15 +9,15 @@ export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd /t
 SQ1="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU"
 SQ2="SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VMEM_RD"
 rocprofv3 -L 2>/dev/null | grep -o "SQ_INSTS_VALU[A-Z0-9_]*" | sort -u > $O/avail_valu_counters.txt
-python $R/bench.py > $O/bench_default.log 2>&1
-python $R/bench.py --sigma0 0.05 --no-cpu-baseline > $O/bench_sigma005.log 2>&1
-python $R/bench.py --tile-cull 0 --no-cpu-baseline > $O/bench_nocull.log 2>&1
-python $R/bench.py --gaussians 589824 --views 128 --no-cpu-baseline > $O/bench_589k.log 2>&1
-python $R/bench.py --data real > $O/bench_real.log 2>&1
+python $R/bench.py --full > $O/bench_default.log 2>&1
+python $R/bench.py --full --sigma0 0.05 --no-cpu-baseline > $O/bench_sigma005.log 2>&1
+python $R/bench.py --full --tile-cull 0 --no-cpu-baseline > $O/bench_nocull.log 2>&1
+python $R/bench.py --full --gaussians 589824 --views 128 --no-cpu-baseline > $O/bench_589k.log 2>&1
+python $R/bench.py --full --data real > $O/bench_real.log 2>&1
 python $R/bench.py --workload dropin --views 60 > $O/bench_dropin.log 2>&1
 python $R/bench.py --workload dropin --views 60 --gaussians 589824 > $O/bench_dropin_589k.log 2>&1
 python $R/tools/bench_small_calls.py > $O/small_calls.log 2>&1
-B="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-d2h --no-exact"
+B="python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-d2h --no-exact"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B > $O/bench_under_rocprof.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o bench -- $B > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o bench -- $B > /dev/null 2>&1
@@ -29,7 +29,7 @@ F64=$(grep -E "F64|TRANS" $O/avail_valu_counters.txt | head -8 | tr '\n' ' ')
 [ -n "$F64" ] && rocprofv3 --pmc $F64 --output-format csv -d $O/pmc_f64 -o bench -- $B > /dev/null 2>&1
 rm -f $O/stats/bench_kernel_trace.csv
 # the exact-arithmetic kernel of the same workload
-BX="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-d2h --render-mode exact"
+BX="python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-d2h --render-mode exact"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_exact -o bench -- $BX > /dev/null 2>&1
 rm -f $O/stats_exact/bench_kernel_trace.csv
 # BEFORE: round 3's compositing arithmetic and LDS reads, same box, same run
@@ -42,17 +42,17 @@ rocprofv3 --pmc $SQ2 --output-format csv -d $O/before_pmc_sq2 -o bench -- $B > /
 rm -f $O/before_stats/bench_kernel_trace.csv
 cd $R; touch f3d-gaus_amd/csrc/f3dg_render.hip; python -c "import importlib; importlib.import_module('f3d-gaus_amd.build').build()" >> $O/build_before.log 2>&1; cd /tmp
 # sigma0 = 0.05
-BS="python $R/bench.py --sigma0 0.05 --steps 3 --warmup 1 --no-cpu-baseline --no-d2h --no-exact"
+BS="python $R/bench.py --full --sigma0 0.05 --steps 3 --warmup 1 --no-cpu-baseline --no-d2h --no-exact"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s005_stats -o bench -- $BS > $O/s005_under_rocprof.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/s005_pmc_fetch -o bench -- $BS > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/s005_pmc_write -o bench -- $BS > /dev/null 2>&1
 rocprofv3 --pmc $SQ1 --output-format csv -d $O/s005_pmc_sq -o bench -- $BS > /dev/null 2>&1
 rm -f $O/s005_stats/bench_kernel_trace.csv
 # larger set and the real merged set: kernel stats (+ SQ counters of the real one)
-BL="python $R/bench.py --gaussians 589824 --views 128 --steps 3 --warmup 1 --no-cpu-baseline --no-d2h --no-exact"
+BL="python $R/bench.py --full --gaussians 589824 --views 128 --steps 3 --warmup 1 --no-cpu-baseline --no-d2h --no-exact"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/l589_stats -o bench -- $BL > /dev/null 2>&1
 rm -f $O/l589_stats/bench_kernel_trace.csv
-BR="python $R/bench.py --data real --steps 3 --warmup 1 --no-cpu-baseline --no-d2h --no-exact"
+BR="python $R/bench.py --full --data real --steps 3 --warmup 1 --no-cpu-baseline --no-d2h --no-exact"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/real_stats -o bench -- $BR > $O/real_under_rocprof.log 2>&1
 rocprofv3 --pmc $SQ1 --output-format csv -d $O/real_pmc_sq -o bench -- $BR > /dev/null 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/real_pmc_fetch -o bench -- $BR > /dev/null 2>&1

@@ -6,14 +6,14 @@
 TAG=${1:-r05}
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 T="timeout 400"
-$T python bench.py > $O/bench_default.log 2>&1
-$T python bench.py --data real > $O/bench_real.log 2>&1
-$T python bench.py --data real --channels rgb_depth_alpha --no-cpu-baseline > $O/bench_real_lean.log 2>&1
-$T python bench.py --channels rgb_depth_alpha --no-cpu-baseline > $O/bench_lean.log 2>&1
-F3DG_RENDER_PACK=0 $T python bench.py --no-cpu-baseline > $O/bench_default_pack0.log 2>&1
-F3DG_RENDER_PACK=0 $T python bench.py --data real --no-cpu-baseline > $O/bench_real_pack0.log 2>&1
-$T python bench.py --sigma0 0.05 --no-cpu-baseline > $O/bench_sigma005.log 2>&1
-$T python bench.py --gaussians 589824 --views 128 --no-cpu-baseline > $O/bench_589k.log 2>&1
+$T python bench.py --full > $O/bench_default.log 2>&1
+$T python bench.py --full --data real > $O/bench_real.log 2>&1
+$T python bench.py --full --data real --channels rgb_depth_alpha --no-cpu-baseline > $O/bench_real_lean.log 2>&1
+$T python bench.py --full --channels rgb_depth_alpha --no-cpu-baseline > $O/bench_lean.log 2>&1
+F3DG_RENDER_PACK=0 $T python bench.py --full --no-cpu-baseline > $O/bench_default_pack0.log 2>&1
+F3DG_RENDER_PACK=0 $T python bench.py --full --data real --no-cpu-baseline > $O/bench_real_pack0.log 2>&1
+$T python bench.py --full --sigma0 0.05 --no-cpu-baseline > $O/bench_sigma005.log 2>&1
+$T python bench.py --full --gaussians 589824 --views 128 --no-cpu-baseline > $O/bench_589k.log 2>&1
 $T python bench.py --workload dropin --views 60 > $O/bench_dropin.log 2>&1
 $T python bench.py --workload dropin --views 60 --render-mode exact > $O/bench_dropin_exact.log 2>&1
 [ -x tools/micro/issue_rate ] || /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/micro/issue_rate.hip -o tools/micro/issue_rate > /dev/null 2>&1; timeout 60 tools/micro/issue_rate > $O/issue_rate.log 2>&1
@@ -23,7 +23,7 @@ $T python bench.py --workload c4 --images 16 --steps 2 --warmup 1 > $O/bench_c4_
 $T python bench.py --workload c4 --images 16 --steps 2 --warmup 1 --backbone-chunk 0 > $O/bench_c4_fp32_chunk0.log 2>&1
 # kernel stats of the default command
 cd /tmp
-B="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-d2h --no-exact"
+B="python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-d2h --no-exact"
 $T rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B > $O/bench_under_rocprof.log 2>&1
 rm -f $O/stats/bench_kernel_trace.csv
 cd $R

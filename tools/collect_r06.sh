@@ -7,24 +7,24 @@ export TMPDIR=/tmp; R=/root/repo; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R; ulim
 T="timeout 400"
 export F3DG_BENCH_PMC=0        # only the two full bench lines below measure roofline.traffic live (two rocprofv3 child runs each)
 python -c "import f3dgaus_amd; from f3dgaus_amd import _lib; print(_lib.lib().f3dg_version().decode())" 2>/dev/null > $O/version.txt
-F3DG_BENCH_PMC=1 timeout 900 python bench.py > $O/bench_default.log 2>&1
-$T python bench.py --no-cpu-baseline --d2h-issue thread > $O/bench_default_thread.log 2>&1
-$T python bench.py --no-cpu-baseline --d2h-issue main > $O/bench_default_main2.log 2>&1
-F3DG_BENCH_PMC=1 timeout 900 python bench.py --data real > $O/bench_real.log 2>&1
-$T python bench.py --data real --scan 1 --no-cpu-baseline > $O/bench_real_scan.log 2>&1
-$T python bench.py --data real --channels rgb_depth_alpha --no-cpu-baseline > $O/bench_real_lean.log 2>&1
-$T python bench.py --data real --channels rgb_depth_alpha --scan 1 --no-cpu-baseline > $O/bench_real_lean_scan.log 2>&1
-$T python bench.py --scan 1 --no-cpu-baseline > $O/bench_default_scan.log 2>&1
-$T python bench.py --channels rgb_depth_alpha --no-cpu-baseline > $O/bench_lean.log 2>&1
-$T python bench.py --sigma0 0.05 --no-cpu-baseline > $O/bench_sigma005.log 2>&1
-$T python bench.py --gaussians 589824 --views 128 --no-cpu-baseline > $O/bench_589k.log 2>&1
+F3DG_BENCH_PMC=1 timeout 900 python bench.py --full > $O/bench_default.log 2>&1
+$T python bench.py --full --no-cpu-baseline --d2h-issue thread > $O/bench_default_thread.log 2>&1
+$T python bench.py --full --no-cpu-baseline --d2h-issue main > $O/bench_default_main2.log 2>&1
+F3DG_BENCH_PMC=1 timeout 900 python bench.py --full --data real > $O/bench_real.log 2>&1
+$T python bench.py --full --data real --scan 1 --no-cpu-baseline > $O/bench_real_scan.log 2>&1
+$T python bench.py --full --data real --channels rgb_depth_alpha --no-cpu-baseline > $O/bench_real_lean.log 2>&1
+$T python bench.py --full --data real --channels rgb_depth_alpha --scan 1 --no-cpu-baseline > $O/bench_real_lean_scan.log 2>&1
+$T python bench.py --full --scan 1 --no-cpu-baseline > $O/bench_default_scan.log 2>&1
+$T python bench.py --full --channels rgb_depth_alpha --no-cpu-baseline > $O/bench_lean.log 2>&1
+$T python bench.py --full --sigma0 0.05 --no-cpu-baseline > $O/bench_sigma005.log 2>&1
+$T python bench.py --full --gaussians 589824 --views 128 --no-cpu-baseline > $O/bench_589k.log 2>&1
 $T python bench.py --workload dropin --views 60 > $O/bench_dropin.log 2>&1
 $T python bench.py --workload c5 --steps 3 --warmup 1 > $O/bench_c5.log 2>&1
 $T python bench.py --workload c4 --images 16 --steps 2 --warmup 1 > $O/bench_c4_fp32.log 2>&1
 python tools/scan_dist_probe.py 2>&1 | grep -v amdgpu.ids > $O/scan_dist_probe.log
 # kernel stats of the default command
 cd /tmp
-B="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-d2h --no-exact"
+B="python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-d2h --no-exact"
 $T rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B > $O/bench_under_rocprof.log 2>&1
 rm -f $O/stats/bench_kernel_trace.csv
 cd $R

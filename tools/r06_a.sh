@@ -2,10 +2,10 @@
 # round 6, call A (lab build): baseline lines on this box, who issues the frame copy, staging-only replay, FETCH_SIZE calibration
 cd /root/repo; export TMPDIR=/tmp; ulimit -c 0; O=gpurun_out/r06a; mkdir -p $O; rm -rf $O/*
 T="timeout 400"
-$T python bench.py --no-cpu-baseline --steps 20 --d2h-issue main > $O/bench_c2_main.log 2>&1
-$T python bench.py --no-cpu-baseline --steps 20 --d2h-issue thread > $O/bench_c2_thread.log 2>&1
-$T python bench.py --no-cpu-baseline --steps 20 --d2h-issue main > $O/bench_c2_main2.log 2>&1
-$T python bench.py --no-cpu-baseline --data real > $O/bench_real.log 2>&1
+$T python bench.py --full --no-cpu-baseline --steps 20 --d2h-issue main > $O/bench_c2_main.log 2>&1
+$T python bench.py --full --no-cpu-baseline --steps 20 --d2h-issue thread > $O/bench_c2_thread.log 2>&1
+$T python bench.py --full --no-cpu-baseline --steps 20 --d2h-issue main > $O/bench_c2_main2.log 2>&1
+$T python bench.py --full --no-cpu-baseline --data real > $O/bench_real.log 2>&1
 $T python tools/replay_staging.py --data real > $O/replay_real.log 2>&1
 $T python tools/replay_staging.py --data real --channels rgb_depth_alpha > $O/replay_real_lean.log 2>&1
 $T python tools/replay_staging.py --data synthetic --views 120 > $O/replay_c2.log 2>&1
