@@ -160,9 +160,11 @@ __device__ __forceinline__ bool f3dg_pair_apply(F3dgPixel& st, unsigned contribu
 }
 
 // Branch-free form of the fast recurrence for the blend trips of the packed schedule (FAST only): a pair that is not blended -- alpha
-// == 0, or the pair that saturates the pixel -- runs the same instructions with weight 0 (its six numbers must then be finite: the
-// caller zeroes them for alpha == 0). Every accumulator receives fma(x, 0, acc) = acc, so the results are those of f3dg_pair_apply to
-// the bit; what goes is the exec-mask bookkeeping of two nested branches (~20 scalar instructions per trip of a divergent loop).
+// == 0, or the pair that saturates the pixel -- runs the same instructions with weight 0 (its depth and normal must then be finite: the
+// caller zeroes them for alpha == 0; its colour is replaced by 0 here, since the caller's colours may hold Inf or NaN and Inf * 0 = NaN
+// would reach a pixel the reference never blends the pair into). Every accumulator receives fma(x, 0, acc) = acc, so the results are
+// those of f3dg_pair_apply to the bit; what goes is the exec-mask bookkeeping of two nested branches (~20 scalar instructions per trip
+// of a divergent loop).
 template <bool NORMAL, bool DIST>
 __device__ __forceinline__ bool f3dg_pair_apply_flat(F3dgPixel& st, unsigned contributor, const F3dgPair& pr, float cr, float cg, float cb)
 {
@@ -182,9 +184,9 @@ __device__ __forceinline__ bool f3dg_pair_apply_flat(F3dgPixel& st, unsigned con
         st.dist1 = fmaf(m, w, st.dist1);
         st.dist2 = fmaf(m2, w, st.dist2);
     }
-    st.C0 = fmaf(cr, w, st.C0);
-    st.C1 = fmaf(cg, w, st.C1);
-    st.C2 = fmaf(cb, w, st.C2);
+    st.C0 = fmaf(go ? cr : 0.0f, w, st.C0);
+    st.C1 = fmaf(go ? cg : 0.0f, w, st.C1);
+    st.C2 = fmaf(go ? cb : 0.0f, w, st.C2);
     if (NORMAL) {
         st.C3 = fmaf(pr.nn0, w, st.C3);
         st.C4 = fmaf(pr.nn1, w, st.C4);

@@ -294,19 +294,22 @@ render5_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                 constexpr int KM = 4 + (NORMAL ? 3 : 0) + (DIST ? 1 : 0);
                 static_assert(KM == 4 || KM == 8, "seg_sums is written for the lean (rgb, alpha) and the full channel set");
                 float v[KM];
-                v[0] = q3.x * w; v[1] = q3.y * w; v[2] = q3.z * w; v[3] = w;
+                // (a pair of weight 0 adds 0 by selection: an Inf colour times 0 would put NaN into its pixel, or through the scan into the next)
+                const bool blend = w != 0.0f;
+                v[0] = (blend ? q3.x : 0.0f) * w; v[1] = (blend ? q3.y : 0.0f) * w; v[2] = (blend ? q3.z : 0.0f) * w; v[3] = w;
                 if constexpr (NORMAL) { v[4] = pr.nn0 * w; v[5] = pr.nn1 * w; v[6] = pr.nn2 * w; }
                 float a[2] = { 0.0f, 0.0f };
                 if constexpr (DIST) {
                     // forward.cu:552-557: error = m^2 (1 - T) + dist2 - 2 m dist1 with the running sums IN FRONT of the pair
                     const float mw = pr.m * w, m2w = pr.m * mw;
                     a[0] = mw; a[1] = m2w;
-                    seg_sums(a, sf);
+                    seg_sums_gated(a, sf);
                     const float E1 = (a[0] - mw) + D1, E2 = (a[1] - m2w) + D2;
                     const float error = fmaf(-2.0f * pr.m, E1, fmaf(pr.m * pr.m, 1.0f - Tb, E2));
                     v[KM - 1] = error * w;
                 }
-                seg_sums(v, sf);
+                // (the gated scan throughout: the per-batch choice of seg_sums costs this kernel 64-VGPR spills)
+                seg_sums_gated(v, sf);
 
                 // ---- the owning lanes take their run's totals from its last lane in this batch
                 const bool mine_in = rs < qh + nb && re > qh;
@@ -497,7 +500,9 @@ render5p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                 const float Tb = Tf * (sub >= 1u ? Psh : 1.0f), tT = Tf * Pi;
                 const bool killed = !(tT >= 0.0001f);         // the stop (forward.cu:543-548), or an entry behind it
                 const float w = killed ? 0.0f : alpha * Tb;
-                C0 = fmaf(q3.x, w, C0); C1 = fmaf(q3.y, w, C1); C2 = fmaf(q3.z, w, C2); C7 += w;
+                // (a lane of weight 0 -- killed, below 1/255, or without an entry -- adds 0 by selection, whatever colour it read)
+                const bool blend = w != 0.0f;
+                C0 = fmaf(blend ? q3.x : 0.0f, w, C0); C1 = fmaf(blend ? q3.y : 0.0f, w, C1); C2 = fmaf(blend ? q3.z : 0.0f, w, C2); C7 += w;
                 C3 = fmaf(pr.nn0, w, C3); C4 = fmaf(pr.nn1, w, C4); C5 = fmaf(pr.nn2, w, C5);
                 // distortion (forward.cu:552-557): the running sums IN FRONT of this entry = the pixel's + the group's earlier lanes'
                 const float a1 = pr.m * w, a2 = pr.m * a1;

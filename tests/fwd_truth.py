@@ -19,7 +19,9 @@ def _rot(q):
     return R
 
 
-def render_fp64(scene, view=0):
+def render_fp64(scene, view=0, blended=False):
+    """The nine channels [9, H, W]; with blended=True also the blend record: a list, front to back, of (Gaussian id, flat indices of
+    the pixels it is blended into)."""
     f = lambda t: None if t is None else np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float64)
     W, H = scene["W"], scene["H"]
     p, op, sc, q = f(scene["means3D"]), f(scene["opacities"]).reshape(-1), f(scene["scales"]), f(scene["rotations"])
@@ -88,6 +90,7 @@ def render_fp64(scene, view=0):
     tile_x, tile_y = xs // 16, ys // 16
     T = np.ones((H, W)); Cacc = np.zeros((8, H, W)); d1 = np.zeros((H, W)); d2 = np.zeros((H, W)); dist = np.zeros((H, W))
     done = np.zeros((H, W), bool)
+    record = []
     order = np.argsort(pv[:, 2].astype(np.float32), kind="stable")       # keys are the float32 depth bits, ties by index
     for g in order:
         if not vis[g]:
@@ -114,6 +117,8 @@ def render_fp64(scene, view=0):
             continue
         mp = (100.0 * t - 20.0) / (99.8 * t)
         ln = np.sqrt(n0 * n0 + n1 * n1 + n2 * n2 + 1e-7)
+        if blended:
+            record.append((int(g), np.flatnonzero(m)))
         w = np.where(m, alpha * T, 0.0)
         A = 1.0 - T
         err = mp * mp * A + d2 - 2.0 * mp * d1
@@ -128,4 +133,38 @@ def render_fp64(scene, view=0):
     out[:3] = Cacc[:3] + T[None] * bg[:, None, None]
     out[3:8] = Cacc[3:8]
     out[8] = dist / ((1.0 - T) * (1.0 - T) + 1e-7)
-    return out
+    return (out, record) if blended else out
+
+
+def run_census(record, W, H, batch=64):
+    """The run structure the segmented-scan kernels see, per 8 x 8 quadrant, from render_fp64's blend record. A quadrant's entries are
+    the Gaussians blended into at least one of its pixels; an entry's RUN is its pixels in the quadrant. The dense backward concatenates
+    the runs back to front and cuts them into batches of `batch` pairs; the split-pixel forward scans the pairs of one pixel.
+    Returns run_lengths (every run of every quadrant), entries (contributing entries per quadrant), straddling (runs that cross a batch
+    boundary), max_runs_ending (most runs ending in one batch), pairs (pairs per quadrant), pairs_per_pixel [H, W], partial (quadrants
+    with fewer than 64 pixels)."""
+    qx, qy = (W + 7) // 8, (H + 7) // 8
+    quads = [[] for _ in range(qx * qy)]
+    for _, pix in record:
+        q = (pix // W) // 8 * qx + (pix % W) // 8
+        ids, cnt = np.unique(q, return_counts=True)
+        for i, c in zip(ids, cnt):
+            quads[i].append(int(c))
+    run_lengths, entries, pairs = [], [], []
+    straddling, max_runs_ending = 0, 0
+    for runs in quads:
+        entries.append(len(runs))
+        pairs.append(int(sum(runs)))
+        run_lengths.extend(runs)
+        if not runs:
+            continue
+        ends = np.cumsum(runs[::-1])                     # back to front
+        starts = ends - np.array(runs[::-1])
+        straddling += int(np.sum(starts // batch != (ends - 1) // batch))
+        max_runs_ending = max(max_runs_ending, int(np.bincount((ends - 1) // batch).max()))
+    ppp = np.zeros(H * W, np.int64)
+    for _, pix in record:
+        ppp[pix] += 1
+    partial = sum(1 for y in range(qy) for x in range(qx) if min(8, W - 8 * x) * min(8, H - 8 * y) < 64)
+    return dict(run_lengths=np.array(run_lengths, np.int64), entries=np.array(entries, np.int64), straddling=straddling,
+                max_runs_ending=max_runs_ending, pairs=np.array(pairs, np.int64), pairs_per_pixel=ppp.reshape(H, W), partial=partial)

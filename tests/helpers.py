@@ -182,3 +182,33 @@ def assert_render_parity(hip_out, ora_out, label="", dist_big_rtol=1e-3):
     if big.any():
         assert frac_within(hip_out[8][big], ora_out[8][big], 0.0, dist_big_rtol) >= 0.999, \
             f"{label} distortion (rel {dist_big_rtol:g} on {int(big.sum())} px): {frac_within(hip_out[8][big], ora_out[8][big], 0.0, dist_big_rtol)}"
+
+
+def _merge_scenes(a, b):
+    """The Gaussians of two scenes with the same cameras, a's first."""
+    out = dict(a)
+    for k in ("means3D", "opacities", "scales", "rotations", "colors_precomp"):
+        out[k] = torch.cat([a[k], b[k]], 0).contiguous()
+    out["P"] = a["P"] + b["P"]
+    return out
+
+
+def make_run_scene(name):
+    """Scenes built for the run structure of the segmented-scan kernels (csrc/f3dg_segscan.h; census: fwd_truth.run_census):
+    wall      large, low-opacity Gaussians stacked in depth: every entry covers whole quadrants (runs of 64) and T stays above 1e-4
+              for hundreds of entries, so the lists run long and the staging rings wrap many times
+    confetti  pixel-ordered splats of sigma0 0.005: runs of 1-4 pixels, many runs ending in one batch
+    mixed     wall + confetti: every run length 1..64, runs that straddle batch boundaries
+    odd       mixed at 73 x 41 (partial quadrants and tiles), three views"""
+    res, views = ((73, 41), 3) if name == "odd" else ((64, 64), 1)
+    if name in ("wall", "mixed", "odd"):
+        wall = make_scene(P=900, res=res, s0=0.25, seed=41, view="oblique", n_views=views, colors_precomp=True)
+        wall["opacities"] = torch.full_like(wall["opacities"], 0.012)
+        if name == "wall":
+            return wall
+    confetti = make_scene(P=64 * 64, res=(64, 64), s0=0.005, seed=43, view="oblique", n_views=views, colors_precomp=True, pixel_ordered=True)
+    if name == "confetti":
+        return confetti
+    for k in ("W", "H"):
+        confetti[k] = wall[k]
+    return _merge_scenes(wall, confetti)
