@@ -17,8 +17,6 @@ ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fgpu-rdc" if False else "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
-if os.environ.get("F3DG_LAB"):          # builder-side experiments: diagnostic kernels and A/B variants no caller of the library reaches
-    FLAGS.append("-DF3DG_LAB")
 
 
 # Per-file extras. -fno-slp-vectorize: the SLP vectorizer pairs the float32 multiplies / adds of the per-pixel quadric into
@@ -44,8 +42,8 @@ STAMP = os.path.join(CSRC, ".build_flags")      # the flag set the objects in th
 
 
 def build(force=False, verbose=False):
-    # a tree that holds the objects of the OTHER flag set (a lab build left behind, or the default one when F3DG_LAB is asked for) is rebuilt
-    # as a whole: the driver's build() must never pick up a -DF3DG_LAB library because its objects look newer than the sources
+    # a tree that holds the objects of another flag set (F3DG_EXTRA_* overrides left behind) is rebuilt as a whole: the driver's build()
+    # must never pick up objects compiled with other flags because they look newer than the sources
     stamp = " ".join(FLAGS) + " | " + " ".join("%s:%s" % (k, " ".join(v)) for k, v in sorted(EXTRA_FLAGS.items()))
     try:
         if open(STAMP).read() != stamp:

@@ -90,7 +90,6 @@ void f3dg_prof_bwd_mark(int slot, int stage_done, hipStream_t s)
 
 int g_f3dg_small_path = 1;
 int g_f3dg_small_path_aux = 1;       // forwards that keep the auxiliary planes (a backward follows) may take the small-call path too
-int g_f3dg_small_debug = 0;
 namespace {
 // shapes (P, n_views, W, H) whose small-call path overflowed a tile list: they take the general path from then on
 // (the library is called from several host threads -- ctypes releases the GIL -- so the process-global tables take a mutex)
@@ -113,33 +112,17 @@ void small_disable(unsigned P, unsigned V, unsigned W, unsigned H)
 }
 } // namespace
 std::atomic<unsigned long long> g_f3dg_kernel_launches{0};      // host-side counter of F3DG_KLAUNCH
-int g_f3dg_render_pretest = 1;
-int g_f3dg_render_cull = 1;
-int g_f3dg_render_queue = 1;
 int g_f3dg_render_fast = 1;
-int g_f3dg_render_kernel = 3;
 int g_f3dg_render_pack = -1;
-int g_f3dg_render_dma = 1;
-int g_f3dg_render_replay = 0;
-int g_f3dg_render_wpb = 1;
 int g_f3dg_render_count = 0;
-#define F3DG_RENDER_TAIL_DEFAULT 0
-int g_f3dg_render_tail = F3DG_RENDER_TAIL_DEFAULT;
-int g_f3dg_render_slide = 1;
 int g_f3dg_render_lowocc = 1;
 #define F3DG_RENDER_UNROLL_DEFAULT -1
 #define F3DG_RENDER_SPLIT_DEFAULT -1
 int g_f3dg_render_split = F3DG_RENDER_SPLIT_DEFAULT;
 int g_f3dg_render_unroll = F3DG_RENDER_UNROLL_DEFAULT;
-int g_f3dg_render_lds_pad = 0;
 int g_f3dg_bwd_occ = 5;
-int g_f3dg_render_round = 192;
-int g_f3dg_sort_wide_groups = 0;
-int g_f3dg_sort_fused_rects = 0;
-int g_f3dg_pre_hoist = 0;
 int g_f3dg_tile_cull = 1;            // instantiate a Gaussian only in the tiles its conservative ellipse reaches (0: the reference's tile lists)
-int g_f3dg_pre_order = 0;             // projection grid: 0 view-major (a view's chunks follow each other), 1 chunk-major (a chunk's views do)
-int g_f3dg_debug_skip_all = 0;       // experiment switch: pre-test threshold = +inf (measures the loop skeleton)
+int g_f3dg_reference_kernels = 0;
 
 extern "C" int f3dg_set_option(const char* name, int value)
 {
@@ -161,36 +144,9 @@ extern "C" int f3dg_set_option(const char* name, int value)
     // diagnostics
     if (strcmp(name, "render_count") == 0) { g_f3dg_render_count = value != 0; return F3DG_OK; }
     if (strcmp(name, "time_launches") == 0) { g_f3dg_time_launches = value != 0; return F3DG_OK; }
-#ifndef F3DG_LAB
+    if (strcmp(name, "reference_kernels") == 0) { g_f3dg_reference_kernels = value != 0; return F3DG_OK; }
     // small launches: 1 = producer + consumer waves (render3p), 2 / 3 = consumer + evaluators + producer (render3q, one view); -1 / 0 = by arithmetic
     if (strcmp(name, "render_split") == 0) { g_f3dg_render_split = value < 1 ? F3DG_RENDER_SPLIT_DEFAULT : value > 3 ? 3 : value; return F3DG_OK; }
-#else
-    // ---- lab builds (-DF3DG_LAB: builder-side experiments; the default library neither compiles the kernels behind these nor knows the names)
-    if (strcmp(name, "render_split") == 0) { g_f3dg_render_split = value < 0 ? F3DG_RENDER_SPLIT_DEFAULT : value > 3 ? 3 : value; return F3DG_OK; }   // 0: render3l
-    if (strcmp(name, "render_kernel") == 0) {       // 1 / 2 / 3: the kernel generations; 4: shorthand for render3s + the packed kernel everywhere
-        g_f3dg_render_kernel = value == 1 ? 1 : value == 2 ? 2 : 3;
-        g_f3dg_render_pack = value == 4 ? 1 : -1;   // (leaving the shorthand restores the default: ADVICE r05)
-        return F3DG_OK;
-    }
-    if (strcmp(name, "tile_split") == 0) { g_f3dg_tile_split = value != 0; return F3DG_OK; }
-    if (strcmp(name, "render_scan_lanes") == 0) { g_f3dg_render_scan_lanes = value == 2 ? 2 : 4; return F3DG_OK; }
-    if (strcmp(name, "render_pretest") == 0) { g_f3dg_render_pretest = value != 0; return F3DG_OK; }
-    if (strcmp(name, "render_queue") == 0) { g_f3dg_render_queue = value != 0; return F3DG_OK; }
-    if (strcmp(name, "render_cull") == 0) { g_f3dg_render_cull = value != 0; return F3DG_OK; }
-    if (strcmp(name, "render_slide") == 0) { g_f3dg_render_slide = value != 0; return F3DG_OK; }
-    if (strcmp(name, "render_tail") == 0) { g_f3dg_render_tail = value < 0 ? F3DG_RENDER_TAIL_DEFAULT : value > 64 ? 64 : value; return F3DG_OK; }
-    if (strcmp(name, "render_wpb") == 0) { g_f3dg_render_wpb = value == 4 ? 4 : 1; return F3DG_OK; }
-    if (strcmp(name, "render_dma") == 0) { g_f3dg_render_dma = value != 0; return F3DG_OK; }
-    if (strcmp(name, "render_round") == 0) { g_f3dg_render_round = value == 256 ? 256 : 192; return F3DG_OK; }
-    if (strcmp(name, "render_lds_pad") == 0) { g_f3dg_render_lds_pad = value < 0 ? 0 : value; return F3DG_OK; }
-    if (strcmp(name, "render_replay") == 0) { g_f3dg_render_replay = value; return F3DG_OK; }
-    if (strcmp(name, "small_debug") == 0) { g_f3dg_small_debug = value; return F3DG_OK; }
-    if (strcmp(name, "sort_wide_groups") == 0) { g_f3dg_sort_wide_groups = value != 0; return F3DG_OK; }
-    if (strcmp(name, "sort_fused_rects") == 0) { g_f3dg_sort_fused_rects = value != 0; return F3DG_OK; }
-    if (strcmp(name, "pre_hoist") == 0) { g_f3dg_pre_hoist = value != 0; return F3DG_OK; }
-    if (strcmp(name, "pre_order") == 0) { g_f3dg_pre_order = value & 3; return F3DG_OK; }
-    if (strcmp(name, "debug_skip_all") == 0) { g_f3dg_debug_skip_all = value != 0; return F3DG_OK; }
-#endif
     return F3DG_ERR_BAD_ARG;
 }
 
@@ -281,11 +237,7 @@ int f3dg_set_hip_error(hipError_t e, const char* where)
     return F3DG_ERR_HIP;
 }
 
-#ifdef F3DG_LAB
-extern "C" const char* f3dg_version(void) { return "f3dg-hip gfx950 0.2.0 lab"; }
-#else
 extern "C" const char* f3dg_version(void) { return "f3dg-hip gfx950 0.2.0"; }
-#endif
 extern "C" const char* f3dg_last_error(void) { return g_last_error; }
 
 int f3dg_sort_passes(int V, int T);
@@ -320,8 +272,7 @@ F3dgLayout f3dg_layout(int P, int W, int H, int V, long long cap)
     L.offsets = take(VP * sizeof(unsigned));
     L.clamped = take(VP);
     L.rects = take(VP * sizeof(uint2));
-    // (planes 4..6 exist for option sort_fused_rects only -- off by default, 3 x V x P x 4 bytes: 400 MB at C3's 512 views x 65,536)
-    L.gsort = take((g_f3dg_sort_fused_rects ? 7 : 4) * VP * sizeof(unsigned));
+    L.gsort = take(4 * VP * sizeof(unsigned));
     L.scan_tmp = take((size_t)L.scan_tmp_elems * sizeof(unsigned));
     L.keys[0] = take(C * 8);
     L.keys[1] = take(C * 4);
@@ -373,13 +324,6 @@ int run_geometry(hipStream_t s, char* ws, const F3dgLayout& L, int n_views, int 
                  const float* cam_pos, float tan_fovx, float tan_fovy, float focal_x, float focal_y, float kernel_size,
                  int* radii_used, int save_aux, int need_box, int tile_cull, ProfCall* prof, F3dgHeaderInit init, int small = 0)
 {
-    // option pre_hoist: the per-Gaussian scratch (96 bytes each) borrows the backward's float64 accumulator plane, which nothing touches
-    // before f3dg_backward -- if it is large enough (80 bytes per (view, Gaussian): at least ~1.2 views per set) and a Gaussian serves
-    // enough views for the extra pass to pay
-    const int n_sets = views_per_set > 0 ? n_views / views_per_set : 1;
-    float4* hoist = nullptr;
-    if (g_f3dg_pre_hoist && n_views / n_sets >= 4 && (size_t)n_views * 80 >= (size_t)n_sets * 96)
-        hoist = reinterpret_cast<float4*>(ws + L.bwd_acc);
     int rc = f3dg_launch_preprocess(s, n_views, views_per_set, P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs,
                                     cov3D_precomp, colors_precomp, view2gaussian_precomp, viewmatrix, projmatrix,
                                     cam_pos, W, H, tan_fovx, tan_fovy, focal_x, focal_y, kernel_size,
@@ -390,7 +334,7 @@ int run_geometry(hipStream_t s, char* ws, const F3dgLayout& L, int n_views, int 
                                     reinterpret_cast<float4*>(ws + L.cull),
                                     reinterpret_cast<float4*>(ws + L.conic), radii_used,
                                     reinterpret_cast<unsigned*>(ws + L.tiles),
-                                    reinterpret_cast<unsigned char*>(ws + L.clamped), save_aux, tile_cull, init, hoist, n_sets,
+                                    reinterpret_cast<unsigned char*>(ws + L.clamped), save_aux, tile_cull, init,
                                     small ? reinterpret_cast<uint2*>(ws + L.small_boxes) : nullptr);
     if (rc != F3DG_OK) return rc;
     prof_mark(prof, ST_PREPROCESS, s);
@@ -448,10 +392,11 @@ extern "C" int f3dg_forward_sets(void* stream, void* workspace, size_t workspace
     if (n_sets > 1 && (save_aux || view2gaussian_precomp != nullptr)) return F3DG_ERR_BAD_ARG;
     // small-call path (f3dg_small.hip): inference calls of one or two views of a modest set go projection -> per-tile sort -> compositing
     // what this call runs with: the process-wide defaults of f3dg_set_option, overridden by the call's own flags
-    const int fast = (flags & F3DG_FLAG_EXACT) ? 0 : (flags & F3DG_FLAG_FAST) ? 1 : f3dg_render_uses_fast(save_aux);
+    // (option reference_kernels: the plain transcription, which knows the reference's arithmetic only)
+    const int fast = g_f3dg_reference_kernels || (flags & F3DG_FLAG_EXACT) ? 0 : (flags & F3DG_FLAG_FAST) ? 1 : f3dg_render_uses_fast(save_aux);
     const int tile_cull = (flags & F3DG_FLAG_NO_TILE_CULL) ? 0 : g_f3dg_tile_cull;
     const int small = g_f3dg_small_path && !(flags & F3DG_FLAG_NO_SMALL_PATH) && (!save_aux || g_f3dg_small_path_aux) && n_sets == 1 && P > 0 && L.small_cap != 0 &&
-                      g_f3dg_render_kernel == 3 && !small_disabled((unsigned)P, (unsigned)n_views, (unsigned)W, (unsigned)H);
+                      !g_f3dg_reference_kernels && !small_disabled((unsigned)P, (unsigned)n_views, (unsigned)W, (unsigned)H);
     // (the header is initialised by the first workgroup of the projection kernel; without Gaussians there is no such launch)
     const F3dgHeaderInit hinit = { hdr, (unsigned)max_rendered, (unsigned)fast, (unsigned)save_aux, (unsigned)small,
                                    { (unsigned)P, (unsigned)n_views, (unsigned)W, (unsigned)H } };
@@ -476,14 +421,13 @@ extern "C" int f3dg_forward_sets(void* stream, void* workspace, size_t workspace
     rc = run_geometry(s, ws, L, n_views, views_per_set, P, D, M, W, H, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
                       rotations, cov3D_precomp, view2gaussian_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx,
                       tan_fovy, focal_x, focal_y, kernel_size, radii_used, save_aux,
-                      save_aux || g_f3dg_render_kernel == 1 /* the culling box: backward + the pixel-lane kernel */, tile_cull, prof, hinit, small);
+                      save_aux /* the box plane: read by no kernel any more, still written by SAVE_AUX calls */, tile_cull, prof, hinit, small);
     if (rc != F3DG_OK) return rc;
 
     rc = f3dg_launch_render(s, n_views, P, W, H, focal_x, focal_y, hdr,
                               reinterpret_cast<const uint2*>(ws + L.ranges),
                               reinterpret_cast<const unsigned*>(ws + (small ? L.small_list : L.vals[0])),
                               reinterpret_cast<const F3dgRec*>(ws + L.rec),
-                              reinterpret_cast<const float4*>(ws + L.bbox),
                               reinterpret_cast<const float4*>(ws + L.cull), background,
                               (flags & F3DG_FLAG_BG_PER_VIEW) ? 1 : 0, out_color,
                               reinterpret_cast<float*>(ws + L.final_T),

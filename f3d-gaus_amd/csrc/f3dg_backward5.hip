@@ -26,12 +26,8 @@ int g_f3dg_bwd_dense = 1;             // option bwd_dense: 1 (default) = render5
 
 namespace {
 
-#ifndef F3DG_B5_STAGE
 #define F3DG_B5_STAGE 6             // runs whose totals go through LDS together (12: 8.5 ms at C5, 6: 8.0, 3: 8.2 -- LDS decides the occupancy)
-#endif
-#ifndef F3DG_B5_OCC
 #define F3DG_B5_OCC 5               // 96 VGPRs, 8 KB of LDS: five waves per SIMD
-#endif
 
 template <int OCC>
 __global__ void __launch_bounds__(64, OCC)
@@ -44,7 +40,7 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                    const float* __restrict__ final_T, const unsigned* __restrict__ n_contrib,
                    const float* __restrict__ dL_dpixels,
                    float* __restrict__ dL_dmean2D, float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolors,
-                   double* __restrict__ dL_dv2g_acc, int debug_no_atomics)
+                   double* __restrict__ dL_dv2g_acc)
 {
     unsigned view, unit;
     f3dg_xcd_map(blockIdx.x, (unsigned)V, 4u * (unsigned)T, view, unit);
@@ -405,7 +401,7 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                     const unsigned staged = nruns - base < (unsigned)F3DG_B5_STAGE ? nruns - base : (unsigned)F3DG_B5_STAGE;
                     for (unsigned r3 = 0u; r3 < staged; r3 += 3u) {       // three runs per pair of atomic instructions, no waiting in between
                         const unsigned rsel = r3 + el_run;
-                        if (el < 17u && el_run < 3u && rsel < staged && !debug_no_atomics) {
+                        if (el < 17u && el_run < 3u && rsel < staged) {
                             const float v = sOut[rsel][el];
                             const size_t id = (size_t)(unsigned)__float_as_int(sOut[rsel][17]);
                             double* rec = gacc + id * 16;
@@ -442,11 +438,11 @@ int f3dg_launch_render5_bwd(hipStream_t s, int V, int P, int W, int H, int tiles
                             const uint2* ranges, const unsigned* point_list, const unsigned* small_list, const F3dgRec* rec, const float4* cull,
                             const float2* means2D, const float4* conic, const float* background, int bg_per_view, const float* final_T,
                             const unsigned* n_contrib, const float* dL_dpixels, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolors,
-                            double* dL_dv2g_acc, int debug_no_atomics)
+                            double* dL_dv2g_acc)
 {
     F3DG_KLAUNCH((render5_bwd_kernel<F3DG_B5_OCC>), dim3((unsigned)V * (unsigned)T * 4u), dim3(64), 0, s, V, P, W, H, tiles_x, T, focal_x, focal_y, hdr, ranges,
                  point_list, small_list, rec, cull, means2D, conic, background, bg_per_view, final_T, n_contrib, dL_dpixels, dL_dmean2D,
-                 dL_dopacity, dL_dcolors, dL_dv2g_acc, debug_no_atomics);
+                 dL_dopacity, dL_dcolors, dL_dv2g_acc);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }

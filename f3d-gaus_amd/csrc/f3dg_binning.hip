@@ -243,24 +243,11 @@ struct ScatterShared {
     u32 sval[F3DG_SORT_CHUNK];
 };
 
-// What a view's LAST depth pass adds with option sort_fused_rects (off by default: measured equal): the element's payload is a Gaussian id and its final
-// position is known, so the pass also fetches that Gaussian's tile rectangle and writes it -- and its area = tiles touched, the input
-// of the prefix sum that places the instances -- at the sorted position. This is the one random gather of the path (an 8-byte read
-// per 128-byte line, from the view's 8 P bytes in its XCD's L2); inside the pass it flies behind the other chunks' LDS work of the CU
-// instead of being a launch of its own that reads the order back.
-struct RectSink {
-    const uint2* rects;     // the segment's rectangles, id-indexed
-    u32* tiles;             // [V P] sorted order
-    u32* rx;
-    u32* ry;
-};
-
 // IOTA: the payload of the input is its position inside the segment (first pass of the depth sort)
-template <typename K, bool IOTA, typename DIGIT, bool RECTS = false>
+template <typename K, bool IOTA, typename DIGIT>
 __device__ __forceinline__ void scatter_chunk(const K* __restrict__ keys_in, const u32* __restrict__ vals_in, K* __restrict__ keys_out,
                                               u32* __restrict__ vals_out, const SegChunk& ck, const DIGIT digit,
-                                              const u32* __restrict__ offsets /* exclusive scan of hist */, ScatterShared& sh, K* skey,
-                                              const RectSink sink = RectSink{nullptr, nullptr, nullptr, nullptr})
+                                              const u32* __restrict__ offsets /* exclusive scan of hist */, ScatterShared& sh, K* skey)
 {
     // the chunk is digit-sorted inside LDS (stable), then written out in coalesced runs
     const u32 n = ck.n;
@@ -339,34 +326,6 @@ __device__ __forceinline__ void scatter_chunk(const K* __restrict__ keys_in, con
         }
     }
     __syncthreads();
-    if constexpr (RECTS) {
-        constexpr int GI = 4;                         // gathers in flight per thread
-        for (u32 s0 = threadIdx.x; s0 < in_block; s0 += GI * F3DG_BLOCK) {
-            u32 pos[GI], id[GI];
-            uint2 r[GI];
-#pragma unroll
-            for (int g = 0; g < GI; g++) {
-                const u32 slot = s0 + (u32)g * F3DG_BLOCK;
-                const bool ok = slot < in_block;
-                id[g] = ok ? sh.sval[slot] : 0u;
-                pos[g] = ok ? sh.gdelta[digit((u32)skey[ok ? slot : 0u])] + slot : 0u;
-            }
-#pragma unroll
-            for (int g = 0; g < GI; g++)
-                r[g] = s0 + (u32)g * F3DG_BLOCK < in_block ? sink.rects[id[g]] : make_uint2(0u, 0u);
-#pragma unroll
-            for (int g = 0; g < GI; g++) {
-                if (s0 + (u32)g * F3DG_BLOCK < in_block) {
-                    vals_out[pos[g]] = id[g];
-                    sink.tiles[pos[g]] = (((r[g].x >> 16) & F3DG_RECT_COORD) - (r[g].x & F3DG_RECT_COORD)) *
-                                         (((r[g].y >> 16) & F3DG_RECT_COORD) - (r[g].y & F3DG_RECT_COORD));
-                    sink.rx[pos[g]] = r[g].x;
-                    sink.ry[pos[g]] = r[g].y;
-                }
-            }
-        }
-        return;
-    }
     for (u32 slot = threadIdx.x; slot < in_block; slot += F3DG_BLOCK) {
         const K k = skey[slot];
         const u32 d = digit((u32)k);
@@ -476,16 +435,14 @@ gsort_range_kernel(u32 cps, const u32* __restrict__ chunk_minmax, u32* __restric
     if (threadIdx.x == 0) { minmax[2 * blockIdx.x] = kmin; minmax[2 * blockIdx.x + 1] = kmax; }
 }
 
-template <int PASS, bool RECTS = false>
+template <int PASS>
 __global__ void __launch_bounds__(F3DG_BLOCK)
 gsort_scatter_kernel(const u32* __restrict__ keys_in, const u32* __restrict__ vals_in, u32* __restrict__ keys_out,
-                     u32* __restrict__ vals_out, u32 seg_len, u32 cps, const u32* __restrict__ offsets, const u32* __restrict__ minmax,
-                     RectSink sink)
+                     u32* __restrict__ vals_out, u32 seg_len, u32 cps, const u32* __restrict__ offsets, const u32* __restrict__ minmax)
 {
     __shared__ ScatterShared sh;
     __shared__ u32 skey[F3DG_SORT_CHUNK];
     const SegChunk ck = fixed_chunk(seg_len, cps);
-    sink.rects += ck.seg_base;
     if constexpr (PASS == 0) {           // the payload of the input is its position inside the segment
         scatter_chunk<u32, true, ShiftDigit>(keys_in, vals_in, keys_out, vals_out, ck, ShiftDigit{0}, offsets, sh, skey);
     } else if constexpr (PASS == 1) {
@@ -494,17 +451,10 @@ gsort_scatter_kernel(const u32* __restrict__ keys_in, const u32* __restrict__ va
         u32 kbase;
         const bool compact = gsort_compact(minmax, ck.seg, kbase);
         // (the keys are not read again after a view's LAST pass -- pass 2 of a compact view, pass 3 otherwise --: it does not write them)
-        if (!compact) {
-            if constexpr (PASS == 3 && RECTS)
-                scatter_chunk<u32, false, ShiftDigit, true>(keys_in, vals_in, (u32*)nullptr, vals_out, ck, ShiftDigit{8 * PASS}, offsets, sh, skey, sink);
-            else
-                scatter_chunk<u32, false, ShiftDigit>(keys_in, vals_in, PASS == 3 ? (u32*)nullptr : keys_out, vals_out, ck, ShiftDigit{8 * PASS}, offsets, sh, skey);
-        } else if constexpr (PASS == 2) {
-            if constexpr (RECTS)
-                scatter_chunk<u32, false, CompactDigit, true>(keys_in, vals_in, (u32*)nullptr, vals_out, ck, CompactDigit{kbase}, offsets, sh, skey, sink);
-            else
-                scatter_chunk<u32, false, CompactDigit>(keys_in, vals_in, (u32*)nullptr, vals_out, ck, CompactDigit{kbase}, offsets, sh, skey);
-        }
+        if (!compact)
+            scatter_chunk<u32, false, ShiftDigit>(keys_in, vals_in, PASS == 3 ? (u32*)nullptr : keys_out, vals_out, ck, ShiftDigit{8 * PASS}, offsets, sh, skey);
+        else if constexpr (PASS == 2)
+            scatter_chunk<u32, false, CompactDigit>(keys_in, vals_in, (u32*)nullptr, vals_out, ck, CompactDigit{kbase}, offsets, sh, skey);
     }
 }
 
@@ -668,7 +618,7 @@ gsort_gather_rects_kernel(int P, u32* __restrict__ gv0, u32* __restrict__ gv1, c
 template <typename G>
 __global__ void __launch_bounds__(F3DG_BLOCK)
 duplicate_sorted_kernel(int P, int tile_bits, int grid_x, const u32* __restrict__ gv0, const u32* __restrict__ gv1,
-                        const u32* __restrict__ minmax, const u32* __restrict__ rx, const u32* __restrict__ ry_fused /* null: the view's spare order buffer */,
+                        const u32* __restrict__ minmax, const u32* __restrict__ rx,
                         const u32* __restrict__ offsets_sorted,
                         const F3dgHeader* __restrict__ hdr, G* __restrict__ kgrp, u32* __restrict__ vals)
 {
@@ -680,7 +630,7 @@ duplicate_sorted_kernel(int P, int tile_bits, int grid_x, const u32* __restrict_
     u32 kbase;
     const bool pass2 = gsort_compact(minmax, (u32)v, kbase);      // as in gsort_gather_rects_kernel
     const u32* perm = pass2 ? gv1 : gv0;
-    const u32* ry = ry_fused ? ry_fused : pass2 ? gv0 : gv1;
+    const u32* ry = pass2 ? gv0 : gv1;                             // the view's spare order buffer
     // output range of the workgroup
     const size_t first = (size_t)v * P + (size_t)blockIdx.x * F3DG_BLOCK;
     const int in_block = min(F3DG_BLOCK, P - (int)(blockIdx.x * F3DG_BLOCK));
@@ -811,7 +761,6 @@ int f3dg_launch_scan_inclusive(hipStream_t s, const unsigned* in, unsigned* out,
 int f3dg_tile_bits(int T) { return bits_for((unsigned long long)T); }
 
 // Number of 8-bit passes over the instances: only the tile bits (instances are generated in (view, depth, id) order).
-int g_f3dg_tile_split = 1;         // lab option tile_split: two tile passes split their bits evenly (1, default) or 8 + rest (0)
 
 int f3dg_sort_passes(int V, int T)
 {
@@ -840,10 +789,6 @@ static int binning_tail(hipStream_t s, int V, int P, int grid_x, int T, int tile
     u32* minmax = reinterpret_cast<u32*>(ws + L.segtab) + L.segtab_minmax;
     u32* chunk_minmax = minmax + 2 * (size_t)V;
     const bool view_scan = cps <= 64;      // one workgroup per view (<= 4 rounds of 4096 entries) or the general three-kernel scan
-    // (sort_fused_rects: the last pass of a view also delivers its rectangles and tile counts in sorted order; see RectSink)
-    const bool fused = g_f3dg_sort_fused_rects != 0;
-    u32* const gx = reinterpret_cast<u32*>(ws + L.gsort) + 4 * VP;           // [3][V P]: tiles / prefix sum, rx, ry of the fused path
-    const RectSink sink{reinterpret_cast<const uint2*>(ws + L.rects), gx, gx + VP, gx + 2 * VP};
 #define F3DG_GSORT_PASS(PASS, IN, OUT)                                                                                                     \
     F3DG_KLAUNCH((gsort_hist_kernel<PASS>), dim3(gblocks), dim3(F3DG_BLOCK), 0, s, gk[IN], (u32)P, cps, hist, minmax, chunk_minmax); \
     if (view_scan)                                                                                                                         \
@@ -852,12 +797,7 @@ static int binning_tail(hipStream_t s, int V, int P, int grid_x, int T, int tile
         rc = f3dg_launch_scan_inclusive(s, hist, hist, (unsigned long long)256 * gblocks, scan_tmp, L.scan_tmp_elems, 1, nullptr);        \
         if (rc != F3DG_OK) return rc;                                                                                                      \
     }                                                                                                                                      \
-    if (fused && PASS >= 2)                                                                                                                \
-        F3DG_KLAUNCH((gsort_scatter_kernel<PASS, (PASS >= 2)>), dim3(gblocks), dim3(F3DG_BLOCK), 0, s, gk[IN], gv[IN], gk[OUT], gv[OUT], (u32)P, cps, \
-                     hist, minmax, sink);                                                                                                  \
-    else                                                                                                                                   \
-        F3DG_KLAUNCH((gsort_scatter_kernel<PASS>), dim3(gblocks), dim3(F3DG_BLOCK), 0, s, gk[IN], gv[IN], gk[OUT], gv[OUT], (u32)P, cps, \
-                     hist, minmax, sink)
+    F3DG_KLAUNCH((gsort_scatter_kernel<PASS>), dim3(gblocks), dim3(F3DG_BLOCK), 0, s, gk[IN], gv[IN], gk[OUT], gv[OUT], (u32)P, cps, hist, minmax)
     F3DG_GSORT_PASS(0, 0, 1);
     F3DG_GSORT_PASS(1, 1, 0);
     F3DG_KLAUNCH(gsort_range_kernel, dim3(V), dim3(64), 0, s, cps, chunk_minmax, minmax);
@@ -865,18 +805,17 @@ static int binning_tail(hipStream_t s, int V, int P, int grid_x, int T, int tile
     F3DG_GSORT_PASS(3, 1, 0);
 #undef F3DG_GSORT_PASS
     // a view's order (perm) is gv[1] after pass 2 if its key range is compact, gv[0] after pass 3 otherwise; the other one takes ry
-    u32* offsets_sorted = fused ? sink.tiles : gk[1];          // tiles_touched in sorted order, then its inclusive prefix sum (in place)
-    u32* rx = fused ? sink.rx : gk[0];
+    u32* offsets_sorted = gk[1];          // tiles_touched in sorted order, then its inclusive prefix sum (in place)
+    u32* rx = gk[0];
 
     // 2. instances in (view, depth, id) order
-    if (!fused)
-        F3DG_KLAUNCH(gsort_gather_rects_kernel, dim3((unsigned)V * (unsigned)((P + 4 * F3DG_BLOCK - 1) / (4 * F3DG_BLOCK))), dim3(F3DG_BLOCK), 0, s, P, gv[0], gv[1], minmax,
+    F3DG_KLAUNCH(gsort_gather_rects_kernel, dim3((unsigned)V * (unsigned)((P + 4 * F3DG_BLOCK - 1) / (4 * F3DG_BLOCK))), dim3(F3DG_BLOCK), 0, s, P, gv[0], gv[1], minmax,
                            reinterpret_cast<const uint2*>(ws + L.rects), offsets_sorted, rx);
     rc = f3dg_launch_scan_inclusive(s, offsets_sorted, offsets_sorted, (unsigned long long)VP, scan_tmp, L.scan_tmp_elems, 0, hdr);
     if (rc != F3DG_OK) return rc;
     const int passes = f3dg_sort_passes(V, T);
     int src = passes & 1;                                                      // so that the tile pass(es) end in half 0
-    F3DG_KLAUNCH((duplicate_sorted_kernel<G>), pgrid, dim3(F3DG_BLOCK), 0, s, P, tile_bits, grid_x, gv[0], gv[1], minmax, rx, fused ? sink.ry : (u32*)nullptr, offsets_sorted, hdr,
+    F3DG_KLAUNCH((duplicate_sorted_kernel<G>), pgrid, dim3(F3DG_BLOCK), 0, s, P, tile_bits, grid_x, gv[0], gv[1], minmax, rx, offsets_sorted, hdr,
                        kgrp[src], vals[src]);
 
     // 3. stable pass(es) over the tile bits inside every view's segment of the instance arrays: (view, tile, depth, id) order
@@ -892,11 +831,11 @@ static int binning_tail(hipStream_t s, int V, int P, int grid_x, int T, int tile
         const u32 per_xcd_h = (u32)((nbmax + 7) / 8 < 512 ? (nbmax + 7) / 8 : 512);
         // two passes (257..65,536 tiles: 512^2 images have 1,024): the tile bits are split EVENLY, 5 + 5 instead of 8 + 2 -- a pass costs
         // the same whatever its digit width, and a chunk's runs of equal digits, which leave LDS as coalesced stores, are 8 x longer
-        // with 32 digits than with 256 (option tile_split 0: the 8-bit digits of rounds 1-5)
-        const int split = (passes == 2 && g_f3dg_tile_split) ? (tile_bits + 1) / 2 : 8;
+        // with 32 digits than with 256
+        const int split = passes == 2 ? (tile_bits + 1) / 2 : 8;
         for (int p = 0; p < passes; p++) {
             const int shift = split * p;
-            const u32 mask = (passes == 2 && g_f3dg_tile_split) ? (1u << (p == 0 ? split : tile_bits - split)) - 1u : 255u;
+            const u32 mask = passes == 2 ? (1u << (p == 0 ? split : tile_bits - split)) - 1u : 255u;
             F3DG_HIP_CHECK(hipMemsetAsync(hist, 0, sizeof(u32) * 256 * nbmax, s));
             F3DG_KLAUNCH((radix2_hist_var_kernel<G>), dim3(8 * per_xcd_h), dim3(F3DG_BLOCK), 0, s, kgrp[src], st, shift, mask, hist);
             rc = f3dg_launch_scan_inclusive(s, hist, hist, (unsigned long long)256 * nbmax, scan_tmp, L.scan_tmp_elems, 1, nullptr);
@@ -936,8 +875,7 @@ int f3dg_launch_binning(hipStream_t s, int V, int P, int W, int H, const F3dgLay
         if (rc != F3DG_OK) return rc;
     }
     // group stream type that fits (view << tile_bits | tile)
-    const bool small = !g_f3dg_sort_wide_groups &&
-                       (((unsigned long long)(V > 0 ? V - 1 : 0) << tile_bits) | ((1ull << tile_bits) - 1ull)) <= 0xFFFFull;
+    const bool small = (((unsigned long long)(V > 0 ? V - 1 : 0) << tile_bits) | ((1ull << tile_bits) - 1ull)) <= 0xFFFFull;
     rc = small ? binning_tail<unsigned short>(s, V, P, grid_x, T, tile_bits, L, ws, hdr)
                : binning_tail<u32>(s, V, P, grid_x, T, tile_bits, L, ws, hdr);
     if (rc != F3DG_OK) return rc;

@@ -79,34 +79,20 @@ struct __attribute__((aligned(16))) F3dgRec { float f[F3DG_REC_FLOATS]; };
 // constant. The reference's float64 island (forward.cu:511-522) becomes error-free float32 pairs:
 //   b^2 = p + e exactly (FMA), q1 = p r, q2 = ((p - q1 a) + e) r with r ~ 1/a: b^2/a = q1 + q2 to ~2^-45; C - q1 is exact (Sterbenz)
 //   wherever the exponent matters, so min_value = (C - q1) - q2 carries one rounding of a number of magnitude <~ 20;
-//   t = -b/a = -b r (<= 1.5 ulp: v_rcp_f32 is good to 1 ulp; round 3 spent two more FMAs on a Newton step for it);
+//   t = -b/a = -b r (<= 1.5 ulp: v_rcp_f32 is good to 1 ulp);
 //   G = exp(min(-min_value / 2, 0)) as v_exp_f32(min(min_value * (-log2(e) / 2), 0)): one multiply and one v_min instead of the
 //   reference's multiply, compare + select, and the log2(e) multiply (a NaN exponent gives G = 1 where the reference's gives NaN:
 //   both are garbage, and no finite record produces one).
-#ifndef F3DG_FAST_R03
-#define F3DG_FAST_R03 0
-#endif
 __device__ __forceinline__ void f3dg_fast_t_G(float aaf, float bhalf, float CC, float& t, float& G)
 {
     const float r = __builtin_amdgcn_rcpf(aaf);
-#if F3DG_FAST_R03      // A/B switch: round 3's sequence (Newton step for t, compare + select clamp, separate log2(e) multiply): +5 VALU per pair
-    const float t0 = -bhalf * r;
-    t = fmaf(fmaf(-aaf, t0, -bhalf), r, t0);
-#else
     t = -bhalf * r;
-#endif
     const float p = bhalf * bhalf;
     const float e = fmaf(bhalf, bhalf, -p);
     const float q1 = p * r;
     const float q2 = (fmaf(-q1, aaf, p) + e) * r;
     const float min_value = (CC - q1) - q2;
-#if F3DG_FAST_R03
-    float power = -0.5f * min_value;
-    if (power > 0.0f) power = 0.0f;
-    G = __builtin_amdgcn_exp2f(power * 1.4426950408889634f);
-#else
     G = __builtin_amdgcn_exp2f(fminf(min_value * -0.7213475204444817f, 0.0f));
-#endif
 }
 
 // Host-side description of where each array lives inside the workspace (byte offsets).
@@ -123,8 +109,8 @@ struct F3dgLayout {
     size_t offsets;        // [V*P] u32   inclusive scan of tiles_touched
     size_t clamped;        // [V*P] u8    bit c set when SH colour channel c was clamped
     size_t rects;          // [V*P] uint2: tile rectangle of every (view, Gaussian) (rminx | rmaxx << 16, rminy | rmaxy << 16)
-    size_t gsort;          // [7][V*P] u32: ping-pong (key, id) buffers of the per-view depth sort of the Gaussians ([0..3]; without
-                           // sort_fused_rects reused for the sorted tile counts and rectangles), [4..6] tile counts -> prefix sum, rx, ry in sorted order
+    size_t gsort;          // [4][V*P] u32: ping-pong (key, id) buffers of the per-view depth sort of the Gaussians, reused for the sorted
+                           // tile counts and rectangles
     size_t scan_tmp;       // u32 block sums for the scans
     size_t keys[2];        // group stream (u16 / u32 per instance) of the two ping-pong halves, [cap] 4 B; [0] is [cap] 8 B: it also
                            // holds the rebuilt 64-bit keys of the debug export
@@ -135,7 +121,7 @@ struct F3dgLayout {
     size_t final_T;        // [V][4][H*W] float
     size_t n_contrib;      // [V][2][H*W] u32
     size_t bwd_acc;        // [V*P][16] double-sized slots (128 B): float64 accumulator of dL/dview2gaussian [10]; with the dense backward also the seven
-                           // float32 sums of colour, mean2D and opacity at byte 80 (lock-step backward: the first 80 V P bytes as [V*P][10])
+                           // float32 sums of colour, mean2D and opacity at byte 80 (render3_bwd_kernel: the first 80 V P bytes as [V*P][10])
     // small-call path (f3dg_small.hip; carved only for the shapes it serves, small_cap = 0 otherwise)
     size_t small_boxes;    // [V][ceil(P/64)] uint2: union of the tile rectangles of every 64 consecutive Gaussians (small path only)
     size_t small_cnt;      // [V*T] u32: length of every (view, tile) list
@@ -202,9 +188,7 @@ int f3dg_launch_preprocess(hipStream_t s, int V, int views_per_set, int P, int D
                            float tan_fovx, float tan_fovy, float focal_x, float focal_y, float kernel_size,
                            F3dgRec* rec, float2* means2D, float* depths, unsigned* sort_keys, uint2* rects, float4* bbox /* may be null */, float4* cull, float4* conic,
                            int* radii, unsigned* tiles, unsigned char* clamped, int save_aux, int tile_cull, F3dgHeaderInit init,
-                           float4* hoist = nullptr /* scratch of n_sets * P * 96 bytes: option pre_hoist */, int n_sets = 1,
                            uint2* chunk_boxes = nullptr /* small path: [V][ceil(P/64)] unions of 64 rectangles */);
-extern int g_f3dg_pre_hoist;            // 1: the view-independent part of the projection is computed once per Gaussian (preprocess_hoist_kernel)
 
 // Small-call path: entries per (view, tile) it can hold, and the shapes it serves (one or two views of at most 2^18 Gaussians on at
 // most 1024 tiles: the reference's one-view-per-call loops, visualize.py:293-314, 387-416)
@@ -225,43 +209,30 @@ int f3dg_launch_scan_inclusive(hipStream_t s, const unsigned* in, unsigned* out,
 int f3dg_launch_binning(hipStream_t s, int V, int P, int W, int H, const F3dgLayout& L, char* ws, int export_offsets);
 int f3dg_launch_export_keys(hipStream_t s, int V, int P, int W, int H, const F3dgLayout& L, char* ws);
 
-extern int g_f3dg_render_pretest;      // 1 (default): conservative f32 pre-test enabled; 0: plain path (A/B, tests)
-extern int g_f3dg_render_cull;         // 1 (default): per-strip culling of the staged list by the conservative box
-extern int g_f3dg_sort_fused_rects;    // 1: a view's last depth pass also gathers its rectangles into sorted order (no gsort_gather_rects_kernel); 0 (default): measured equal
-extern int g_f3dg_sort_wide_groups;    // 0 (default): u16 group stream when it fits; 1: always u32 (tests)
-extern int g_f3dg_render_queue;        // 1 (default): two-phase loop with per-lane work queues
-extern int g_f3dg_render_kernel;       // 3 (default): render3 (one wave64 per 8x8 quadrant, no barriers); 2: render2 (four waves per tile,
-                                       // Gaussians across the lanes in phase 1); 1: the pixel-lane kernel with its filters
-extern int g_f3dg_small_debug;         // timing experiments of small_bin_kernel: 1 return at once, 2 after the collection, 3 no sort passes
 extern int g_f3dg_small_path;          // 1 (default): inference calls of a small shape (f3dg_small_shape) take the three-launch path
 extern int g_f3dg_bwd_occ;             // waves per SIMD render3_bwd_kernel is compiled for: 5 (default: 10.0 ms at C5), 2..4 (10.2-10.4: the kernel is VALU-bound at any of them) or 6 (spills, 12.0)
-extern int g_f3dg_render_lds_pad;      // experiment: extra dynamic LDS bytes per render3 workgroup (lowers the occupancy)
 extern int g_f3dg_render_unroll;       // small launches (render_lowocc): entries per phase-2 trip of render3p (1 or 2); -1 = by launch size and arithmetic
+extern int g_f3dg_reference_kernels;   // diagnostic: 1 = the compositing forward and integrate pass 1 take the plain transcriptions (render_fwd_kernel,
+                                       // integrate_pass1_kernel) in the reference's arithmetic: the baseline of the bit-identity tests
 int f3dg_launch_render_small(hipStream_t s, int V, int P, int W, int H, float focal_x, float focal_y, const F3dgHeader* hdr, const uint2* ranges,
                          const unsigned* point_list, const F3dgRec* rec, const float4* cull, const float* background, int bg_per_view,
                          float* out_color, int fast, int save_aux, float* final_T, unsigned* n_contrib, int unroll, int split, int count);
 extern int g_f3dg_render_split;        // small launches: 1 = two waves per quadrant (render3p_fwd_kernel: a producer wave scans, gathers and runs phase 1 for the window after the one the consumer wave composites)
 extern int g_f3dg_render_lowocc;       // n >= 1 (default 1): launches of at most max(2, n) x 1024 quadrant waves take the multi-wave kernels of f3dg_render4.hip; 0: never
-extern int g_f3dg_render_slide;        // 1 (default): render3 with the sliding half-window (render3s_fwd_kernel); 0: fixed 64-entry windows
-extern int g_f3dg_render_tail;         // N > 0: render3s switches a quadrant to the tail schedule once at most N of its pixels are unsaturated (0: never)
 extern int g_f3dg_render_count;        // 1: the one-wave kernel's counting variant (diagnostic; f3dg_debug_render_counts)
-extern int g_f3dg_render_wpb;          // quadrant waves per render3s workgroup: 1 (default) or 4 (a tile's four waves start together on one CU)
-extern int g_f3dg_render_replay;       // lab builds (-DF3DG_LAB) only: 2 / 3 = launch render3s_stage_only_kernel instead of the compositing kernel
-extern int g_f3dg_render_dma;          // render3 stages the records with global_load_lds_dwordx4 (1, default) or through registers (0)
 int f3dg_prof_bwd_begin(hipStream_t s);
 void f3dg_prof_bwd_mark(int slot, int stage_done, hipStream_t s);
 int f3dg_render_uses_fast(int save_aux);       // the arithmetic mode a compositing launch with / without SAVE_AUX takes
-extern int g_f3dg_render_round;        // list entries render2 stages per round in fast arithmetic: 192 (default, 7 workgroups per CU) or 256 (6)
 extern int g_f3dg_render_fast;         // 1 (default): float64 island of the blend replaced by error-free float32 pairs in inference
                                        // calls (no SAVE_AUX); 2: also with SAVE_AUX (tests); 0: the reference's float32/float64 order always
 
 int f3dg_launch_render(hipStream_t s, int V, int P, int W, int H, float focal_x, float focal_y,
                        const F3dgHeader* hdr, const uint2* ranges, const unsigned* point_list, const F3dgRec* rec,
-                       const float4* bbox, const float4* cull, const float* background, int bg_per_view, float* out_color,
+                       const float4* cull, const float* background, int bg_per_view, float* out_color,
                        float* final_T, unsigned* n_contrib, int save_aux, unsigned skip_channels = 0u, int fast = -1 /* -1: the process default */,
                        int scan = 0 /* the call carries F3DG_FLAG_SCAN */);
 
-// the rank-packed compositing forward (f3dg_render4.hip; option render_kernel = 4, inference launches)
+// the rank-packed compositing forward (f3dg_render4.hip; option render_pack)
 extern int g_f3dg_render_pack;         // -1 (default): inference launches in the reference's arithmetic take render4; 1: all inference launches; 0: none
 extern int g_f3dg_render_pack_th;      // trips of a slide with at most this many participating pixels are packed (default 32; 0: never)
 int f3dg_launch_render4(hipStream_t s, int V, int P, int W, int H, float focal_x, float focal_y, const F3dgHeader* hdr, const uint2* ranges,
@@ -272,9 +243,7 @@ int f3dg_launch_render4(hipStream_t s, int V, int P, int W, int H, float focal_x
 // the split-pixel compositing forward (f3dg_render5.hip; F3DG_FLAG_SCAN / option render_scan: fast inference launches of the general path)
 extern int g_f3dg_render_scan;         // -1 (default): calls with F3DG_FLAG_SCAN; 1: every eligible launch; 0: never
 extern int g_f3dg_render_scan_min;     // stragglers holding fewer older-half entries than this finish the slide in fused trips (default 4; 0: always compact)
-extern int g_f3dg_tile_split;          // two tile passes of the binning split their bits evenly (default 1; lab option tile_split)
-extern int g_f3dg_render_scan_lanes;   // lanes per pixel of the one- and two-view scan kernel (render5p): 4 (default) or 2 (lab option render_scan_lanes)
-extern int g_f3dg_render_scan_th;      // fused trips while more than this many pixels take part (default 20)
+extern int g_f3dg_render_scan_th;      // fused trips while more than this many pixels take part (default 12)
 int f3dg_launch_render5(hipStream_t s, int V, int P, int W, int H, float focal_x, float focal_y, const F3dgHeader* hdr, const uint2* ranges,
                         const unsigned* point_list, const F3dgRec* rec, const float4* cull, const float* background, int bg_per_view,
                         float* out_color, unsigned skip_channels, int count);
@@ -288,7 +257,7 @@ int f3dg_launch_render5_bwd(hipStream_t s, int V, int P, int W, int H, int tiles
                             const uint2* ranges, const unsigned* point_list, const unsigned* small_list, const F3dgRec* rec, const float4* cull,
                             const float2* means2D, const float4* conic, const float* background, int bg_per_view, const float* final_T,
                             const unsigned* n_contrib, const float* dL_dpixels, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolors,
-                            double* dL_dv2g_acc, int debug_no_atomics);
+                            double* dL_dv2g_acc);
 
 int f3dg_launch_integrate_fill(hipStream_t s, int W, int H, int PN, float* out_color, float* out_alpha_integrated,
                                float* out_color_integrated);

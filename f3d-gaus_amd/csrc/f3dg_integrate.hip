@@ -9,9 +9,9 @@
 //
 //   pass 1  (one workgroup per tile, one pixel per lane)  the first loop of integrateCUDA: five rays per pixel
 //           (centre + 4 corners), colour / alpha / maximal depth of the pixel, and the pixel's list of contributing
-//           Gaussians -- written to a global [pixel][1024] u16 table instead of a private array. The culled per-16-lane
-//           entry lists and the conservative K pre-test of the compositing kernel are reused (boxes widened by the half
-//           pixel of the corner rays); both only remove (ray, Gaussian) pairs the reference `continue`s on.
+//           Gaussians -- written to a global [pixel][1024] u16 table instead of a private array. The conservative
+//           alpha >= 1/255 ellipse of the compositing kernel is reused (widened by the half pixel of the corner rays); it
+//           only removes (ray, Gaussian) pairs the reference `continue`s on.
 //   points  (one LANE PER POINT, visited in pixel order)  preprocessPointsCUDA fused with the second loop of integrateCUDA:
 //           the point finds its pixel, walks that pixel's contributor list and accumulates its alpha. Loop interchange
 //           (points outside, Gaussians inside) is exact because every point's recurrence is independent. The tile's
@@ -130,19 +130,18 @@ __device__ __forceinline__ bool ray_apply(Pass1State& st, const RayEval& e, cons
     return true;
 }
 
-#ifdef F3DG_LAB      // ---- round 1's per-pixel pass and its plain variant, lab builds only (the baseline of the bit-identity tests)
-template <bool FILTER>
+// ---- the plain transcription of pass 1: every ray of every pixel visits every list entry (option reference_kernels; the baseline the
+// bit-identity tests hold the shared-ray pass below to). One camera per launch.
 __global__ void __launch_bounds__(F3DG_BLOCK)
 integrate_pass1_kernel(int W, int H, int tiles_x, float focal_x, float focal_y, const F3dgHeader* __restrict__ hdr,
-                       const uint2* __restrict__ ranges, const unsigned* __restrict__ point_list,
-                       const F3dgRec* __restrict__ rec, const float4* __restrict__ bbox,
+                       const uint2* __restrict__ ranges, const unsigned* __restrict__ point_list, const F3dgRec* __restrict__ rec,
                        const float* __restrict__ background, float* __restrict__ out_color,
                        float* __restrict__ final_T, unsigned* __restrict__ n_contrib,
                        unsigned short* __restrict__ contrib_ids, unsigned* __restrict__ contrib_n)
 {
     const unsigned tile = blockIdx.x;
     const unsigned tile_x = tile % (unsigned)tiles_x, tile_y = tile / (unsigned)tiles_x;
-    // lane -> pixel as in the compositing kernel: wave = 8x8 quadrant, 16-lane group = 4x4 block
+    // lane -> pixel: wave = 8x8 quadrant, 16-lane group = 4x4 block
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const unsigned grp = lane >> 4, gi = lane & 15u;
     const unsigned blk_x = (wave & 1u) * 2u + (grp & 1u), blk_y = (wave >> 1) * 2u + (grp >> 1);
@@ -165,10 +164,9 @@ integrate_pass1_kernel(int W, int H, int tiles_x, float focal_x, float focal_y, 
     __shared__ float4 sq0[F3DG_BLOCK];            // v0 v1 v2 v3
     __shared__ float4 sq1[F3DG_BLOCK];            // v4 v5 v6 v7
     __shared__ float4 sq2[F3DG_BLOCK];            // v8 v9 opac K
-    __shared__ float4 sq3[F3DG_BLOCK];            // r g b, and (FILTER) the 16-bit block mask in place of the depth
-    __shared__ __align__(16) unsigned char grp_list[FILTER ? F3DG_BLOCK / 64 : 1][FILTER ? 4 : 1][FILTER ? F3DG_BLOCK : 1];
+    __shared__ float4 sq3[F3DG_BLOCK];            // r g b depth
     if (threadIdx.x == F3DG_ROUND) {
-        // sentinel (see f3dg_render.hip): fails the pre-test, pads the culled lists; .x/.y of sq3 hold the vote counters
+        // sentinel slot, never visited: .x/.y of sq3 hold the vote counters
         sq0[F3DG_ROUND] = make_float4(1.0f, 0.0f, 0.0f, 1.0f);
         sq1[F3DG_ROUND] = make_float4(0.0f, 1.0f, 0.0f, 0.0f);
         sq2[F3DG_ROUND] = make_float4(0.0f, 0.0f, 0.0f, __builtin_inff());
@@ -176,8 +174,6 @@ integrate_pass1_kernel(int W, int H, int tiles_x, float focal_x, float focal_y, 
     }
     int* done_cnt = reinterpret_cast<int*>(&sq3[F3DG_ROUND]);
     __syncthreads();
-
-    const float tile_px0 = (float)(tile_x * F3DG_TILE), tile_py0 = (float)(tile_y * F3DG_TILE);
 
     bool done = !inside;
     Pass1State st;
@@ -204,70 +200,24 @@ integrate_pass1_kernel(int W, int H, int tiles_x, float focal_x, float focal_y, 
         if (threadIdx.x < F3DG_ROUND && range.x + progress < range.y) {
             const unsigned id = point_list[range.x + progress] & F3DG_ID_MASK;
             const float4* src = reinterpret_cast<const float4*>(rec + id);
-            const float4 a = src[0], b = src[1], c = src[2];
-            float4 d = src[3];
-            sq0[threadIdx.x] = a;
-            sq1[threadIdx.x] = b;
-            sq2[threadIdx.x] = c;
-            if (FILTER) {
-                const float4 bx = bbox[id];                       // pixel-index coordinates of the alpha >= 1/255 region
-                unsigned mx = 0, my = 0;
-#pragma unroll
-                for (int q = 0; q < 4; q++) {                     // corner rays reach half a pixel beyond the block
-                    if (bx.x <= tile_px0 + (float)(4 * q + 3) + 0.5f && bx.y >= tile_px0 + (float)(4 * q) - 0.5f) mx |= 1u << q;
-                    if (bx.z <= tile_py0 + (float)(4 * q + 3) + 0.5f && bx.w >= tile_py0 + (float)(4 * q) - 0.5f) my |= 1u << q;
-                }
-                const unsigned m = ((my & 1u) ? mx : 0u) | ((my & 2u) ? mx << 4 : 0u) | ((my & 4u) ? mx << 8 : 0u) |
-                                   ((my & 8u) ? mx << 12 : 0u);
-                d.w = __uint_as_float(m);
-            }
-            sq3[threadIdx.x] = d;
-        } else if (FILTER && threadIdx.x < F3DG_ROUND) {
-            sq3[threadIdx.x].w = 0.0f;
+            sq0[threadIdx.x] = src[0];
+            sq1[threadIdx.x] = src[1];
+            sq2[threadIdx.x] = src[2];
+            sq3[threadIdx.x] = src[3];
         }
         __syncthreads();
 
-        const int n = min(F3DG_ROUND, toDo);
-        int count = n;
-        if (FILTER) {
-            {
-                uint4* fill = reinterpret_cast<uint4*>(&grp_list[wave][0][0]);
-                const unsigned ss = 0x01010101u * F3DG_ROUND;
-                fill[lane] = make_uint4(ss, ss, ss, ss);
-            }
-            int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-            const unsigned qx2 = (wave & 1u) * 2u, qy2 = (wave >> 1) * 2u;
-            const unsigned long long lt = (1ull << lane) - 1ull;
-#pragma unroll
-            for (int c = 0; c < F3DG_BLOCK / 64; c++) {
-                const unsigned e = c * 64 + lane;
-                const unsigned m = __float_as_uint(sq3[e].w);
-                const bool b0 = (m >> ((qy2 + 0u) * 4u + qx2 + 0u)) & 1u, b1 = (m >> ((qy2 + 0u) * 4u + qx2 + 1u)) & 1u;
-                const bool b2 = (m >> ((qy2 + 1u) * 4u + qx2 + 0u)) & 1u, b3 = (m >> ((qy2 + 1u) * 4u + qx2 + 1u)) & 1u;
-                const unsigned long long l0 = __ballot(b0), l1 = __ballot(b1), l2 = __ballot(b2), l3 = __ballot(b3);
-                if (b0) grp_list[wave][0][c0 + __popcll(l0 & lt)] = (unsigned char)e;
-                if (b1) grp_list[wave][1][c1 + __popcll(l1 & lt)] = (unsigned char)e;
-                if (b2) grp_list[wave][2][c2 + __popcll(l2 & lt)] = (unsigned char)e;
-                if (b3) grp_list[wave][3][c3 + __popcll(l3 & lt)] = (unsigned char)e;
-                c0 += __popcll(l0); c1 += __popcll(l1); c2 += __popcll(l2); c3 += __popcll(l3);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            count = max(max(c0, c1), max(c2, c3));
-        }
-        const unsigned char* my_list = FILTER ? grp_list[wave][grp] : nullptr;
+        const int count = min(F3DG_ROUND, toDo);
         const unsigned round_base = (unsigned)i * F3DG_ROUND;
 
-        for (int kk = 0; !done && kk < count; kk++) {
-            const int j = FILTER ? (int)my_list[kk] : kk;
+        for (int j = 0; !done && j < count; j++) {
             const float4 q0 = sq0[j], q1 = sq1[j], q2 = sq2[j], q3 = sq3[j];
             bool used = false;
-            used |= ray_entry<FILTER, 0>(st, rx0, ry0, q0, q1, q2, q3);
-            used |= ray_entry<FILTER, 1>(st, rxm, rym, q0, q1, q2, q3);
-            used |= ray_entry<FILTER, 2>(st, rxp, rym, q0, q1, q2, q3);
-            used |= ray_entry<FILTER, 3>(st, rxm, ryp, q0, q1, q2, q3);
-            used |= ray_entry<FILTER, 4>(st, rxp, ryp, q0, q1, q2, q3);
+            used |= ray_entry<false, 0>(st, rx0, ry0, q0, q1, q2, q3);
+            used |= ray_entry<false, 1>(st, rxm, rym, q0, q1, q2, q3);
+            used |= ray_entry<false, 2>(st, rxp, rym, q0, q1, q2, q3);
+            used |= ray_entry<false, 3>(st, rxm, ryp, q0, q1, q2, q3);
+            used |= ray_entry<false, 4>(st, rxp, ryp, q0, q1, q2, q3);
             if (used) {
                 const unsigned contributor = round_base + (unsigned)j + 1u;
                 st.last_contributor = contributor;
@@ -294,9 +244,7 @@ integrate_pass1_kernel(int W, int H, int tiles_x, float focal_x, float focal_y, 
     }
 }
 
-#endif // F3DG_LAB (integrate_pass1_kernel)
-
-// The same pass with the culling machinery of the compositing forward (f3dg_render.hip: render2): the per-ray K pre-test above costs
+// The same pass with the culling machinery of the compositing forward: a per-ray K pre-test (ray_entry<true>) costs
 // ~25 instructions per (ray, Gaussian) = 125 per (pixel, list entry), and no pixel ever leaves the loop early here (a saturated ray
 // `continue`s), so the pass was 60-90 % of an integrate call. A list entry is instead tested ONCE per pixel against the record's
 // conservative alpha >= 1/255 ellipse, Gaussians across the lanes (two FMAs per pixel, one comparison = one wave ballot), and only
@@ -1060,12 +1008,12 @@ int f3dg_launch_integrate_pass1(hipStream_t s, int V, int P, int W, int H, float
     unsigned* n_contrib = reinterpret_cast<unsigned*>(ws + L.n_contrib);
     unsigned short* contrib_ids = reinterpret_cast<unsigned short*>(ws + I.contrib_ids);
     unsigned* contrib_n = reinterpret_cast<unsigned*>(ws + I.contrib_n);
-#ifdef F3DG_LAB
-    const bool rays = g_f3dg_render_pretest && g_f3dg_render_cull && g_f3dg_render_kernel >= 3;
-#else
-    const bool rays = true;
-#endif
-    if (rays) {
+    if (g_f3dg_reference_kernels) {
+        for (int v = 0; v < V; v++)         // the plain transcription, one camera per launch
+            F3DG_KLAUNCH(integrate_pass1_kernel, dim3(T), dim3(F3DG_BLOCK), 0, s, W, H, tiles_x, focal_x, focal_y, hdr, ranges + (size_t)v * T,
+                         point_list, rec + (size_t)v * P, background, out_color + (size_t)v * F3DG_OUT_CHANNELS * HW, final_T + (size_t)v * 4 * HW,
+                         n_contrib + (size_t)v * 2 * HW, contrib_ids + (size_t)v * HW * F3DG_MAX_CONTRIB, contrib_n + (size_t)v * HW);
+    } else {
         // 545 shared rays per tile, then the per-pixel kernel on the tiles that hit the contributor limit (normally none)
         unsigned* redo = reinterpret_cast<unsigned*>(ws + I.redo);
         F3DG_KLAUNCH(integrate_pass1_rays_kernel, dim3((unsigned)V * (unsigned)T), dim3(F3DG_RAYS_THREADS), 0, s, V, P, T, W, H, tiles_x, focal_x, focal_y,
@@ -1075,28 +1023,6 @@ int f3dg_launch_integrate_pass1(hipStream_t s, int V, int P, int W, int H, float
                            hdr, ranges, point_list, rec, reinterpret_cast<const float4*>(ws + L.cull), background,
                            out_color, final_T, n_contrib, contrib_ids, contrib_n, redo);
     }
-#ifdef F3DG_LAB
-    else if (g_f3dg_render_pretest && g_f3dg_render_cull && g_f3dg_render_kernel >= 2)
-        F3DG_KLAUNCH(integrate_pass1_cull_kernel, dim3((unsigned)V * (unsigned)T), dim3(F3DG_BLOCK), 0, s, V, P, T, W, H, tiles_x, focal_x, focal_y,
-                           hdr, ranges, point_list, rec, reinterpret_cast<const float4*>(ws + L.cull), background,
-                           out_color, final_T, n_contrib, contrib_ids, contrib_n, (const unsigned*)nullptr);
-    else
-        for (int v = 0; v < V; v++) {       // the A/B variants of the tests: one camera per launch
-            const float4* bbox = reinterpret_cast<const float4*>(ws + L.bbox) + (size_t)v * P;
-            if (g_f3dg_render_pretest && g_f3dg_render_cull)          // round 1's version: per-ray pre-test + block masks from the boxes
-                F3DG_KLAUNCH((integrate_pass1_kernel<true>), dim3(T), dim3(F3DG_BLOCK), 0, s, W, H, tiles_x, focal_x, focal_y,
-                                   hdr, ranges + (size_t)v * T, point_list, rec + (size_t)v * P, bbox, background,
-                                   out_color + (size_t)v * F3DG_OUT_CHANNELS * HW, final_T + (size_t)v * 4 * HW, n_contrib + (size_t)v * 2 * HW,
-                                   contrib_ids + (size_t)v * HW * F3DG_MAX_CONTRIB, contrib_n + (size_t)v * HW);
-            else
-                F3DG_KLAUNCH((integrate_pass1_kernel<false>), dim3(T), dim3(F3DG_BLOCK), 0, s, W, H, tiles_x, focal_x, focal_y,
-                                   hdr, ranges + (size_t)v * T, point_list, rec + (size_t)v * P, bbox, background,
-                                   out_color + (size_t)v * F3DG_OUT_CHANNELS * HW, final_T + (size_t)v * 4 * HW, n_contrib + (size_t)v * 2 * HW,
-                                   contrib_ids + (size_t)v * HW * F3DG_MAX_CONTRIB, contrib_n + (size_t)v * HW);
-        }
-#else
-    (void)HW;
-#endif
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }

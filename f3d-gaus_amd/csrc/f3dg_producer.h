@@ -10,7 +10,7 @@
 // (submodules/diff-gof-rasterization/cuda_rasterizer/forward.cu:452-478).
 //
 // Round 6: the gathers of window k + 1 are REQUESTED before phase 1 of window k runs, into a third record buffer. With nothing passing
-// (lab option debug_skip_all, --tile-cull 0) the one-view launch still took 35.6 us of its 52-61: a window cost the producer
+// (a measurement build in which no entry passed, --tile-cull 0) the one-view launch still took 35.6 us of its 52-61: a window cost the producer
 // latency(gather) + phase 1 (~330 dependent instructions), back to back. Now the ~1.5 us a gather is in flight lie behind the ballots of
 // the window before. Which entries form a window, their order, the pass masks: unchanged, so the consumers see the same data.
 //

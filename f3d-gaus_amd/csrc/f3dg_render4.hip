@@ -1,4 +1,4 @@
-// f3dg_render4.hip -- compositing forward with RANK-PACKED trips (option render_kernel = 4).
+// f3dg_render4.hip -- compositing forward with RANK-PACKED trips (option render_pack).
 //
 // render3s_fwd_kernel (f3dg_render.hip) gives every pixel of an 8x8 quadrant a lane; in a phase-2 trip every pixel that still has a
 // passing entry in the window pops its next one and runs the whole loop body of renderCUDA (reference RAST/cuda_rasterizer/
@@ -40,15 +40,6 @@ __device__ unsigned long long g_f3dg_counts4[64][16];
 
 namespace {
 
-#ifndef F3DG_R4_PARK
-#define F3DG_R4_PARK 1              // 1: a batch's results go to its blend trips through LDS (parked); 0: by ds_bpermute from the dense lanes' registers
-#endif
-#ifndef F3DG_R4_FLAT
-#define F3DG_R4_FLAT 1              // 1: the blend trips of fast arithmetic run the branch-free recurrence (f3dg_pair_apply_flat)
-#endif
-#ifndef F3DG_R4_FLAT_FUSED
-#define F3DG_R4_FLAT_FUSED 0        // 1: the fused trips of fast arithmetic run the branch-free recurrence as well (measured: no gain)
-#endif
 #define F3DG_R4_WIN 64
 #define F3DG_R4_RING 128
 #define F3DG_R4_MAXR 10             // ranks per packed batch (two 32-bit registers of 6-bit slots)
@@ -73,9 +64,7 @@ __device__ __forceinline__ float pull(int addr, float v)
 
 // SAVE_AUX (a forward that f3dg_backward follows): also final_T [V][4][HW] and n_contrib [V][2][HW]; last_contributor / max_contributor are
 // 1-based positions in the tile's list, kept per staged slot (sP) and translated when a half of the window retires, as in render3s.
-#ifndef F3DG_R4_OCC
 #define F3DG_R4_OCC 8               // waves per SIMD the register allocation aims at (the full variants' 6 KB of LDS allow 6.5)
-#endif
 template <bool FAST, bool NORMAL, bool DIST, bool COUNT, bool SAVE_AUX = false>
 __global__ void __launch_bounds__(64, F3DG_R4_OCC)
 render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x, float focal_y,
@@ -104,7 +93,6 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
     __shared__ unsigned sQ[F3DG_R4_RING];          // ids of kept entries not staged yet, ring
     __shared__ unsigned sQpos[SAVE_AUX ? F3DG_R4_RING : 1];     // ... and their positions in the tile's list
     __shared__ unsigned sP[SAVE_AUX ? F3DG_R4_WIN : 1];         // list position of every staged slot (the reference's `contributor`)
-#if F3DG_R4_PARK
     // the parking area of a packed batch: what the dense trip hands to the blend trips, [position in the queue]. The queue itself
     // (sK: 64 x u16, (owning lane << 6) | physical slot) is read by the dense trip before it parks its results and aliases the first
     // 128 bytes. (Aliasing the id ring as well -- its pending ids parked in a register between slides, 5,632 instead of 6,144 bytes,
@@ -112,9 +100,6 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
     __shared__ float4 sPark[(NORMAL || DIST) ? 64 : 32];       // full: (alpha, t, m, nn0)        lean: 64 x (alpha, t)
     __shared__ float2 sPark2[(NORMAL || DIST) ? 64 : 1];       // full: (nn1, nn2)
     unsigned short* sK = reinterpret_cast<unsigned short*>(sPark);
-#else
-    __shared__ unsigned short sK[64];              // pair queue of a packed batch: (owning lane << 6) | physical slot
-#endif
 
     const F3dgRec* vrec = rec + (size_t)view * P;
     const float4* vcull = cull + (size_t)view * P;
@@ -209,24 +194,15 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
 
         // ---- phase 2a: fused trips while many pixels take part (a divergent loop: a pixel leaves it when its mask is empty; the
         // ballots are taken over the pixels still inside)
-#ifdef F3DG_R4_NOPACK       // experiment: the fused loop without its population test
-        while (pass != 0ull && __ballot((unsigned)pass != 0u) != 0ull) {
-#else
         while (pass != 0ull && __ballot((unsigned)pass != 0u) != 0ull && (int)__popcll(__ballot(true)) > pack_th) {
-#endif
             const unsigned j = (unsigned)__builtin_ctzll(pass) ^ xr;
             pass &= pass - 1;
             if (COUNT) n_lane_fused++;
             const float4 q0 = sR[0][j], q1 = sR[1][j], q2 = sR[2][j], q3 = sR[3][j];
-            const F3dgPair pr = f3dg_pair_eval<FAST, NORMAL, DIST, F3DG_R4_FLAT_FUSED != 0>(ray_x, ray_y, q0, q1, q2);
+            const F3dgPair pr = f3dg_pair_eval<FAST, NORMAL, DIST, false>(ray_x, ray_y, q0, q1, q2);
             // keeps the loads 16 bytes wide (ds_read_b96 takes twice the LDS cycles); placed behind the evaluation so that the
             // arithmetic on the first chunks starts while the last ones are still on their way
             asm volatile("" :: "v"(q2.w), "v"(q3.w), "v"(pr.alpha));
-#if F3DG_R4_FLAT_FUSED
-            if (FAST)
-                done = f3dg_pair_apply_flat<NORMAL, DIST>(st, F3DG_R4_FLAG | j, pr, q3.x, q3.y, q3.z);
-            else
-#endif
             if (pr.alpha != 0.0f)
                 done = f3dg_pair_apply<FAST, NORMAL, DIST>(st, F3DG_R4_FLAG | j, pr, q3.x, q3.y, q3.z);
             if (done) pass = 0ull;
@@ -273,12 +249,11 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                 const float rx = pull(owner, ray_x), ry = pull(owner, ray_y);
                 const unsigned j = k & 63u;
                 const float4 q0 = sR[0][j], q1 = sR[1][j], q2 = sR[2][j];
-                pr = f3dg_pair_eval<FAST, NORMAL, DIST, F3DG_R4_FLAT != 0>(rx, ry, q0, q1, q2);
+                pr = f3dg_pair_eval<FAST, NORMAL, DIST, true>(rx, ry, q0, q1, q2);
                 asm volatile("" :: "v"(q2.w), "v"(pr.alpha));
             }
             if (COUNT) { n_batches++; n_blend_trips += R; n_dense_pairs += total; }
 
-#if F3DG_R4_PARK
             // park the results (every lane has read its queue entry: the queue's bytes may go), then the blend trips: a divergent loop,
             // every owning lane walks ITS pairs of the batch through the recurrence, the wave runs as long as the longest of them
             wave_lds_fence();
@@ -305,11 +280,9 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                         mine.alpha = a.x; mine.t = a.y; mine.m = 0.0f; mine.nn0 = mine.nn1 = mine.nn2 = 0.0f;
                     }
                     if (COUNT) n_blend_pairs++;
-#if F3DG_R4_FLAT
                     if (FAST)
                         done = f3dg_pair_apply_flat<NORMAL, DIST>(st, F3DG_R4_FLAG | j, mine, q3.x, q3.y, q3.z);
                     else
-#endif
                     if (mine.alpha != 0.0f)
                         done = f3dg_pair_apply<FAST, NORMAL, DIST>(st, F3DG_R4_FLAG | j, mine, q3.x, q3.y, q3.z);
                     asm volatile("" :: "v"(q3.w));
@@ -317,34 +290,6 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                 }
             }
             wave_lds_fence();          // the next batch's queue overwrites the parking area
-#else
-            // R blend trips: every owning lane pulls its pair's numbers and applies the recurrence
-            F3DG_R4_PIN(st);
-            int src = (int)(off << 2);
-            unsigned i = 0;
-#pragma nounroll
-            do {
-                // (the colour of this trip's pair: requested before the pulls, needed last)
-                const unsigned j = (unsigned)slots & 63u;
-                const float4 q3 = sR[3][j];
-                F3dgPair mine;
-                mine.alpha = pull(src, pr.alpha);
-                mine.t = pull(src, pr.t);
-                mine.m = DIST ? pull(src, pr.m) : 0.0f;
-                mine.nn0 = NORMAL ? pull(src, pr.nn0) : 0.0f;
-                mine.nn1 = NORMAL ? pull(src, pr.nn1) : 0.0f;
-                mine.nn2 = NORMAL ? pull(src, pr.nn2) : 0.0f;
-                if (i < c && !done) {
-                    if (COUNT) n_blend_pairs++;
-                    if (mine.alpha != 0.0f) {
-                        asm volatile("" :: "v"(q3.w));
-                        done = f3dg_pair_apply<FAST, NORMAL, DIST>(st, F3DG_R4_FLAG | j, mine, q3.x, q3.y, q3.z);
-                    }
-                }
-                src += 4;
-                slots >>= 6;
-            } while (++i < R);
-#endif
             if (done) pass = 0ull;
         } while (__ballot((unsigned)pass != 0u) != 0ull);
 
@@ -419,7 +364,7 @@ thread_local char g_kernel_name4[160] = "";
 #define F3DG_R3U_RING 256
 // ---- SMALL launches, two waves per quadrant: a PRODUCER wave prepares window k + 1 while the CONSUMER wave composites window k ------
 // What is left of a lone wave's chain once phase 2 is shortened is everything else: with no entry passing the ellipse test at all
-// (option debug_skip_all) the one-view kernel still takes 36 of its 66 us -- list chunks, the id-dependent record gathers, the 64
+// (measured with a build in which no entry passes) the one-view kernel still takes 36 of its 66 us -- list chunks, the id-dependent record gathers, the 64
 // ellipse ballots of phase 1, each a latency nobody fills. That part does not depend on any pixel's state, so here it runs on its own
 // wave: workgroup = 2 waves on 2 SIMDs of a CU; wave 1 scans the list, requests the records of the next window into the other half
 // of the double buffer (global_load_lds), waits for them, runs phase 1 and leaves the 64 pass masks in LDS; wave 0 owns the pixels and

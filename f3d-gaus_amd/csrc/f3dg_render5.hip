@@ -42,7 +42,6 @@ extern thread_local const char* g_f3dg_last_render_kernel;
 int g_f3dg_render_scan = -1;          // option render_scan: -1 (default) = calls that ask for it (F3DG_FLAG_SCAN); 1 = every fast inference launch of the general path; 0 = never
 int g_f3dg_render_scan_min = 4;       // option render_scan_min: stragglers that hold fewer than this many older-half entries each finish the slide in fused trips (0: always compact)
 int g_f3dg_render_scan_th = 12;       // option render_scan_th: fused trips while more than this many pixels take part (64: every trip is compacted)
-int g_f3dg_render_scan_lanes = 4;     // lab option render_scan_lanes: lanes per pixel of the one- and two-view kernel (4, or 2: measured 54.8 against 52.7 us)
 
 // work counters (option render_count = 1; f3dg_debug_render5_counts): [0] staged entries, [1] scanned, [2] fused trips, [3] slides,
 // [4] lane-trips of fused trips, [5] waves, [6] dense batches, [7] pairs in dense batches, [8] pixels compacted, [9] slides with a compaction
@@ -52,9 +51,7 @@ namespace {
 
 #define F3DG_R5_WIN 64
 #define F3DG_R5_RING 128
-#ifndef F3DG_R5_OCC
 #define F3DG_R5_OCC 8               // 59 VGPRs (52 without normals and distortion), 5 KB of LDS: 8 waves per SIMD
-#endif
 
 __device__ __forceinline__ void wave_lds_fence5()
 {
@@ -398,7 +395,7 @@ render5_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
 // ---- SMALL launches (one or two views: every wave alone on its SIMD) in the split-pixel arithmetic --------------------------------------
 // A one-view launch is 1,024 quadrants on 1,024 SIMDs: a quadrant lasts as long as its pixels' chains of dependent instructions (render3p,
 // f3dg_render4.hip: a producer wave prepares the next window while a consumer wave composites, ~85 dependent instructions per entry and
-// pixel). Here every pixel gets FOUR lanes (LPP; two were measured slower, eight do not fit the CU's wave slots): a workgroup is the producer
+// pixel). Here every pixel gets FOUR lanes (two were measured slower: 54.8 against 52.7 us; eight do not fit the CU's wave slots): a workgroup is the producer
 // wave of render3p (f3dg_producer.h) + four consumer waves of 16 pixels x 4 lanes; a trip takes the pixel's next four passing entries, one per lane, evaluates their stateless parts side by side
 // (f3dg_pair_eval), and a two-step segmented product over the quad (DPP quad_perm) gives every lane the transmittance in front of ITS
 // entry -- hence its weight, the 1e-4 stop as a per-lane predicate, the median-depth candidate. Nothing else crosses lanes per trip: each
@@ -408,8 +405,7 @@ render5_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
 #define F3DG_QP(a, b, c, d) ((a) | ((b) << 2) | ((c) << 4) | ((d) << 6))
 #define F3DG_QDPP(x, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), ctrl, 0xf, 0xf, false))
 
-template <int LPP>          // lanes per pixel: 4 (four consumer waves of 16 pixels) or 2 (two consumer waves of 32 pixels)
-__global__ void __launch_bounds__(64 * (LPP + 1), 1)
+__global__ void __launch_bounds__(320, 1)
 render5p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x, float focal_y,
                     const F3dgHeader* __restrict__ hdr, const uint2* __restrict__ ranges,
                     const unsigned* __restrict__ point_list, const F3dgRec* __restrict__ rec,
@@ -421,8 +417,8 @@ render5p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
     const unsigned tile = unit >> 2, quad = unit & 3u;
     const unsigned tile_x = tile % (unsigned)tiles_x, tile_y = tile / (unsigned)tiles_x;
     const unsigned lane = threadIdx.x & 63u;
-    const unsigned wv = threadIdx.x >> 6;                 // 0..LPP-1: consumers, LPP: the producer (wave-uniform)
-    const bool producer = wv == (unsigned)LPP;
+    const unsigned wv = threadIdx.x >> 6;                 // 0..3: consumers, 4: the producer (wave-uniform)
+    const bool producer = wv == 4u;
     const unsigned qx0 = tile_x * F3DG_TILE + (quad & 1u) * 8u, qy0 = tile_y * F3DG_TILE + (quad >> 1) * 8u;
 
     __shared__ float4 sR[3][4][F3DG_PROD_WIN];            // three windows of records, [window % 3][16-byte chunk][entry]
@@ -435,13 +431,13 @@ render5p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
 
     if (producer) {
         // ================================================ wave 4: scan, gather, phase 1 (f3dg_producer.h) ================================
-        f3dg_window_producer(lane, view, tile, quad, qx0, qy0, P, T, hdr, ranges, point_list, rec, cull, sR, sQ, sPass, sMH, sStop, (1u << LPP) - 1u);
+        f3dg_window_producer(lane, view, tile, quad, qx0, qy0, P, T, hdr, ranges, point_list, rec, cull, sR, sQ, sPass, sMH, sStop, 15u);
         return;
     }
 
     // ================================================== waves 0..3: 16 pixels x 4 lanes each ==================================================
-    const unsigned sub = lane & (unsigned)(LPP - 1);      // which of the pixel's next LPP entries this lane takes
-    const unsigned q = (64u / LPP) * wv + lane / LPP;     // the pixel, 0..63 in the quadrant
+    const unsigned sub = lane & 3u;                       // which of the pixel's next four entries this lane takes
+    const unsigned q = 16u * wv + lane / 4u;              // the pixel, 0..63 in the quadrant
     const unsigned pix_x = qx0 + (q & 7u), pix_y = qy0 + (q >> 3);
     const bool inside = pix_x < (unsigned)W && pix_y < (unsigned)H;
     const float pixf_x = (float)pix_x + 0.5f, pixf_y = (float)pix_y + 0.5f;
@@ -458,22 +454,17 @@ render5p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
         for (;;) {
             __syncthreads();                                  // window `buf` is ready
             const unsigned m = sMH[buf].x;
-            if (m == 0u || sStop[buf ^ 1u] == (1u << LPP) - 1u)
+            if (m == 0u || sStop[buf ^ 1u] == 15u)
                 break;
             unsigned long long pass = done ? 0ull : sPass[buf][q];
             while (pass != 0ull) {
-                // the pixel's next LPP passing entries: lane `sub` takes the one of that rank
+                // the pixel's next four passing entries: lane `sub` takes the one of that rank
                 unsigned long long mine;
                 {
                     const unsigned long long p1 = pass & (pass - 1ull);
-                    if constexpr (LPP == 4) {
-                        const unsigned long long p2 = p1 & (p1 - 1ull), p3 = p2 & (p2 - 1ull);
-                        mine = sub == 0u ? pass : sub == 1u ? p1 : sub == 2u ? p2 : p3;
-                        pass = p3 & (p3 - 1ull);
-                    } else {
-                        mine = sub == 0u ? pass : p1;
-                        pass = p1 & (p1 - 1ull);
-                    }
+                    const unsigned long long p2 = p1 & (p1 - 1ull), p3 = p2 & (p2 - 1ull);
+                    mine = sub == 0u ? pass : sub == 1u ? p1 : sub == 2u ? p2 : p3;
+                    pass = p3 & (p3 - 1ull);
                 }
                 const bool have = mine != 0ull;
                 const int j = have ? __builtin_ctzll(mine) : 0;
@@ -483,20 +474,14 @@ render5p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                 const float alpha = have ? pr.alpha : 0.0f;
                 // transmittance in front of this lane's entry: T of the pixel x the product over the group's earlier lanes
                 // (DPP quad_perm patterns: SHR1 = the lane before within the group, LAST = the group's last lane, swaps for the sums)
-                constexpr int SHR1 = LPP == 4 ? F3DG_QP(0, 0, 1, 2) : F3DG_QP(0, 0, 2, 2);
-                constexpr int LAST = LPP == 4 ? F3DG_QP(3, 3, 3, 3) : F3DG_QP(1, 1, 3, 3);
+                constexpr int SHR1 = F3DG_QP(0, 0, 1, 2);
+                constexpr int LAST = F3DG_QP(3, 3, 3, 3);
                 float Pi = 1.0f - alpha;
                 float t = F3DG_QDPP(Pi, SHR1);
-                float Psh;
-                if constexpr (LPP == 4) {
-                    Pi *= sub >= 1u ? t : 1.0f;
-                    t = F3DG_QDPP(Pi, F3DG_QP(0, 1, 0, 1));
-                    Pi *= sub >= 2u ? t : 1.0f;
-                    Psh = F3DG_QDPP(Pi, SHR1);
-                } else {
-                    Psh = t;                                 // lane 1's exclusive product is lane 0's factor
-                    Pi *= sub >= 1u ? t : 1.0f;
-                }
+                Pi *= sub >= 1u ? t : 1.0f;
+                t = F3DG_QDPP(Pi, F3DG_QP(0, 1, 0, 1));
+                Pi *= sub >= 2u ? t : 1.0f;
+                const float Psh = F3DG_QDPP(Pi, SHR1);
                 const float Tb = Tf * (sub >= 1u ? Psh : 1.0f), tT = Tf * Pi;
                 const bool killed = !(tT >= 0.0001f);         // the stop (forward.cu:543-548), or an entry behind it
                 const float w = killed ? 0.0f : alpha * Tb;
@@ -509,10 +494,8 @@ render5p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                 float s1 = a1, s2 = a2;
                 t = F3DG_QDPP(s1, SHR1); s1 += sub >= 1u ? t : 0.0f;
                 t = F3DG_QDPP(s2, SHR1); s2 += sub >= 1u ? t : 0.0f;
-                if constexpr (LPP == 4) {
-                    t = F3DG_QDPP(s1, F3DG_QP(0, 1, 0, 1)); s1 += sub >= 2u ? t : 0.0f;
-                    t = F3DG_QDPP(s2, F3DG_QP(0, 1, 0, 1)); s2 += sub >= 2u ? t : 0.0f;
-                }
+                t = F3DG_QDPP(s1, F3DG_QP(0, 1, 0, 1)); s1 += sub >= 2u ? t : 0.0f;
+                t = F3DG_QDPP(s2, F3DG_QP(0, 1, 0, 1)); s2 += sub >= 2u ? t : 0.0f;
                 const float E1 = (s1 - a1) + D1, E2 = (s2 - a2) + D2;
                 Cd = fmaf(fmaf(-2.0f * pr.m, E1, fmaf(pr.m * pr.m, 1.0f - Tb, E2)), w, Cd);
                 D1 += F3DG_QDPP(s1, LAST);
@@ -521,7 +504,7 @@ render5p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                 // the pixel's new T; if one of the group stopped: T in front of the stopping entry = T - the weights blended before it
                 float ws = w;
                 ws += F3DG_QDPP(ws, F3DG_QP(1, 0, 3, 2));
-                if constexpr (LPP == 4) ws += F3DG_QDPP(ws, F3DG_QP(2, 3, 0, 1));
+                ws += F3DG_QDPP(ws, F3DG_QP(2, 3, 0, 1));
                 const float tT3 = F3DG_QDPP(tT, LAST);
                 const bool stop = !(tT3 >= 0.0001f);
                 Tf = stop ? Tf - ws : tT3;
@@ -534,18 +517,16 @@ render5p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
         }
     }
     // the four partial sums of a pixel meet; the median depth is the candidate of the highest rank
-#define F3DG_QSUM(x) do { x += F3DG_QDPP(x, F3DG_QP(1, 0, 3, 2)); if constexpr (LPP == 4) x += F3DG_QDPP(x, F3DG_QP(2, 3, 0, 1)); } while (0)
+#define F3DG_QSUM(x) do { x += F3DG_QDPP(x, F3DG_QP(1, 0, 3, 2)); x += F3DG_QDPP(x, F3DG_QP(2, 3, 0, 1)); } while (0)
     F3DG_QSUM(C0); F3DG_QSUM(C1); F3DG_QSUM(C2); F3DG_QSUM(C3); F3DG_QSUM(C4); F3DG_QSUM(C5); F3DG_QSUM(C7); F3DG_QSUM(Cd);
 #undef F3DG_QSUM
     {
         unsigned r = (unsigned)__builtin_amdgcn_update_dpp(0, (int)med_rank, F3DG_QP(1, 0, 3, 2), 0xf, 0xf, false);
         float tt = F3DG_QDPP(med_t, F3DG_QP(1, 0, 3, 2));
         if (r > med_rank) { med_rank = r; med_t = tt; }
-        if constexpr (LPP == 4) {
-            r = (unsigned)__builtin_amdgcn_update_dpp(0, (int)med_rank, F3DG_QP(2, 3, 0, 1), 0xf, 0xf, false);
-            tt = F3DG_QDPP(med_t, F3DG_QP(2, 3, 0, 1));
-            if (r > med_rank) { med_rank = r; med_t = tt; }
-        }
+        r = (unsigned)__builtin_amdgcn_update_dpp(0, (int)med_rank, F3DG_QP(2, 3, 0, 1), 0xf, 0xf, false);
+        tt = F3DG_QDPP(med_t, F3DG_QP(2, 3, 0, 1));
+        if (r > med_rank) { med_rank = r; med_t = tt; }
     }
     if (inside && sub == 0u) {
         const size_t HW = (size_t)H * W;
@@ -597,15 +578,9 @@ int f3dg_launch_render5_small(hipStream_t s, int V, int P, int W, int H, float f
 {
     const int tiles_x = (W + F3DG_TILE - 1) / F3DG_TILE, tiles_y = (H + F3DG_TILE - 1) / F3DG_TILE;
     const int T = tiles_x * tiles_y;
-    const int lpp = g_f3dg_render_scan_lanes == 2 ? 2 : 4;
-    if (lpp == 4)
-        F3DG_KLAUNCH(render5p_fwd_kernel<4>, dim3((unsigned)V * (unsigned)T * 4u), dim3(320), 0, s, V, P, W, H, tiles_x, T, focal_x, focal_y, hdr, ranges,
-                     point_list, rec, cull, background, bg_per_view, out_color);
-    else
-        F3DG_KLAUNCH(render5p_fwd_kernel<2>, dim3((unsigned)V * (unsigned)T * 4u), dim3(192), 0, s, V, P, W, H, tiles_x, T, focal_x, focal_y, hdr, ranges,
-                     point_list, rec, cull, background, bg_per_view, out_color);
-    snprintf(g_kernel_name5, sizeof g_kernel_name5, "render5p_fwd_kernel<%d lanes per pixel>", lpp);
-    g_f3dg_last_render_kernel = g_kernel_name5;
+    F3DG_KLAUNCH(render5p_fwd_kernel, dim3((unsigned)V * (unsigned)T * 4u), dim3(320), 0, s, V, P, W, H, tiles_x, T, focal_x, focal_y, hdr, ranges,
+                 point_list, rec, cull, background, bg_per_view, out_color);
+    g_f3dg_last_render_kernel = "render5p_fwd_kernel<4 lanes per pixel>";
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }

@@ -49,10 +49,9 @@ static_assert(sizeof(u64) * SMALL_STEPS * SMALL_WAVES <= 2 * sizeof(u32) * F3DG_
 // Gaussians is a latency chain per wave -- the sixteen waves of a CU each take a sixteenth of it.
 __global__ void __launch_bounds__(SMALL_THREADS)
 small_bin_kernel(u32 P, u32 T, u32 grid_x, F3dgHeader* __restrict__ hdr, const uint2* __restrict__ rects, const uint2* __restrict__ boxes,
-                 const u32* __restrict__ sort_keys, u32* __restrict__ list, u32* __restrict__ cnt, uint2* __restrict__ ranges, int debug_stop)
+                 const u32* __restrict__ sort_keys, u32* __restrict__ list, u32* __restrict__ cnt, uint2* __restrict__ ranges)
 {
     __shared__ SmallShared sh;
-    if (debug_stop == 1) return;
     const u32 seg = blockIdx.x, view = seg / T, tile = seg % T;
     const u32 tx = tile % grid_x, ty = tile / grid_x;
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -174,7 +173,7 @@ small_bin_kernel(u32 P, u32 T, u32 grid_x, F3dgHeader* __restrict__ hdr, const u
         cnt[seg] = over ? 0u : n;
         ranges[seg] = over ? make_uint2(0u, 0u) : make_uint2(slot_base, slot_base + n);
     }
-    if (over || n == 0u || debug_stop == 2)
+    if (over || n == 0u)
         return;
 
     // the hits' ids, in id order, into buffer 1 at the wave's offset: lane l expands the ballots of steps l, l + 64, ...
@@ -201,7 +200,6 @@ small_bin_kernel(u32 P, u32 T, u32 grid_x, F3dgHeader* __restrict__ hdr, const u
         }
     }
     __syncthreads();
-    if (debug_stop == 4) return;
     // depth key and quadrant mask of every hit (dense: at most four per thread), the key range of the list
     u32 kmin = 0xFFFFFFFFu, kmax = 0u;
     u32 mykey[F3DG_SMALL_CAP / SMALL_THREADS];
@@ -247,9 +245,8 @@ small_bin_kernel(u32 P, u32 T, u32 grid_x, F3dgHeader* __restrict__ hdr, const u
         if (i < n) k1[i] = mykey[j] - kmin;
     }
     __syncthreads();
-    if (debug_stop == 5) return;
     const u32 span = kmax - kmin;
-    const int key_bits = debug_stop == 3 ? 0 : span == 0u ? 0 : 32 - __builtin_clz(span);
+    const int key_bits = span == 0u ? 0 : 32 - __builtin_clz(span);
 
     // ---- 2. stable LSD radix sort by the depth bits; wave w owns entries [w q, (w + 1) q) of the current buffer
     const u32 q = ((n + 64u * SMALL_WAVES - 1u) / (64u * SMALL_WAVES)) * 64u;
@@ -355,8 +352,7 @@ int f3dg_launch_small_bin(hipStream_t s, int V, int P, int W, int H, const F3dgL
     const u32 T = grid_x * (u32)((H + F3DG_TILE - 1) / F3DG_TILE);
     F3DG_KLAUNCH(small_bin_kernel, dim3((u32)V * T), dim3(SMALL_THREADS), 0, s, (u32)P, T, grid_x, reinterpret_cast<F3dgHeader*>(ws + L.header),
                  reinterpret_cast<const uint2*>(ws + L.rects), reinterpret_cast<const uint2*>(ws + L.small_boxes), reinterpret_cast<const u32*>(ws + L.gsort),
-                 reinterpret_cast<u32*>(ws + L.small_list), reinterpret_cast<u32*>(ws + L.small_cnt), reinterpret_cast<uint2*>(ws + L.ranges),
-                 g_f3dg_small_debug);
+                 reinterpret_cast<u32*>(ws + L.small_list), reinterpret_cast<u32*>(ws + L.small_cnt), reinterpret_cast<uint2*>(ws + L.ranges));
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }

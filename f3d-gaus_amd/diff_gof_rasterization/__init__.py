@@ -86,7 +86,7 @@ class Workspace:
     def fits(self, P, W, H, n_views, max_rendered):
         """True (and the workspace now describes that call) if the buffer is large enough for it."""
         same = (self.P, self.W, self.H, self.n_views) == (P, W, H, n_views) and self.max_rendered >= max_rendered
-        # (asked again even for the same five numbers: the carving also depends on process options, e.g. sort_fused_rects)
+        # (asked again even for the same five numbers: the carving is the library's business)
         need = _lib.lib().f3dg_workspace_bytes(int(P), int(W), int(H), int(n_views), int(self.max_rendered if same else max_rendered))
         if need == 0 or need > self.buffer.numel():
             return False

@@ -398,13 +398,13 @@ int f3dg_residual_join_f16(void* stream, int N, int C, int HW, int nhwc, const u
  *                   rounds 2-5); "bwd_occ" (default 5): waves per SIMD the lock-step kernel is compiled for (2..6).
  *   "render_scan_min" (default 4) split-pixel mode: stragglers that hold fewer older-half entries than this finish the slide in fused trips.
  *   diagnostics: "render_count" (default 0) swaps in the counting variants of the compositing kernels (f3dg_debug_render_counts /
- *                   _render4_counts / _render5_counts); "time_launches" (default 0): f3dg_debug_launch_times.
- * A library built with -DF3DG_LAB (`F3DG_LAB=1 python f3d-gaus_amd/build.py --force`; f3dg_version() then ends in "lab") also compiles the
- * kernel generations and schedules that were measured and superseded -- the round-1 pixel-lane kernel and its filters ("render_kernel",
- * "render_pretest", "render_cull", "render_queue"), render2 ("render_round"), render3 with fixed windows ("render_slide", "render_dma"),
- * render3l ("render_split" 0), the tail schedule ("render_tail"), four-wave workgroups ("render_wpb"), "render_lds_pad",
- * "sort_wide_groups", "sort_fused_rects", "pre_hoist", "pre_order", "small_debug", "debug_skip_all", the staging replay ("render_replay")
- * -- for the bit-identity tests against the plain transcription and for A/B runs; NOTES.md has their measurements. */
+ *                   _render4_counts / _render5_counts); "time_launches" (default 0): f3dg_debug_launch_times; "reference_kernels"
+ *                   (default 0) 1 = the compositing forward and pass 1 of f3dg_integrate take the plain transcriptions of the reference
+ *                   (render_fwd_kernel, integrate_pass1_kernel: every pixel visits every entry of its tile's list, nothing is filtered) in
+ *                   the reference's arithmetic whatever the call's flags say, and no call takes the small-call path. The baseline the
+ *                   tests hold every other compositing path to, bit for bit; slow.
+ * Any other name is F3DG_ERR_BAD_ARG, among them the switches of the kernel generations that were measured and retired (NOTES.md has
+ * their measurements). */
 int f3dg_set_option(const char* name, int value);
 
 /* Diagnostic: number of kernels this library has launched from this process since the last reset (host-side counter, every
@@ -430,7 +430,7 @@ int f3dg_profile_collect_calls(double* h_stage_ms, int* h_calls, double* h_per_c
  * trips of slides that began with <= 8 / <= 24 live pixels, those slides, 0 ... }. */
 const char* f3dg_debug_last_render_kernel(void);
 int f3dg_debug_render_counts(unsigned long long* h_out8, int reset);
-/* The counters of the rank-packed kernel's counting variant (render_kernel = 4 with render_count = 1): h_out[SIXTEEN] = { list entries
+/* The counters of the rank-packed kernel's counting variant (render_pack with render_count = 1): h_out[SIXTEEN] = { list entries
  * staged, scanned, fused trips, slides, lane-trips of fused trips, waves, packed batches (= dense trips), blend trips of the batches,
  * pairs evaluated in dense trips, pairs that reached a blend trip, 0 ... }. */
 int f3dg_debug_render4_counts(unsigned long long* h_out, int reset);
@@ -463,9 +463,8 @@ int f3dg_debug_export(void* stream, const void* workspace, int P, int W, int H, 
                       unsigned* offsets, unsigned char* clamped, unsigned long long* keys_sorted,
                       unsigned* point_list, unsigned* ranges, float* final_T, unsigned* n_contrib, float* depths);
 
-/* Inspection hook of the compositing kernel: shader-clock cycles per wave, summed over all waves of all launches since the
- * last reset, h_out8 = {barrier waits, staging, list build, phase 1, phase 2, repack, total, waves}. Only a library built
- * with -DF3DG_TIMING (tools/render_timing.sh) counts; the product build returns zeros. BLOCKING (device-to-host copy). */
+/* Kept for callers of earlier versions: h_out8[8] was the phase timing of an instrumented compositing kernel. No kernel is
+ * instrumented any more: it returns zeros. */
 int f3dg_debug_timing(unsigned long long* h_out8, int reset);
 
 #ifdef __cplusplus

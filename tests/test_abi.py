@@ -98,18 +98,18 @@ def test_round3_host_logic(f3d):
     """Options, diagnostics, the small-call path's workspace carving and the integrate layouts: pure host arithmetic."""
     from f3dgaus_amd import _lib
     L = _lib.lib()
-    # the default library knows fifteen options and two diagnostics; the switches of the superseded generations exist in lab builds only
+    # the library knows fourteen options and three diagnostics; the switches of the retired kernel generations are unknown names
     defaults = ((b"render_fast", 1), (b"tile_cull", 1), (b"small_path", 2), (b"small_path_aux", 1), (b"render_lowocc", 1), (b"render_split", -1),
                 (b"render_unroll", -1), (b"render_pack", -1), (b"render_pack_th", 32), (b"render_scan", -1), (b"render_scan_th", 12), (b"render_scan_min", 4), (b"bwd_dense", 1), (b"bwd_occ", 5),
-                (b"render_count", 0), (b"time_launches", 0))
+                (b"render_count", 0), (b"time_launches", 0), (b"reference_kernels", 0))
     for name, v in defaults:
         assert L.f3dg_set_option(name, v) == 0, name
-    lab_only = ((b"render_kernel", 3), (b"render_slide", 1), (b"render_dma", 1), (b"render_lds_pad", 0), (b"small_debug", 0), (b"render_tail", 16), (b"render_tail", -1),
+    retired = ((b"render_kernel", 3), (b"render_slide", 1), (b"render_dma", 1), (b"render_lds_pad", 0), (b"small_debug", 0), (b"render_tail", 16), (b"render_tail", -1),
                 (b"sort_fused_rects", 1), (b"sort_fused_rects", 0), (b"pre_order", 3), (b"pre_order", 0), (b"render_wpb", 1), (b"render_pretest", 1),
-                (b"render_cull", 1), (b"render_queue", 1), (b"render_round", 192), (b"sort_wide_groups", 0), (b"pre_hoist", 0), (b"debug_skip_all", 0))
-    lab = L.f3dg_version().endswith(b"lab")
-    for name, v in lab_only:
-        assert L.f3dg_set_option(name, v) == (0 if lab else _lib.ERR_BAD_ARG), name
+                (b"render_cull", 1), (b"render_queue", 1), (b"render_round", 192), (b"sort_wide_groups", 0), (b"pre_hoist", 0), (b"debug_skip_all", 0),
+               (b"render_replay", 0), (b"tile_split", 1), (b"render_scan_lanes", 4))
+    for name, v in retired:
+        assert L.f3dg_set_option(name, v) == _lib.ERR_BAD_ARG, name
     assert L.f3dg_set_option(b"no_such_option", 1) == _lib.ERR_BAD_ARG
     assert L.f3dg_debug_launch_count(1) >= 0 and L.f3dg_debug_launch_count(0) == 0
     # the per-tile slots of the small-call path exist for one or two views of at most 2^18 Gaussians only: 4096 x 4 B per (view, tile)

@@ -43,33 +43,25 @@ def test_integrate_matches_oracle(name):
     assert_integrate_parity(o, h, name)
 
 
-@pytest.mark.lab
 @pytest.mark.parametrize("kw", [dict(P=20000, res=(128, 128), s0=0.03, view="oblique"),
                                 dict(P=3000, res=(96, 80), s0=0.3, view="oblique", aniso=True),        # large, flat splats
                                 dict(P=60000, res=(64, 64), s0=0.004, view="canonical")],               # sub-pixel splats
                          ids=["mid", "large_aniso", "tiny"])
 def test_integrate_filters_are_bit_identical(kw):
-    """The culled lists + K pre-test of pass 1 only remove (ray, Gaussian) pairs the reference `continue`s on."""
+    """The filters of pass 1 (545 shared rays per tile, the per-pixel ellipse test) only remove (ray, Gaussian) pairs the reference
+    `continue`s on: the default pass must match the plain transcription (option reference_kernels) bit for bit."""
     scene = make_scene(**kw)
     pts = make_points(scene, 50000)
     L = _lib.lib()
-    res = []
+    dev = torch.device("cuda:0")
+    h = hip_integrate(scene, pts, dev)
     try:
-        # (2, 1): the default, per-pixel ellipse test with Gaussians across the lanes; (1, 1): round 1's per-ray pre-test + box masks;
-        # (2, 0): the plain transcription every variant must match bit for bit
-        # (3, 1): the default, 545 shared rays per tile (integrate_pass1_rays_kernel); (2, 1): round 2's per-pixel pass
-        for kernel, on in ((3, 1), (2, 1), (1, 1), (2, 0)):
-            L.f3dg_set_option(b"render_kernel", kernel)
-            L.f3dg_set_option(b"render_pretest", on)
-            L.f3dg_set_option(b"render_cull", on)
-            res.append(run_both(scene, pts, torch.device("cuda:0"))[1])
+        assert L.f3dg_set_option(b"reference_kernels", 1) == 0
+        plain = hip_integrate(scene, pts, dev)
     finally:
-        L.f3dg_set_option(b"render_kernel", 3)
-        L.f3dg_set_option(b"render_pretest", 1)
-        L.f3dg_set_option(b"render_cull", 1)
-    for r in res[:3]:
-        for k in ("out", "ai", "ci", "radii"):
-            assert np.array_equal(r[k].view(np.uint32), res[3][k].view(np.uint32)), k
+        L.f3dg_set_option(b"reference_kernels", 0)
+    for k in ("out", "ai", "ci", "radii"):
+        assert np.array_equal(h[k].view(np.uint32), plain[k].view(np.uint32)), k
 
 
 def test_contributor_limit_tiles_are_redone_per_pixel():
@@ -95,13 +87,11 @@ def test_contributor_limit_tiles_are_redone_per_pixel():
     assert 0 < n.value <= 9, n.value                       # some of the 3 x 3 tiles, i.e. the limit was reached
     o, h = run_both(scene, pts, dev)
     assert_integrate_parity(o, h, "contributor limit")
-    if not L.f3dg_version().endswith(b"lab"):
-        return                                             # (the plain transcription is compiled in lab builds only)
     try:
-        L.f3dg_set_option(b"render_pretest", 0); L.f3dg_set_option(b"render_cull", 0)
+        assert L.f3dg_set_option(b"reference_kernels", 1) == 0
         plain = hip_integrate(scene, pts, dev)
     finally:
-        L.f3dg_set_option(b"render_pretest", 1); L.f3dg_set_option(b"render_cull", 1)
+        L.f3dg_set_option(b"reference_kernels", 0)
     for k in ("out", "ai", "ci", "radii"):
         assert np.array_equal(h[k].view(np.uint32), plain[k].view(np.uint32)), k
 

@@ -116,54 +116,6 @@ def test_forward_batched_views_equal_single_views(gpu_device, kw):
     assert total == h["num_rendered"]
 
 
-@pytest.mark.lab
-@pytest.mark.parametrize("kw", [
-    dict(P=8000, res=(128, 128), s0=0.03, view=[0, 1, 3, 5, 6, 2, 4, 7, 8]),
-    dict(P=4001, res=(96, 80), s0=0.2, view=[0, 3, 5], depth_range=(1.0, 30.0)),       # four-pass views: the last pass is pass 3
-], ids=["compact", "four_pass"])
-def test_fused_rectangle_gather_is_invisible(gpu_device, kw):
-    """Option sort_fused_rects (a view's last depth pass also delivers its tile rectangles in sorted order; measured equal, off by
-    default) against the separate gather launch: lists, ranges and images identical."""
-    from f3dgaus_amd import _lib
-    scene = make_scene(**kw)
-    L = _lib.lib()
-    a = run_hip(scene, gpu_device)
-    try:
-        assert L.f3dg_set_option(b"sort_fused_rects", 1) == 0
-        b = run_hip(scene, gpu_device)
-    finally:
-        L.f3dg_set_option(b"sort_fused_rects", 0)
-    assert a["num_rendered"] == b["num_rendered"]
-    for k in ("point_list", "ranges", "keys_sorted"):
-        assert np.array_equal(a[k], b[k]), k
-    assert np.array_equal(a["out_color"].view(np.uint32), b["out_color"].view(np.uint32))
-
-
-@pytest.mark.lab
-@pytest.mark.parametrize("save_aux", [True, False])
-def test_projection_hoist_is_bit_identical(gpu_device, save_aux):
-    """Option pre_hoist (round 5): the view-independent part of the projection -- 3D covariance, rotation matrix, float64 scale
-    reciprocals -- computed once per Gaussian by preprocess_hoist_kernel and read by the per-(view, Gaussian) threads instead of being
-    recomputed per view. Same operations in the same order: records, radii, lists and images identical to the bit."""
-    from f3dgaus_amd import _lib
-    scene = make_scene(P=9000, res=(128, 96), s0=0.03, view=[0, 1, 3, 5, 6, 2], aniso=True, scale_modifier=0.8)
-    L = _lib.lib()
-    a = run_hip(scene, gpu_device, save_aux=save_aux)
-    try:
-        assert L.f3dg_set_option(b"pre_hoist", 1) == 0
-        L.f3dg_debug_launch_count(1)
-        b = run_hip(scene, gpu_device, save_aux=save_aux)
-    finally:
-        L.f3dg_set_option(b"pre_hoist", 0)
-    assert a["num_rendered"] == b["num_rendered"]
-    vis = a["radii"] > 0
-    for k in ("radii", "point_list", "ranges"):
-        assert np.array_equal(a[k], b[k]), k
-    for k in ("view2gaussian", "opac", "rgb"):
-        assert np.array_equal(a[k][vis].view(np.uint32), b[k][vis].view(np.uint32)), k
-    assert np.array_equal(a["out_color"].view(np.uint32), b["out_color"].view(np.uint32))
-
-
 @pytest.mark.parametrize("which", ["cov3D+view2gaussian", "view2gaussian"])
 def test_precomputed_covariance_and_view2gaussian(which, gpu_device):
     """cov3D_precomp replaces scales / rotations in the 2D footprint (forward.cu:338-348), view2gaussian_precomp replaces the
@@ -211,26 +163,26 @@ def test_c2_view_with_large_splats_full_size(gpu_device):
     assert (h["n_contrib"][0] == o["n_contrib"]).mean() >= 0.999
 
 
-@pytest.mark.lab
 def test_wide_group_stream_is_identical(gpu_device):
-    """The binning stage carries (view << tile_bits | tile) as u16 when it fits, else u32: both must give the same lists
-    (the u32 path is otherwise only reached with more than 65,536 (view, tile) groups)."""
-    from f3dgaus_amd import _lib
-    L = _lib.lib()
-    res = []
-    try:
-        for wide in (0, 1):
-            L.f3dg_set_option(b"sort_wide_groups", wide)
-            for name in ("F5_odd_size", "F9_long_tile_lists", "F10_huge_tile_lists", "F11_wide_radix"):
-                res.append((wide, name, run_hip(make_scene(**SCENES[name]), gpu_device)))
-            res.append((wide, "multi", run_hip(make_scene(P=8000, res=(128, 128), s0=0.03, view=[0, 1, 3, 5, 6, 2, 4, 7, 8]), gpu_device)))
-    finally:
-        L.f3dg_set_option(b"sort_wide_groups", 0)
-    half = len(res) // 2
-    for (w0, n0, a), (w1, n1, b) in zip(res[:half], res[half:]):
-        assert n0 == n1 and w0 != w1
-        for k in ("point_list", "keys_sorted", "ranges", "out_color"):
-            assert np.array_equal(a[k], b[k]), (n0, k)
+    """66 views of 512^2 (1,024 tiles: 10 tile bits) in one call: (view << tile_bits | tile) does not fit 16 bits, so the binning stage
+    carries the u32 group stream through two evenly split tile passes (5 + 5 bits). The same views in calls of at most 64 views take the
+    u16 stream: per-view lists, ranges and images must be identical."""
+    cams = [i % 9 for i in range(66)]
+    assert ((len(cams) - 1) << 10 | 1023) > 0xFFFF and ((64 - 1) << 10 | 1023) <= 0xFFFF
+    scene = make_scene(P=1500, res=(512, 512), s0=0.02, view=cams)
+    wide = run_hip(scene, gpu_device)
+    total = 0
+    for a, b in ((0, 64), (64, 66)):
+        part = dict(scene, **{k: scene[k][a:b].contiguous() for k in ("viewmatrix", "projmatrix", "campos")})
+        h = run_hip(part, gpu_device)
+        R = h["num_rendered"]
+        assert np.array_equal(wide["point_list"][total:total + R], h["point_list"][:R]), (a, b)
+        wr = wide["ranges"][a:b].astype(np.int64)
+        assert np.array_equal(wr - total * (wr.sum(-1, keepdims=True) > 0), h["ranges"].astype(np.int64)), (a, b)
+        for k in ("out_color", "final_T", "n_contrib"):
+            assert np.array_equal(wide[k][a:b].view(np.uint32), h[k].view(np.uint32)), (a, b, k)
+        total += R
+    assert total == wide["num_rendered"] > 0
 
 
 def test_empty_and_all_culled(gpu_device):
@@ -276,54 +228,50 @@ def test_c1_full_size_single_view(gpu_device):
     assert_render_parity(h["out_color"][0], o["out_color"], "C1")
 
 
-@pytest.mark.lab
 @pytest.mark.parametrize("name", ["F1_tiny_identity", "F2_oblique_aniso", "F5_odd_size", "F6_small_splats", "F4_filter_scalemod", "C1", "tiny_sigma", "huge_sigma"])
 def test_pretest_is_conservative_bit_identical_outputs(name, gpu_device):
-    """The float32 pre-test of the compositing kernel may only skip pairs whose alpha is certainly < 1/255:
-    every output and every auxiliary plane must be bit-identical with it on and off."""
+    """The compositing kernels may only skip pairs whose alpha is certainly < 1/255 (quadrant masks, conservative ellipses): every
+    output and every auxiliary plane of every compositing path must be bit-identical to the plain transcription's (option
+    reference_kernels: render_fwd_kernel, every pixel visits every entry of its tile's list). The transcription computes in the
+    reference's arithmetic only; in fast arithmetic the paths are held to render3s."""
+    import helpers
     from f3dgaus_amd import _lib
     extra = {"C1": dict(P=65536, res=(256, 256), s0=0.01, view="oblique"),
              "tiny_sigma": dict(P=20000, res=(256, 256), s0=0.003, view="oblique"),
              "huge_sigma": dict(P=1500, res=(64, 64), s0=0.3, view="canonical")}
     scene = make_scene(**(SCENES[name] if name in SCENES else extra[name]))
     L = _lib.lib()
+    exact = helpers.RENDER_MODE == "exact"
+    variants = []
     try:
-        assert L.f3dg_set_option(b"render_kernel", 1) == 0
-        for o in (b"render_pretest", b"render_cull", b"render_queue"):
-            assert L.f3dg_set_option(o, 0) == 0
-        a = run_hip(scene, gpu_device)              # plain transcription-order kernel
-        variants = []
-        for pre, cull, que in ((1, 0, 0), (0, 1, 0), (1, 1, 0), (0, 0, 1), (1, 0, 1), (0, 1, 1), (1, 1, 1)):
-            L.f3dg_set_option(b"render_pretest", pre); L.f3dg_set_option(b"render_cull", cull); L.f3dg_set_option(b"render_queue", que)
+        if exact:
+            assert L.f3dg_set_option(b"reference_kernels", 1) == 0
+            a = run_hip(scene, gpu_device)              # plain transcription-order kernel
+            assert b"render_fwd_kernel" in L.f3dg_debug_last_render_kernel(), L.f3dg_debug_last_render_kernel()
+            L.f3dg_set_option(b"reference_kernels", 0)
+        L.f3dg_set_option(b"render_lowocc", 0)          # the general path: sliding half-windows (render3s_fwd_kernel) ...
+        L.f3dg_set_option(b"render_pack", 0)
+        variants.append(run_hip(scene, gpu_device))
+        assert b"render3s" in L.f3dg_debug_last_render_kernel(), L.f3dg_debug_last_render_kernel()
+        L.f3dg_set_option(b"render_pack", 1)            # ... and the rank-packed kernel
+        variants.append(run_hip(scene, gpu_device))
+        assert b"render4" in L.f3dg_debug_last_render_kernel(), L.f3dg_debug_last_render_kernel()
+        L.f3dg_set_option(b"render_pack", -1)
+        L.f3dg_set_option(b"render_lowocc", 1)          # the multi-wave kernels of small launches (every scene here is one)
+        for split, kernel in ((1, b"render3p"), (2, b"render3q"), (3, b"render3q")):
+            L.f3dg_set_option(b"render_split", split)
             variants.append(run_hip(scene, gpu_device))
-        L.f3dg_set_option(b"render_kernel", 2)      # render2: four waves per tile, Gaussians across the lanes + conservative ellipse in phase 1
-        for rnd in (192, 256):                      # list entries staged per round (fast arithmetic: 192 by default)
-            L.f3dg_set_option(b"render_round", rnd)
-            variants.append(run_hip(scene, gpu_device))
-        L.f3dg_set_option(b"render_kernel", 3)      # render3 (default): one wave64 per 8x8 quadrant, quadrant masks from the binning stage
-        variants.append(run_hip(scene, gpu_device))   # the default for launches this small: render3l_fwd_kernel (prefetching windows)
-        L.f3dg_set_option(b"render_lowocc", 0)
-        variants.append(run_hip(scene, gpu_device))   # the default for everything larger: sliding half-windows (render3s_fwd_kernel)
-        for tail in (64, 24, 5, 0):                   # ... with the tail schedule from at most `tail` unsaturated pixels per quadrant on
-            L.f3dg_set_option(b"render_tail", tail)
-            variants.append(run_hip(scene, gpu_device))
-        L.f3dg_set_option(b"render_slide", 0)         # fixed 64-entry windows,
-        for dma in (1, 0):                          # records staged by global_load_lds / through registers
-            L.f3dg_set_option(b"render_dma", dma)
-            variants.append(run_hip(scene, gpu_device))
+            assert kernel in L.f3dg_debug_last_render_kernel(), L.f3dg_debug_last_render_kernel()
     finally:
-        L.f3dg_set_option(b"render_kernel", 3)
-        L.f3dg_set_option(b"render_slide", 1)
+        L.f3dg_set_option(b"reference_kernels", 0)
         L.f3dg_set_option(b"render_lowocc", 1)
-        L.f3dg_set_option(b"render_dma", 1)
-        L.f3dg_set_option(b"render_round", 192)
-        L.f3dg_set_option(b"render_tail", -1)
-        for o in (b"render_pretest", b"render_cull", b"render_queue"):
-            L.f3dg_set_option(o, 1)
+        L.f3dg_set_option(b"render_pack", -1)
+        L.f3dg_set_option(b"render_split", -1)
+    if not exact:
+        a = variants.pop(0)
     for b in variants:
         for k in ("out_color", "final_T", "n_contrib"):
             assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
-    assert L.f3dg_set_option(b"no_such_option", 1) == _lib.ERR_BAD_ARG
 
 
 @pytest.mark.parametrize("name", ["F2_oblique_aniso", "F5_odd_size", "F6_small_splats", "F9_long_tile_lists", "C1", "pixel_aligned", "thin"])
@@ -445,36 +393,6 @@ def test_small_launch_kernels_bit_identical(name, gpu_device):
     for v in range(V):
         o = run_oracle(scene, view=v)
         assert_render_parity(res["split", 2, False]["out_color"][v], o["out_color"], "small launch %s view %d" % (name, v))
-
-
-@pytest.mark.lab
-@pytest.mark.parametrize("tail", [64, 16, 3])
-def test_tail_schedule_thin_coverage(tail, gpu_device):
-    """The tail schedule of the one-wave kernel (option render_tail) on the case it exists for: long tile lists of faint
-    Gaussians, so that pixels never saturate and walk the whole list (several views, odd image size, inference and SAVE_AUX
-    calls). Held against the oracle and bit-identical to the sliding-window schedule."""
-    from f3dgaus_amd import _lib
-    scene = make_scene(P=40000, res=(120, 88), s0=0.03, view="oblique", n_views=3, seed=7)
-    scene["opacities"] = scene["opacities"] * 0.04        # ~40 entries per pixel, alpha <= 0.04 each: T stays far above 1e-4
-    L = _lib.lib()
-    try:
-        L.f3dg_set_option(b"render_lowocc", 0)
-        L.f3dg_set_option(b"render_tail", 0)
-        a = run_hip(scene, gpu_device)
-        a_inf = run_hip(scene, gpu_device, save_aux=False)
-        L.f3dg_set_option(b"render_tail", tail)
-        b = run_hip(scene, gpu_device)
-        b_inf = run_hip(scene, gpu_device, save_aux=False)
-    finally:
-        L.f3dg_set_option(b"render_lowocc", 1)
-        L.f3dg_set_option(b"render_tail", -1)
-    for k in ("out_color", "final_T", "n_contrib"):
-        assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
-    assert np.array_equal(a_inf["out_color"].view(np.uint32), b_inf["out_color"].view(np.uint32))
-    assert float(b["final_T"][:, 0].min()) > 1e-3         # nothing saturated: every quadrant went through its whole list
-    for v in range(3):
-        o = run_oracle(scene, view=v)
-        assert_render_parity(b["out_color"][v], o["out_color"], "tail %d view %d" % (tail, v))
 
 
 @pytest.mark.parametrize("seed", range(12))

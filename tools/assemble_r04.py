@@ -94,9 +94,9 @@ def main():
     if len(sys.argv) > 3:
         ab = sys.argv[3]
         out = ["# A/B lines of round 4's second GPU session (`tools/ab_r04b.sh`): per-stage ms min / median / max over the steps, frame hash", ""]
-        for f, title in (("ab_fused.log", "## option sort_fused_rects (the rectangle gather inside a view's last depth pass)"),
-                         ("ab_tail.log", "## option render_tail = N (the tail schedule of the one-wave compositing kernel from at most N live pixels on)"),
-                         ("../r04c/ab_pre_order.log", "## option pre_order (1: chunk-major projection grid, 2: streaming stores for the record + ellipse, 3: both) -- `tools/ab_r04c.sh`")):
+        for f, title in (("ab_fused.log", "## the rectangle gather inside a view's last depth pass (a retired option)"),
+                         ("ab_tail.log", "## the tail schedule of the one-wave compositing kernel (a retired option: from at most N live pixels on)"),
+                         ("../r04c/ab_pre_order.log", "## projection grid order (a retired option; 1: chunk-major projection grid, 2: streaming stores for the record + ellipse, 3: both) -- `tools/ab_r04c.sh`")):
             p = os.path.join(ab, f)
             if os.path.exists(p):
                 out += [title, "", "```"] + [x.rstrip() for x in open(p) if "amdgpu.ids" not in x] + ["```", ""]

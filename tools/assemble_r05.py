@@ -134,7 +134,7 @@ open(os.path.join(dst, "compositing_packed.md"), "w").write("\n".join(L) + "\n")
 # ---- projection_hoist.md
 d = os.path.join(GO, "r05_hoist")
 if os.path.isdir(d):
-    L = ["# Projection with the per-Gaussian hoist through memory (option `pre_hoist`; `tools/ab_r05e.sh`, alternating runs on one box)", "",
+    L = ["# Projection with the per-Gaussian hoist through memory (a retired option; `tools/ab_r05e.sh`, alternating runs on one box)", "",
          "| run | views/s | projection ms | binning ms | compositing ms |", "|---|---:|---:|---:|---:|"]
     for f in sorted(glob.glob(os.path.join(d, "*.log"))):
         j = lj(f)

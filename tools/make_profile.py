@@ -12,7 +12,7 @@ import shutil
 import sys
 
 SIMDS = 1024          # 256 CUs x 4 SIMDs (MI355X_MICROARCH.md)
-RENDER_KERNELS = ("render3s_fwd_kernel", "render3_fwd_kernel", "render2_fwd_kernel", "render_fwd_kernel")
+RENDER_KERNELS = ("render3s_fwd_kernel", "render_fwd_kernel")
 
 
 def short(name):
