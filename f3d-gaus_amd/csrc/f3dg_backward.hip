@@ -18,6 +18,7 @@
 // reproducible to rounding where the reference is not.
 #include "f3dg_common.h"
 #include "f3dg_ellipse.h"
+#include "f3dg_quad.h"
 
 namespace {
 
@@ -136,10 +137,10 @@ __device__ __forceinline__ double row_total(double v)
 // forward (f3dg_render.hip, render3s_fwd_kernel):
 //   * a workgroup is one wave that owns a quadrant from its deepest last contributor back to the first list entry; nothing is
 //     shared with the other quadrants of the tile and nothing waits at a barrier;
-//   * the wave scans the tile's list BACKWARDS 64 ids at a time and keeps the entries whose quadrant bit is set (F3DG_ID_BITS);
-//   * a window of 64 kept entries is staged (record by global_load_lds, 2D conic, centre) and tested with the Gaussians across the
-//     lanes against the conservative ellipse (quad_ballots_any): every pixel gets its pass mask and the wave the mask of entries
-//     that can reach ANY of its pixels -- the others are never looked at;
+//   * the wave scans the tile's list BACKWARDS 64 ids at a time and keeps the entries whose quadrant bit is set (F3DG_ID_BITS); a window
+//     of 64 kept entries is staged and tested against the conservative ellipse: every pixel gets its pass mask and the wave the mask of
+//     entries that can reach ANY of its pixels -- the others are never looked at (F3dgBwdWindow, f3dg_quad.h, shared with
+//     render5_bwd_kernel);
 //   * the surviving entries are walked in lock-step, back to front, because the 17 partials of a Gaussian are reduced across the
 //     wave before they touch memory.
 template <int OCC>
@@ -155,73 +156,25 @@ render3_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                    float* __restrict__ dL_dmean2D, float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolors,
                    double* __restrict__ dL_dv2g_acc)
 {
-    unsigned view, unit;
-    f3dg_xcd_map(blockIdx.x, (unsigned)V, 4u * (unsigned)T, view, unit);
-    const unsigned tile = unit >> 2, quad = unit & 3u;
-    const unsigned tile_x = tile % (unsigned)tiles_x, tile_y = tile / (unsigned)tiles_x;
+    const F3dgQuad qd = f3dg_quad(V, T, tiles_x);
     const unsigned lane = threadIdx.x;
-    const unsigned qx0 = tile_x * F3DG_TILE + (quad & 1u) * 8u, qy0 = tile_y * F3DG_TILE + (quad >> 1) * 8u;
-    const unsigned pix_x = qx0 + (lane & 7u), pix_y = qy0 + (lane >> 3);
-    const bool inside = pix_x < (unsigned)W && pix_y < (unsigned)H;
-    const size_t HW = (size_t)H * W;
-    const size_t pix_id = (size_t)W * pix_y + pix_x;
-    const float pixf_x = (float)pix_x + 0.5f, pixf_y = (float)pix_y + 0.5f;
-    const float ray_x = (float)((pixf_x - W / 2.) / focal_x);
-    const float ray_y = (float)((pixf_y - H / 2.) / focal_y);
-
-    uint2 range = ranges[(size_t)view * T + tile];
-    // no lists to walk after an overflow -- and none that belong to this call when the workspace's last forward kept no auxiliary
-    // planes (an inference call): all gradients stay zero, the header says why
-    // (a one-view forward with auxiliary planes may have taken the small-call path: its lists live in the per-tile slots)
-    const unsigned* __restrict__ point_list = hdr->small_path != 0u ? small_list : point_list_general;
-    if (hdr->overflow || hdr->save_aux == 0u) {
-        range = make_uint2(0, 0);
-        if (!hdr->overflow && blockIdx.x == 0 && threadIdx.x == 0) const_cast<F3dgHeader*>(hdr)->bwd_stale = 1u;
-    }
+    const auto [pix_x, pix_y, inside, pix_id, ray_x, ray_y] = f3dg_quad_pixel(qd, lane, W, H, focal_x, focal_y);
 
     __shared__ float4 sR[4][64];          // records of the window, [16-byte chunk][entry] (global_load_lds image)
     __shared__ float4 sC[64];             // 2D conic + opacity * coef
     __shared__ float2 sX[64];             // projected centre
-    __shared__ uint2 sQ[128];             // (list position, Gaussian id) of the kept entries, ring
+    __shared__ uint2 sQ[F3DG_QUAD_RING];  // (list position, Gaussian id) of the kept entries, ring
 
-    const bool alpha_fast = hdr->alpha_fast != 0;
-    const size_t vP = (size_t)view * P;
-    const F3dgRec* vrec = rec + vP;
-    const float4* vcull = cull + vP;
-    const float* fT = final_T + (size_t)view * 4 * HW;
-    const unsigned* nc = n_contrib + (size_t)view * 2 * HW;
-    const float* dpix = dL_dpixels + (size_t)view * F3DG_OUT_CHANNELS * HW;
-    const float* bg = background + (bg_per_view ? 3 * view : 0);
-
-    const float T_final = inside ? fT[pix_id] : 0;
-    float Tr = T_final;
-    const float final_D = inside ? fT[pix_id + HW] : 0;
-    const float final_A = 1 - T_final;
-    const float dL_dreg = inside ? dpix[8 * HW + pix_id] : 0;
-
-    const int last_contributor = inside ? (int)nc[pix_id] : 0;
-    const int max_contributor = inside ? (int)nc[pix_id + HW] : 0;
+    F3dgBwdWindow<false> w(sR, sC, sX, nullptr, sQ, qd, inside, pix_id, lane, P, T, W, H, hdr, ranges, point_list_general, small_list, rec, cull,
+                           means2D, conic, background, bg_per_view, final_T, n_contrib, dL_dpixels);
+    const size_t vP = w.vP;
+    const float pixf_x = (float)pix_x + 0.5f, pixf_y = (float)pix_y + 0.5f;
+    float Tr = w.T_final;
     float accum_rec0 = 0, accum_rec1 = 0, accum_rec2 = 0;
-    float dpx0 = 0, dpx1 = 0, dpx2 = 0, dn0 = 0, dn1 = 0, dn2 = 0, dL_dmax_depth = 0;
-    if (inside) {
-        dpx0 = dpix[pix_id]; dpx1 = dpix[HW + pix_id]; dpx2 = dpix[2 * HW + pix_id];
-        dn0 = dpix[3 * HW + pix_id]; dn1 = dpix[4 * HW + pix_id]; dn2 = dpix[5 * HW + pix_id];
-        dL_dmax_depth = dpix[6 * HW + pix_id];
-    }
     float last_alpha = 0;
     float last_c0 = 0, last_c1 = 0, last_c2 = 0;
     float last_n0 = 0, last_n1 = 0, last_n2 = 0;
     float acc_n0 = 0, acc_n1 = 0, acc_n2 = 0;
-    const float ddelx_dx = (float)(0.5 * W);
-    const float ddely_dy = (float)(0.5 * H);
-    const float bg_dot_dpixel = bg[0] * dpx0 + bg[1] * dpx1 + bg[2] * dpx2;
-
-    // entries at or behind a pixel's last contributor are skipped by the reference one by one (backward.cu:745-746): the wave starts
-    // at the deepest last contributor of ITS 64 pixels
-    const int wave_last = min((int)__builtin_amdgcn_readfirstlane((int)__reduce_max_sync(~0ull, last_contributor)),
-                              (int)(range.y - range.x));
-    const unsigned qbit = 1u << (F3DG_ID_BITS + quad);
-    const unsigned long long lt = (1ull << lane) - 1ull;
     unsigned n_pairs = 0;                 // contributing (pixel, Gaussian) pairs of this wave
 
     // Where lane 15 of row r adds its totals (see the reduction below): everything but the Gaussian id is fixed per lane, so the
@@ -232,73 +185,15 @@ render3_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
     const unsigned stride1 = row < 2 ? 12u : 4u;
     char* const addD = reinterpret_cast<char*>(dL_dv2g_acc + vP * 10 + row);                                                           // stride 80
 
-    unsigned cursor = (unsigned)wave_last, qhead = 0, qcount = 0;     // list positions [0, cursor) are still to be scanned
-    unsigned idn = lane < cursor ? point_list[range.x + cursor - 1u - lane] : 0u;       // back to front: lane l reads position cursor - 1 - l
-    for (;;) {
-        while (qcount < 64u && cursor != 0u) {
-            const unsigned idm = idn;
-            const bool valid = lane < cursor;
-            const unsigned pos = cursor - 1u - lane;
-            cursor = cursor > 64u ? cursor - 64u : 0u;
-            idn = lane < cursor ? point_list[range.x + cursor - 1u - lane] : 0u;
-            const bool keep = valid && (idm & qbit) != 0u;
-            const unsigned long long kb = __ballot(keep);
-            if (keep) sQ[(qhead + qcount + (unsigned)__popcll(kb & lt)) & 127u] = make_uint2(pos, idm & F3DG_ID_MASK);
-            qcount += (unsigned)__popcll(kb);
-        }
-        if (qcount == 0u)
-            break;
-        const unsigned m = qcount < 64u ? qcount : 64u;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-        float4 e4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        float ec = 0.0f;
-        if (lane < m) {
-            const unsigned id = sQ[(qhead + lane) & 127u].y;
-            const float4* src = reinterpret_cast<const float4*>(vrec + id);
-#pragma unroll
-            for (int c = 0; c < 4; c++)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + c),
-                                                 (__attribute__((address_space(3))) void*)&sR[c][0], 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(conic + vP + id),
-                                             (__attribute__((address_space(3))) void*)&sC[0], 16, 0, 0);
-            e4 = vcull[id];
-            sX[lane] = means2D[vP + id];
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane < m) ec = sR[3][lane].w;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-        // ---- phase 1: lane e tests entry e against the 64 pixels of the quadrant
-        int pass_lo = 0, pass_hi = 0;
-        unsigned long long any = 0ull;
-        {
-            const float u0 = lane < m ? (float)qx0 - e4.x : __builtin_nanf("");
-            const float v0 = (float)qy0 - e4.y;
-            float dxx[8], adx[8], dyy[8], cdy[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                dxx[q] = u0 + (float)q;
-                adx[q] = e4.z * dxx[q];
-                dyy[q] = v0 + (float)q;
-                cdy[q] = ec * dyy[q] * dyy[q];
-            }
-            quad_ballots_any<0>(pass_lo, pass_hi, any, fmaf(dxx[0], fmaf(e4.w, dyy[0], adx[0]), cdy[0]), dxx, adx, dyy, cdy, e4.w);
-        }
-        const unsigned long long pass = ((unsigned long long)(unsigned)pass_hi << 32) | (unsigned)pass_lo;
-
+    while (w.next()) {
         // ---- lock-step walk over the entries that reach at least one pixel, back to front (window slot order)
-        unsigned long long todo = any;
+        unsigned long long todo = w.any;
         while (todo != 0ull) {
             const int j = __builtin_ctzll(todo);
             todo &= todo - 1ull;
-            const uint2 pe = sQ[(qhead + (unsigned)j) & 127u];
+            const uint2 pe = w.entry((unsigned)j);
             const int contributor = (int)pe.x;                             // 0-based position from the front
-            bool active = inside && ((pass >> j) & 1ull) != 0ull && contributor < last_contributor;
+            bool active = inside && ((w.pass >> j) & 1ull) != 0ull && contributor < w.last_contributor;
             if (__ballot(active) == 0)
                 continue;
 
@@ -312,7 +207,7 @@ render3_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
             const float CC = q2.y;
             float t = 0, G = 0, alpha = 0;
             if (active) {
-                if (alpha_fast) {
+                if (w.alpha_fast) {
                     // the forward of this workspace took the fast arithmetic: the same function, to the bit
                     f3dg_fast_t_G(aaf, bhalf, CC, t, G);
                     if (t < 0.2f) active = false;
@@ -366,28 +261,28 @@ render3_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                 float dL_dalpha = 0.0f;
                 const float c0 = q3.x, c1 = q3.y, c2 = q3.z;
                 accum_rec0 = last_alpha * last_c0 + (1.f - last_alpha) * accum_rec0; last_c0 = c0;
-                dL_dalpha += (c0 - accum_rec0) * dpx0;
-                g_col0 = dchannel_dcolor * dpx0;
+                dL_dalpha += (c0 - accum_rec0) * w.dpx0;
+                g_col0 = dchannel_dcolor * w.dpx0;
                 accum_rec1 = last_alpha * last_c1 + (1.f - last_alpha) * accum_rec1; last_c1 = c1;
-                dL_dalpha += (c1 - accum_rec1) * dpx1;
-                g_col1 = dchannel_dcolor * dpx1;
+                dL_dalpha += (c1 - accum_rec1) * w.dpx1;
+                g_col1 = dchannel_dcolor * w.dpx1;
                 accum_rec2 = last_alpha * last_c2 + (1.f - last_alpha) * accum_rec2; last_c2 = c2;
-                dL_dalpha += (c2 - accum_rec2) * dpx2;
-                g_col2 = dchannel_dcolor * dpx2;
+                dL_dalpha += (c2 - accum_rec2) * w.dpx2;
+                g_col2 = dchannel_dcolor * w.dpx2;
 
                 float dL_dmax_t = 0.0f;
-                dL_dmax_t += 2.0f * (Tr * alpha) * (mapped_max_t * final_A - final_D) * dL_dreg * dmax_t_dd;
+                dL_dmax_t += 2.0f * (Tr * alpha) * (mapped_max_t * w.final_A - w.final_D) * w.dL_dreg * dmax_t_dd;
                 dL_dalpha += 0.f - 0.f;
 
                 acc_n0 = last_alpha * last_n0 + (1.f - last_alpha) * acc_n0; last_n0 = nn0;
-                dL_dalpha += (nn0 - acc_n0) * dn0;
-                const float dnn0 = alpha * Tr * dn0;
+                dL_dalpha += (nn0 - acc_n0) * w.dn0;
+                const float dnn0 = alpha * Tr * w.dn0;
                 acc_n1 = last_alpha * last_n1 + (1.f - last_alpha) * acc_n1; last_n1 = nn1;
-                dL_dalpha += (nn1 - acc_n1) * dn1;
-                const float dnn1 = alpha * Tr * dn1;
+                dL_dalpha += (nn1 - acc_n1) * w.dn1;
+                const float dnn1 = alpha * Tr * w.dn1;
                 acc_n2 = last_alpha * last_n2 + (1.f - last_alpha) * acc_n2; last_n2 = nn2;
-                dL_dalpha += (nn2 - acc_n2) * dn2;
-                const float dnn2 = alpha * Tr * dn2;
+                dL_dalpha += (nn2 - acc_n2) * w.dn2;
+                const float dnn2 = alpha * Tr * w.dn2;
 
                 float dL_dlength = (dnn0 * n0 + dnn1 * n1 + dnn2 * n2);
                 dL_dlength *= inv_len * inv_len;
@@ -396,21 +291,21 @@ render3_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                 float dLn2 = (-dnn2 + dL_dlength * n2) * inv_len;
 
                 float dL_dt = dL_dmax_t;
-                if (contributor == max_contributor - 1)
-                    dL_dt += dL_dmax_depth;
+                if (contributor == w.max_contributor - 1)
+                    dL_dt += w.dL_dmax_depth;
 
                 dL_dalpha *= Tr;
                 last_alpha = alpha;
-                dL_dalpha += (-T_final * inv_oma) * bg_dot_dpixel;
+                dL_dalpha += (-w.T_final * inv_oma) * w.bg_dot_dpixel;
 
                 const float dL_dG = con.w * dL_dalpha;
                 const float gdx = G * d_x;
                 const float gdy = G * d_y;
                 const float dG_ddelx = -gdx * con.x - gdy * con.y;
                 const float dG_ddely = -gdy * con.z - gdx * con.y;
-                g_mx = dL_dG * dG_ddelx * ddelx_dx;
-                g_my = dL_dG * dG_ddely * ddely_dy;
-                g_mz = fabsf(dL_dG * dG_ddelx * ddelx_dx) + fabsf(dL_dG * dG_ddely * ddely_dy);
+                g_mx = dL_dG * dG_ddelx * w.ddelx_dx;
+                g_my = dL_dG * dG_ddely * w.ddely_dy;
+                g_mz = fabsf(dL_dG * dG_ddelx * w.ddelx_dx) + fabsf(dL_dG * dG_ddely * w.ddely_dy);
                 g_op = G * dL_dalpha;
 
                 const float dL_dpower = dL_dG * G;
@@ -455,11 +350,7 @@ render3_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                 if (row < 2) unsafeAtomicAdd(acc + 8, (double)d2);
             }
         }
-        qhead += m;
-        qcount -= m;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the window's slots are rewritten by the next one
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        w.retire();
     }
     if (lane == 0 && n_pairs)
         atomicAdd(&hdr->bwd_pairs, (unsigned long long)n_pairs);

@@ -20,6 +20,7 @@
 // (tests/test_raster_backward_gpu.py runs with either kernel).
 #include "f3dg_common.h"
 #include "f3dg_ellipse.h"
+#include "f3dg_quad.h"
 #include "f3dg_segscan.h"
 
 int g_f3dg_bwd_dense = 1;             // option bwd_dense: 1 (default) = render5_bwd_kernel, 0 = render3_bwd_kernel (the lock-step walk)
@@ -42,156 +43,44 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                    float* __restrict__ dL_dmean2D, float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolors,
                    double* __restrict__ dL_dv2g_acc)
 {
-    unsigned view, unit;
-    f3dg_xcd_map(blockIdx.x, (unsigned)V, 4u * (unsigned)T, view, unit);
-    const unsigned tile = unit >> 2, quad = unit & 3u;
-    const unsigned tile_x = tile % (unsigned)tiles_x, tile_y = tile / (unsigned)tiles_x;
+    const F3dgQuad qd = f3dg_quad(V, T, tiles_x);
     const unsigned lane = threadIdx.x;
-    const unsigned qx0 = tile_x * F3DG_TILE + (quad & 1u) * 8u, qy0 = tile_y * F3DG_TILE + (quad >> 1) * 8u;
-    const unsigned pix_x = qx0 + (lane & 7u), pix_y = qy0 + (lane >> 3);
-    const bool inside = pix_x < (unsigned)W && pix_y < (unsigned)H;
-    const size_t HW = (size_t)H * W;
-    const size_t pix_id = (size_t)W * pix_y + pix_x;
-    const float pixf_x = (float)pix_x + 0.5f, pixf_y = (float)pix_y + 0.5f;
-    const float ray_x = (float)((pixf_x - W / 2.) / focal_x);
-    const float ray_y = (float)((pixf_y - H / 2.) / focal_y);
-
-    uint2 range = ranges[(size_t)view * T + tile];
-    // no lists to walk after an overflow -- and none that belong to this call when the workspace's last forward kept no auxiliary
-    // planes (an inference call): all gradients stay zero, the header says why
-    // (a one-view forward with auxiliary planes may have taken the small-call path: its lists live in the per-tile slots)
-    const unsigned* __restrict__ point_list = hdr->small_path != 0u ? small_list : point_list_general;
-    if (hdr->overflow || hdr->save_aux == 0u) {
-        range = make_uint2(0, 0);
-        if (!hdr->overflow && blockIdx.x == 0 && threadIdx.x == 0) const_cast<F3dgHeader*>(hdr)->bwd_stale = 1u;
-    }
+    const auto [pix_x, pix_y, inside, pix_id, ray_x, ray_y] = f3dg_quad_pixel(qd, lane, W, H, focal_x, focal_y);
 
     __shared__ float4 sR[4][64];          // records of the window, [16-byte chunk][entry] (global_load_lds image)
     __shared__ float4 sC[64];             // 2D conic (x, y, z) and, over the opacity * coef the record carries as well, the projected centre's x
     __shared__ float sY[64];              // the projected centre's y
-    __shared__ uint2 sQ[128];             // (list position, Gaussian id) of the kept entries, ring
+    __shared__ uint2 sQ[F3DG_QUAD_RING];  // (list position, Gaussian id) of the kept entries, ring
     __shared__ unsigned short sK[128];    // (owning lane << 6) | window slot: the pairs of the batches, entry-major, ring
     __shared__ __attribute__((aligned(16))) float sOut[F3DG_B5_STAGE][20];     // the 17 totals + Gaussian id of up to twelve runs on their way to one-element-per-lane
     __shared__ float4 sS[64];             // per pixel: (T in front of its last blended entry, blended dot behind it, that entry's alpha, its dot)
 
-    const bool alpha_fast = hdr->alpha_fast != 0;
-    const size_t vP = (size_t)view * P;
-    const F3dgRec* vrec = rec + vP;
-    const float4* vcull = cull + vP;
-    const float* fT = final_T + (size_t)view * 4 * HW;
-    const unsigned* nc = n_contrib + (size_t)view * 2 * HW;
-    const float* dpix = dL_dpixels + (size_t)view * F3DG_OUT_CHANNELS * HW;
-    const float* bg = background + (bg_per_view ? 3 * view : 0);
-
-    const float T_final = inside ? fT[pix_id] : 0;
-    const float final_D = inside ? fT[pix_id + HW] : 0;
-    const float final_A = 1 - T_final;
-    const float dL_dreg = inside ? dpix[8 * HW + pix_id] : 0;
-
-    const int last_contributor = inside ? (int)nc[pix_id] : 0;
-    const int max_contributor = inside ? (int)nc[pix_id + HW] : 0;
-    float dpx0 = 0, dpx1 = 0, dpx2 = 0, dn0 = 0, dn1 = 0, dn2 = 0, dL_dmax_depth = 0;
-    if (inside) {
-        dpx0 = dpix[pix_id]; dpx1 = dpix[HW + pix_id]; dpx2 = dpix[2 * HW + pix_id];
-        dn0 = dpix[3 * HW + pix_id]; dn1 = dpix[4 * HW + pix_id]; dn2 = dpix[5 * HW + pix_id];
-        dL_dmax_depth = dpix[6 * HW + pix_id];
-    }
-    const float ddelx_dx = (float)(0.5 * W);
-    const float ddely_dy = (float)(0.5 * H);
-    const float bg_dot_dpixel = bg[0] * dpx0 + bg[1] * dpx1 + bg[2] * dpx2;
-
-    // entries at or behind a pixel's last contributor are skipped by the reference one by one (backward.cu:745-746): the wave starts
-    // at the deepest last contributor of ITS 64 pixels
-    const int wave_last = min((int)__builtin_amdgcn_readfirstlane((int)__reduce_max_sync(~0ull, last_contributor)),
-                              (int)(range.y - range.x));
-    const unsigned qbit = 1u << (F3DG_ID_BITS + quad);
-    const unsigned long long lt = (1ull << lane) - 1ull;
+    F3dgBwdWindow<true> w(sR, sC, nullptr, sY, sQ, qd, inside, pix_id, lane, P, T, W, H, hdr, ranges, point_list_general, small_list, rec, cull,
+                          means2D, conic, background, bg_per_view, final_T, n_contrib, dL_dpixels);
+    const unsigned qx0 = qd.qx0, qy0 = qd.qy0;
     unsigned n_pairs = 0;                 // contributing (pixel, Gaussian) pairs of this wave
 
     // the pixel's running state of backward.cu:745-810, folded: every accumulated colour / normal only ever meets dL/dpixel as a dot product,
     // and dL/dpixel is constant per pixel, so the six recurrences accum_rec[c] / accum_normal[k] are ONE: A <- alpha' u' + (1 - alpha') A with
     // u = c . dL/dC + n . dL/dN of the entry blended last (alpha', u')
-    sS[lane] = make_float4(T_final, 0.0f, 0.0f, 0.0f);
+    sS[lane] = make_float4(w.T_final, 0.0f, 0.0f, 0.0f);
     const unsigned el_run = lane / 20u, el = lane - 20u * el_run;      // lane 20 r + c adds element c of the r-th run of a group of three
-    const float TfBg = T_final * bg_dot_dpixel;
+    const float TfBg = w.T_final * w.bg_dot_dpixel;
     // one 128-byte record per (view, Gaussian) takes all 17 sums of an entry: ten float64 (view2gaussian) at byte 0, seven float32 (colour,
     // mean2D, opacity) at byte 80 -- an atomic event touches ONE line (three 64-byte requests at most) instead of four arrays;
     // preprocess_bwd_kernel hands the float32 ones to the caller's arrays
-    double* const gacc = dL_dv2g_acc + vP * 16;
-    unsigned cursor = (unsigned)wave_last, qhead = 0, qcount = 0;     // list positions [0, cursor) are still to be scanned
-    unsigned idn = lane < cursor ? point_list[range.x + cursor - 1u - lane] : 0u;       // back to front: lane l reads position cursor - 1 - l
-    for (;;) {
-        while (qcount < 64u && cursor != 0u) {
-            const unsigned idm = idn;
-            const bool valid = lane < cursor;
-            const unsigned pos = cursor - 1u - lane;
-            cursor = cursor > 64u ? cursor - 64u : 0u;
-            idn = lane < cursor ? point_list[range.x + cursor - 1u - lane] : 0u;
-            const bool keep = valid && (idm & qbit) != 0u;
-            const unsigned long long kb = __ballot(keep);
-            if (keep) sQ[(qhead + qcount + (unsigned)__popcll(kb & lt)) & 127u] = make_uint2(pos, idm & F3DG_ID_MASK);
-            qcount += (unsigned)__popcll(kb);
-        }
-        if (qcount == 0u)
-            break;
-        const unsigned m = qcount < 64u ? qcount : 64u;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-        float4 e4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        float ec = 0.0f;
-        float2 m2 = make_float2(0.0f, 0.0f);
-        if (lane < m) {
-            const unsigned id = sQ[(qhead + lane) & 127u].y;
-            const float4* src = reinterpret_cast<const float4*>(vrec + id);
-#pragma unroll
-            for (int c = 0; c < 4; c++)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + c),
-                                                 (__attribute__((address_space(3))) void*)&sR[c][0], 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(conic + vP + id),
-                                             (__attribute__((address_space(3))) void*)&sC[0], 16, 0, 0);
-            e4 = vcull[id];
-            m2 = means2D[vP + id];
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane < m) {
-            ec = sR[3][lane].w;
-            sC[lane].w = m2.x;          // (conic.w = opacity * coef is record word 10: sR[2][j].z)
-            sY[lane] = m2.y;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-        // ---- phase 1: lane e tests entry e against the 64 pixels of the quadrant
-        int pass_lo = 0, pass_hi = 0;
-        unsigned long long any = 0ull;
-        {
-            const float u0 = lane < m ? (float)qx0 - e4.x : __builtin_nanf("");
-            const float v0 = (float)qy0 - e4.y;
-            float dxx[8], adx[8], dyy[8], cdy[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                dxx[q] = u0 + (float)q;
-                adx[q] = e4.z * dxx[q];
-                dyy[q] = v0 + (float)q;
-                cdy[q] = ec * dyy[q] * dyy[q];
-            }
-            quad_ballots_any<0>(pass_lo, pass_hi, any, fmaf(dxx[0], fmaf(e4.w, dyy[0], adx[0]), cdy[0]), dxx, adx, dyy, cdy, e4.w);
-        }
-        const unsigned long long pass = ((unsigned long long)(unsigned)pass_hi << 32) | (unsigned)pass_lo;
-
+    double* const gacc = dL_dv2g_acc + w.vP * 16;
+    while (w.next()) {
         // ---- the window's contributing (pixel, entry) pairs, ENTRY-major (back to front: window slot order), 64 to a batch
-        unsigned long long todo = any;
+        unsigned long long todo = w.any;
         unsigned qh = 0u, qt = 0u;                        // wave-uniform ring counters of this window
-        const int slot_pos = (int)sQ[(qhead + lane) & 127u].x;       // lane j: list position of window slot j (read back with v_readlane: no LDS round trip per entry)
+        const int slot_pos = (int)w.entry(lane).x;       // lane j: list position of window slot j (read back with v_readlane: no LDS round trip per entry)
         do {
             while (todo != 0ull && qt - qh < 64u) {
                 const int j = __builtin_ctzll(todo);
                 todo &= todo - 1ull;
                 const int contributor = __builtin_amdgcn_readlane(slot_pos, j);      // 0-based position from the front
-                const bool mine = inside && ((pass >> j) & 1ull) != 0ull && contributor < last_contributor;
+                const bool mine = inside && ((w.pass >> j) & 1ull) != 0ull && contributor < w.last_contributor;
                 const unsigned long long rowmask = __ballot(mine);
                 if (rowmask == 0ull)
                     continue;
@@ -202,9 +91,7 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
             const unsigned nb = qt - qh < 64u ? qt - qh : 64u;
             if (nb == 0u)
                 break;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            f3dg_wave_fence();
 
             // ---- one batch: lane q takes pair q of the ring
             const unsigned kk = (unsigned)sK[(qh + lane) & 127u];
@@ -221,14 +108,14 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
             const int oaddr = (int)(own << 2);
 #define F3DG_B5_PULL(v) __int_as_float(__builtin_amdgcn_ds_bpermute(oaddr, __float_as_int(v)))
             const float p_ray_x = F3DG_B5_PULL(ray_x), p_ray_y = F3DG_B5_PULL(ray_y);
-            const float p_dpx0 = F3DG_B5_PULL(dpx0), p_dpx1 = F3DG_B5_PULL(dpx1), p_dpx2 = F3DG_B5_PULL(dpx2);
-            const float p_dn0 = F3DG_B5_PULL(dn0), p_dn1 = F3DG_B5_PULL(dn1), p_dn2 = F3DG_B5_PULL(dn2);
-            const float p_dmaxd = F3DG_B5_PULL(dL_dmax_depth), p_dreg = F3DG_B5_PULL(dL_dreg);
-            const float p_final_A = F3DG_B5_PULL(final_A), p_final_D = F3DG_B5_PULL(final_D), p_TfBg = F3DG_B5_PULL(TfBg);
-            const int p_maxc = __builtin_amdgcn_ds_bpermute(oaddr, max_contributor);
+            const float p_dpx0 = F3DG_B5_PULL(w.dpx0), p_dpx1 = F3DG_B5_PULL(w.dpx1), p_dpx2 = F3DG_B5_PULL(w.dpx2);
+            const float p_dn0 = F3DG_B5_PULL(w.dn0), p_dn1 = F3DG_B5_PULL(w.dn1), p_dn2 = F3DG_B5_PULL(w.dn2);
+            const float p_dmaxd = F3DG_B5_PULL(w.dL_dmax_depth), p_dreg = F3DG_B5_PULL(w.dL_dreg);
+            const float p_final_A = F3DG_B5_PULL(w.final_A), p_final_D = F3DG_B5_PULL(w.final_D), p_TfBg = F3DG_B5_PULL(TfBg);
+            const int p_maxc = __builtin_amdgcn_ds_bpermute(oaddr, w.max_contributor);
             const float p_pixx = (float)(qx0 + (own & 7u)), p_pixy = (float)(qy0 + (own >> 3));      // the owner's pixel
 #undef F3DG_B5_PULL
-            const uint2 pe = sQ[(qhead + (unsigned)j) & 127u];
+            const uint2 pe = w.entry((unsigned)j);
             const int contributor = (int)pe.x;
 
             const float4 q0 = sR[0][j], q1 = sR[1][j], q2 = sR[2][j];
@@ -241,7 +128,7 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
             float t = 1.0f, G = 0, alpha = 0;
             bool active = valid;
             if (active) {
-                if (alpha_fast) {
+                if (w.alpha_fast) {
                     // the forward of this workspace took the fast arithmetic: the same function, to the bit
                     f3dg_fast_t_G(aaf, bhalf, CC, t, G);
                     if (t < 0.2f) active = false;
@@ -296,9 +183,7 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                         A = st.z * st.w + (1.f - st.z) * st.y;
                         sS[own] = make_float4(Tr, A, alpha, u);
                     }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    f3dg_wave_fence();
                 }
 
                 if (active) {
@@ -329,9 +214,9 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                     const float gdy = G * d_y;
                     const float dG_ddelx = -gdx * con.x - gdy * con.y;
                     const float dG_ddely = -gdy * con.z - gdx * con.y;
-                    g[3] = dL_dG * dG_ddelx * ddelx_dx;
-                    g[4] = dL_dG * dG_ddely * ddely_dy;
-                    g[5] = fabsf(dL_dG * dG_ddelx * ddelx_dx) + fabsf(dL_dG * dG_ddely * ddely_dy);
+                    g[3] = dL_dG * dG_ddelx * w.ddelx_dx;
+                    g[4] = dL_dG * dG_ddely * w.ddely_dy;
+                    g[5] = fabsf(dL_dG * dG_ddelx * w.ddelx_dx) + fabsf(dL_dG * dG_ddely * w.ddely_dy);
                     g[6] = G * dL_dalpha;
 
                     const float dL_dpower = dL_dG * G;
@@ -395,9 +280,7 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                         *reinterpret_cast<float4*>(o + 12) = make_float4(g[12], g[13], g[14], g[15]);
                         *reinterpret_cast<float2*>(o + 16) = make_float2(g[16], __int_as_float((int)pe.y));
                     }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    f3dg_wave_fence();
                     const unsigned staged = nruns - base < (unsigned)F3DG_B5_STAGE ? nruns - base : (unsigned)F3DG_B5_STAGE;
                     for (unsigned r3 = 0u; r3 < staged; r3 += 3u) {       // three runs per pair of atomic instructions, no waiting in between
                         const unsigned rsel = r3 + el_run;
@@ -411,21 +294,13 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                                 unsafeAtomicAdd(rec + (el - 7u), (double)v);
                         }
                     }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the next round overwrites the slots
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    f3dg_wave_fence();     // the next round overwrites the slots
                 }
             }
             qh += nb;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the next compaction overwrites ring slots this batch has read
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            f3dg_wave_fence();     // the next compaction overwrites ring slots this batch has read
         } while (todo != 0ull || qt != qh);
-        qhead += m;
-        qcount -= m;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the window's slots are rewritten by the next one
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        w.retire();
     }
     if (lane == 0 && n_pairs)
         atomicAdd(&hdr->bwd_pairs, (unsigned long long)n_pairs);

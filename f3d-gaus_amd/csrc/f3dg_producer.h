@@ -26,16 +26,10 @@
 #pragma once
 #include "f3dg_common.h"
 #include "f3dg_ellipse.h"
+#include "f3dg_quad.h"
 
 #define F3DG_PROD_RING 256
 #define F3DG_PROD_WIN 64
-
-__device__ __forceinline__ void f3dg_prod_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // LDS accesses the compiler must not see: it cannot tell the buffers of an LDS array apart, so every ds_read / ds_write it schedules
 // while a global_load_lds is outstanding gets an s_waitcnt vmcnt(0) in front (SIInsertWaitcnts) -- which is exactly the wait this
@@ -68,8 +62,7 @@ __device__ __forceinline__ void f3dg_window_producer(unsigned lane, unsigned vie
                                                      unsigned long long (*sPass)[64], uint2* sMH, const unsigned* sStop,
                                                      unsigned stop_full)
 {
-    uint2 range = ranges[(size_t)view * T + tile];
-    if (hdr->overflow) range = make_uint2(0, 0);
+    const uint2 range = f3dg_tile_range(hdr, ranges, view, T, tile);
     const unsigned n = range.y - range.x;
     const F3dgRec* vrec = rec + (size_t)view * P;
     const float4* vcull = cull + (size_t)view * P;
@@ -93,7 +86,7 @@ __device__ __forceinline__ void f3dg_window_producer(unsigned lane, unsigned vie
             if (keep) sQ[(qnext + qcount + (unsigned)__popcll(kb & lt)) & (F3DG_PROD_RING - 1)] = make_uint2(pos, idm & F3DG_ID_MASK);
             qcount += (unsigned)__popcll(kb);
         }
-        f3dg_prod_fence();
+        f3dg_wave_fence();
     };
     // request the records of ring entries [head, head + m) into record buffer rb; returns the lane's cull record (centre, conic a b)
     // and conic c (the last float of the record: a register copy, so that phase 1 reads no LDS)
@@ -128,7 +121,7 @@ __device__ __forceinline__ void f3dg_window_producer(unsigned lane, unsigned vie
         scan(qnext);
         const unsigned m_next = qcount < F3DG_PROD_WIN ? qcount : F3DG_PROD_WIN;
         F3DG_PROD_WAIT_VM0();
-        f3dg_prod_fence();
+        f3dg_wave_fence();
         const unsigned rb_next = rb == 2u ? 0u : rb + 1u;
         e4n = gather(qnext, m_next, rb_next, ecn);        // (buffer of window k - 2: the consumers left it before the last barrier)
         qcount -= m_next;

@@ -22,6 +22,7 @@
 // rounding is innocuous for p = 24, q = 53 >= 2p + 2), so the float64 divide is not needed.
 #include "f3dg_common.h"
 #include "f3dg_ellipse.h"
+#include "f3dg_quad.h"
 
 #include <stdio.h>
 #include <string.h>
@@ -315,17 +316,14 @@ __device__ unsigned long long g_f3dg_counts[64][16];
 // table). An empty asm that "uses" the fourth word keeps the loads 16 bytes wide.
 #define F3DG_FULL16(a, b) asm volatile("" :: "v"((a).w), "v"((b).w))
 
-#define F3DG_R3_WIN 64              // list entries per window = lanes
-#define F3DG_R3_RING 128            // queue ring of (list position, id) pairs
-#define F3DG_R3_FLAG 0x80000000u    // contributor values of the current window are slots (flag | slot) until the window ends
-
 // ---- render3 with a SLIDING window (the default) ----------------------------------------------------------------------------------
 // With fixed 64-entry windows every lane waits at the end of a window for the lane with the most passing entries: the CPU model
 // (tests/tools/wave1_model.py) puts the lane utilisation of phase 2 at 0.54. Here the 64 staged entries are two halves of 32; a slide
 // retires the older half -- which every live pixel has finished -- stages 32 new entries in its place and tests them (lanes e and
 // e + 32 share entry e and split the quadrant's rows: half_ballots), and phase 2 runs until the now-older half is finished by
 // everybody, pixels that are through with it already working on the newer half. Same LDS (4 KB of records), same phase-1 cost per
-// entry; the model gives 0.64 (15 % fewer phase-2 trips). Per pixel the sequence of blended entries is unchanged.
+// entry; the model gives 0.64 (15 % fewer phase-2 trips). Per pixel the sequence of blended entries is unchanged. The scan, the staging,
+// phase 1 and the slide are F3dgHalfWindow (f3dg_quad.h), shared with render4 and render5.
 // One quadrant wave per workgroup, 8 waves per SIMD (every variant fits 64 VGPRs and 5 KB of LDS).
 template <bool SAVE_AUX, bool FAST, bool NORMAL = true, bool DIST = true, bool COUNT = false>
 __global__ void __launch_bounds__(64, 8)
@@ -335,34 +333,16 @@ render3s_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                     const float4* __restrict__ cull, const float* __restrict__ background, int bg_per_view,
                     float* __restrict__ out_color, float* __restrict__ final_T, unsigned* __restrict__ n_contrib)
 {
-    unsigned view, unit;
-    f3dg_xcd_map(blockIdx.x, (unsigned)V, 4u * (unsigned)T, view, unit);
-    const unsigned tile = unit >> 2, quad = unit & 3u;
-    const unsigned tile_x = tile % (unsigned)tiles_x, tile_y = tile / (unsigned)tiles_x;
+    const F3dgQuad qd = f3dg_quad(V, T, tiles_x);
+    const unsigned view = qd.view;
     const unsigned lane = threadIdx.x & 63u;
-    const unsigned qx0 = tile_x * F3DG_TILE + (quad & 1u) * 8u, qy0 = tile_y * F3DG_TILE + (quad >> 1) * 8u;
-    const unsigned pix_x = qx0 + (lane & 7u), pix_y = qy0 + (lane >> 3);
-    const bool inside = pix_x < (unsigned)W && pix_y < (unsigned)H;
+    const auto [pix_x, pix_y, inside, pix_id, ray_x, ray_y] = f3dg_quad_pixel(qd, lane, W, H, focal_x, focal_y);
     const size_t HW = (size_t)H * W;
-    const size_t pix_id = (size_t)W * pix_y + pix_x;
-    const float pixf_x = (float)pix_x + 0.5f, pixf_y = (float)pix_y + 0.5f;
-    const float ray_x = (float)((pixf_x - W / 2.) / focal_x);
-    const float ray_y = (float)((pixf_y - H / 2.) / focal_y);
 
-    uint2 range = ranges[(size_t)view * T + tile];
-    if (hdr->overflow) range = make_uint2(0, 0);
-    const unsigned n = range.y - range.x;
-
-    __shared__ float4 sR[4][F3DG_R3_WIN];     // records, [16-byte chunk][slot]; slots 0..31 and 32..63 are the two halves of the window
-    __shared__ uint2 sQ[F3DG_R3_RING];        // kept (list position, Gaussian id) pairs not staged yet, ring
-    __shared__ unsigned sP[SAVE_AUX ? F3DG_R3_WIN : 1];   // list position of every staged slot (the reference's `contributor`)
-
-    const F3dgRec* vrec = rec + (size_t)view * P;
-    const float4* vcull = cull + (size_t)view * P;
-    const unsigned qbit = 1u << (F3DG_ID_BITS + quad);
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    const unsigned hl = lane & 31u;               // entry of a half this lane tests in phase 1 ...
-    const unsigned row4 = (lane >> 5) * 4u;       // ... against the pixels of rows row4 .. row4 + 3
+    __shared__ float4 sR[4][64];                              // records, [16-byte chunk][slot]; slots 0..31 and 32..63 are the two halves of the window
+    __shared__ unsigned sQ[F3DG_QUAD_RING];                   // ids of kept entries not staged yet, ring
+    __shared__ unsigned sQpos[SAVE_AUX ? F3DG_QUAD_RING : 1]; // ... and their positions in the tile's list
+    __shared__ unsigned sP[SAVE_AUX ? 64 : 1];                // list position of every staged slot (the reference's `contributor`)
 
     bool done = !inside;
     PixelState st;
@@ -371,95 +351,25 @@ render3s_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
     st.C0 = st.C1 = st.C2 = st.C3 = st.C4 = st.C5 = st.C6 = st.C7 = 0;
     st.dist1 = st.dist2 = st.distortion = 0;
 
-    auto translate = [&](unsigned half_or_all) {      // slots -> 1-based list positions for the slots of one physical half (2: both)
-        if (SAVE_AUX) {
-            const unsigned a = st.last_contributor - F3DG_R3_FLAG, b = st.max_contributor - F3DG_R3_FLAG;
-            if (a < (unsigned)F3DG_R3_WIN && (half_or_all == 2u || (a >> 5) == half_or_all)) st.last_contributor = sP[a] + 1u;
-            if (b < (unsigned)F3DG_R3_WIN && (half_or_all == 2u || (b >> 5) == half_or_all)) st.max_contributor = sP[b] + 1u;
-        }
-    };
-
     unsigned n_useful = 0;
     unsigned n_half_sep = 0, n_half_pair = 0;
     unsigned n_staged = 0, n_trips = 0, n_wave_trips = 0, n_slides = 0, n_t8 = 0, n_t24 = 0, n_s8 = 0, n_s24 = 0;    // COUNT (option render_count): what this wave did, summed into g_f3dg_counts at its end
-    unsigned cursor = 0, qhead = 0, qpend = 0;    // wave-uniform: scan position, ring index of the first pending entry, pending entries
-    unsigned flip = 0;                            // physical half (slots 32 flip ..) that holds the OLDER half of the window
-    unsigned long long pass = 0ull;               // per pixel: bits 0..31 older half, 32..63 newer half, in list order
-    unsigned idn = lane < n ? point_list[range.x + lane] : 0u;
+    F3dgHalfWindow<SAVE_AUX> win(sR, sQ, sQpos, sP, qd, lane, P, T, hdr, ranges, point_list, rec, cull);
+    unsigned long long& pass = win.pass;
     if (__ballot(!done) != 0ull)
     for (;;) {
-        // ---- scan: keep the entries whose box reaches this quadrant until 32 are pending
-        while (qpend < 32u && cursor < n) {
-            const unsigned idm = idn, pos = cursor + lane;
-            cursor += 64u;
-            idn = cursor + lane < n ? point_list[range.x + cursor + lane] : 0u;
-            const bool keep = pos < n && (idm & qbit) != 0u;
-            const unsigned long long kb = __ballot(keep);
-            if (keep) sQ[(qhead + qpend + (unsigned)__popcll(kb & lt)) & (F3DG_R3_RING - 1)] = make_uint2(pos, idm & F3DG_ID_MASK);
-            qpend += (unsigned)__popcll(kb);
-        }
-        const unsigned m = qpend < 32u ? qpend : 32u;
-        // every live pixel has finished the older half (bits 0..31 of `pass` are clear): retire it
-        translate(flip);
-        if (m == 0u && __ballot(pass != 0ull) == 0ull)
+        win.translate(win.flip, st.last_contributor, st.max_contributor);     // the older half retires
+        if (!win.slide(done))
             break;                                // nothing left to stage, nothing left in the newer half
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-        // ---- stage m entries into the retired half; lanes e and e + 32 both take entry e
-        const unsigned base = flip * 32u;
-        float4 e4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        float ec = 0.0f;
-        if (hl < m) {
-            const uint2 q = sQ[(qhead + hl) & (F3DG_R3_RING - 1)];
-            if (lane < 32u) {
-                const float4* src = reinterpret_cast<const float4*>(vrec + q.y);
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + c),
-                                                     (__attribute__((address_space(3))) void*)&sR[c][base], 16, 0, 0);
-                if (SAVE_AUX) sP[base + lane] = q.x;
-            }
-            e4 = vcull[q.y];
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (hl < m) ec = sR[3][base + hl].w;
-        qhead += m;
-        qpend -= m;
-        if (COUNT) { n_staged += m; n_slides++; }
-
-        // ---- phase 1: the 32 new entries against the quadrant's 64 pixels
-        int fresh = 0;
-        if (m != 0u) {
-            const float u0 = hl < m ? (float)qx0 - e4.x : __builtin_nanf("");     // NaN: every comparison below is false
-            const float v0 = (float)(qy0 + row4) - e4.y;
-            float dxx[8], adx[8], dyy[4], cdy[4];
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                dxx[q] = u0 + (float)q;
-                adx[q] = e4.z * dxx[q];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                dyy[q] = v0 + (float)q;
-                cdy[q] = ec * dyy[q] * dyy[q];
-            }
-            half_ballots<0>(fresh, fmaf(dxx[0], fmaf(e4.w, dyy[0], adx[0]), cdy[0]), dxx, adx, dyy, cdy, e4.w);
-        }
         if (COUNT) {        // staged entries that reach at least one pixel that is still alive (the others were gathered for nothing)
-            unsigned u = done ? 0u : (unsigned)fresh;
+            n_staged += win.m;
+            n_slides++;
+            unsigned u = done ? 0u : (unsigned)win.fresh;
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) u |= (unsigned)__shfl_xor((int)u, o, 64);
             n_useful += (unsigned)__popc(u);
         }
-        // ---- slide: the newer half becomes the older one, the fresh bits the newer one
-        pass = (pass >> 32) | (done ? 0ull : ((unsigned long long)(unsigned)fresh << 32));
-        flip ^= 1u;
-        const unsigned xr = flip << 5;            // logical slot j (0..31 older, 32..63 newer) lives in physical slot j ^ xr
+        const unsigned xr = win.xr;
 
         // ---- phase 2: until every live pixel has finished the older half; pixels that have go on with the newer one
         // (a divergent loop: a pixel leaves it when its mask is empty -- it has nothing left in either half -- and the ballot, taken
@@ -477,7 +387,7 @@ render3s_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
             const float n2 = q0.z * ray_x + q1.x * ray_y + q1.y;
             const float aaf = ray_x * n0 + ray_y * n1 + n2;
             const float bhalf = q1.z * ray_x + q1.w * ray_y + q2.x;
-            done = (FAST ? blend_entry_fast<NORMAL, DIST> : blend_entry<NORMAL, DIST>)(st, F3DG_R3_FLAG | j, n0, n1, n2, aaf, bhalf, q2.y, q2.z, q3.x, q3.y, q3.z);
+            done = (FAST ? blend_entry_fast<NORMAL, DIST> : blend_entry<NORMAL, DIST>)(st, F3DG_SLOT_FLAG | j, n0, n1, n2, aaf, bhalf, q2.y, q2.z, q3.x, q3.y, q3.z);
             if (done) pass = 0ull;
         }
         if (COUNT) {                // the loop ran as often as its busiest lane needed (lanes leave it, none re-enters)
@@ -504,14 +414,14 @@ render3s_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
         if (live == 0ull)
             break;
     }
-    translate(2u);
+    win.translate(2u, st.last_contributor, st.max_contributor);
     if (COUNT && lane == 0) {
         unsigned long long* c = g_f3dg_counts[blockIdx.x & 63u];
         atomicAdd(&c[13], (unsigned long long)n_useful);
         atomicAdd(&c[14], (unsigned long long)n_half_sep);
         atomicAdd(&c[15], (unsigned long long)n_half_pair);
         atomicAdd(&c[0], (unsigned long long)n_staged);
-        atomicAdd(&c[1], (unsigned long long)(cursor < n ? cursor : n));
+        atomicAdd(&c[1], (unsigned long long)(win.cursor < win.n ? win.cursor : win.n));
         atomicAdd(&c[2], (unsigned long long)n_wave_trips);
         atomicAdd(&c[3], (unsigned long long)n_slides);
         atomicAdd(&c[5], 1ull);

@@ -9,7 +9,8 @@
 //
 // Two thirds of a trip do not depend on the pixel's running state (f3dg_blend.h: f3dg_pair_eval -- quadric, error-free quotient, exp,
 // NDC depth, unit normal); only the last third (f3dg_pair_apply: the transmittance recurrence and the accumulators) is serial per
-// pixel. This kernel keeps render3s's scan / staging / phase 1 / sliding half-windows and splits phase 2 of a slide in two regimes:
+// pixel. This kernel shares render3s's scan / staging / phase 1 / sliding half-windows (F3dgHalfWindow, f3dg_quad.h) and splits phase 2
+// of a slide in two regimes:
 //   * FUSED trips, as before, while more than `pack_th` pixels take part;
 //   * then PACKED batches. A batch takes the next R pending entries of every pixel (R ranks: as many as fit 64 pairs, at most what the
 //     pixels that hold the window back still need), writes the (pixel, slot) pairs to a 64-entry LDS queue in pixel-major order
@@ -26,6 +27,7 @@
 #include "f3dg_blend.h"
 #include "f3dg_ellipse.h"
 #include "f3dg_producer.h"
+#include "f3dg_quad.h"
 
 #include <stdio.h>
 #include <string.h>
@@ -41,26 +43,12 @@ __device__ unsigned long long g_f3dg_counts4[64][16];
 namespace {
 
 #define F3DG_R4_WIN 64
-#define F3DG_R4_RING 128
 #define F3DG_R4_MAXR 10             // ranks per packed batch (two 32-bit registers of 6-bit slots)
-#define F3DG_R4_FLAG 0x80000000u
-
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // keeps the pixel state in ONE set of registers across the packed batches (without it the register allocator parks the twelve
 // accumulators in a second set around the dense trip: 24 v_mov per batch)
 #define F3DG_R4_PIN(st) asm volatile("" : "+v"((st).Tr), "+v"((st).C0), "+v"((st).C1), "+v"((st).C2), "+v"((st).C3), "+v"((st).C4), "+v"((st).C5), \
                                           "+v"((st).C6), "+v"((st).C7), "+v"((st).dist1), "+v"((st).dist2), "+v"((st).distortion))
-
-__device__ __forceinline__ float pull(int addr, float v)
-{
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v)));
-}
 
 // SAVE_AUX (a forward that f3dg_backward follows): also final_T [V][4][HW] and n_contrib [V][2][HW]; last_contributor / max_contributor are
 // 1-based positions in the tile's list, kept per staged slot (sP) and translated when a half of the window retires, as in render3s.
@@ -73,25 +61,14 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                    const float4* __restrict__ cull, const float* __restrict__ background, int bg_per_view,
                    float* __restrict__ out_color, int pack_th, float* __restrict__ final_T, unsigned* __restrict__ n_contrib)
 {
-    unsigned view, unit;
-    f3dg_xcd_map(blockIdx.x, (unsigned)V, 4u * (unsigned)T, view, unit);
-    const unsigned tile = unit >> 2, quad = unit & 3u;
-    const unsigned tile_x = tile % (unsigned)tiles_x, tile_y = tile / (unsigned)tiles_x;
+    const F3dgQuad qd = f3dg_quad(V, T, tiles_x);
+    const unsigned view = qd.view, qx0 = qd.qx0, qy0 = qd.qy0;
     const unsigned lane = threadIdx.x;
-    const unsigned qx0 = tile_x * F3DG_TILE + (quad & 1u) * 8u, qy0 = tile_y * F3DG_TILE + (quad >> 1) * 8u;
-    const unsigned pix_x = qx0 + (lane & 7u), pix_y = qy0 + (lane >> 3);
-    const bool inside = pix_x < (unsigned)W && pix_y < (unsigned)H;
-    const float pixf_x = (float)pix_x + 0.5f, pixf_y = (float)pix_y + 0.5f;
-    const float ray_x = (float)((pixf_x - W / 2.) / focal_x);
-    const float ray_y = (float)((pixf_y - H / 2.) / focal_y);
-
-    uint2 range = ranges[(size_t)view * T + tile];
-    if (hdr->overflow) range = make_uint2(0, 0);
-    const unsigned n = range.y - range.x;
+    const auto [pix_x, pix_y, inside, pix_id, ray_x, ray_y] = f3dg_quad_pixel(qd, lane, W, H, focal_x, focal_y);
 
     __shared__ float4 sR[4][F3DG_R4_WIN];          // records, [16-byte chunk][slot]; slots 0..31 and 32..63 are the two halves of the window
-    __shared__ unsigned sQ[F3DG_R4_RING];          // ids of kept entries not staged yet, ring
-    __shared__ unsigned sQpos[SAVE_AUX ? F3DG_R4_RING : 1];     // ... and their positions in the tile's list
+    __shared__ unsigned sQ[F3DG_QUAD_RING];        // ids of kept entries not staged yet, ring
+    __shared__ unsigned sQpos[SAVE_AUX ? F3DG_QUAD_RING : 1];   // ... and their positions in the tile's list
     __shared__ unsigned sP[SAVE_AUX ? F3DG_R4_WIN : 1];         // list position of every staged slot (the reference's `contributor`)
     // the parking area of a packed batch: what the dense trip hands to the blend trips, [position in the queue]. The queue itself
     // (sK: 64 x u16, (owning lane << 6) | physical slot) is read by the dense trip before it parks its results and aliases the first
@@ -101,96 +78,20 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
     __shared__ float2 sPark2[(NORMAL || DIST) ? 64 : 1];       // full: (nn1, nn2)
     unsigned short* sK = reinterpret_cast<unsigned short*>(sPark);
 
-    const F3dgRec* vrec = rec + (size_t)view * P;
-    const float4* vcull = cull + (size_t)view * P;
-    const unsigned qbit = 1u << (F3DG_ID_BITS + quad);
-    const unsigned hl = lane & 31u;               // entry of a half this lane tests in phase 1 ...
-    const unsigned row4 = (lane >> 5) * 4u;       // ... against the pixels of rows row4 .. row4 + 3
-
     bool done = !inside;
     F3dgPixel st;
     f3dg_pixel_init(st);
 
-    auto translate = [&](unsigned half_or_all) {      // slots -> 1-based list positions for the slots of one physical half (2: both)
-        if (SAVE_AUX) {
-            const unsigned a = st.last_contributor - F3DG_R4_FLAG, b = st.max_contributor - F3DG_R4_FLAG;
-            if (a < (unsigned)F3DG_R4_WIN && (half_or_all == 2u || (a >> 5) == half_or_all)) st.last_contributor = sP[a] + 1u;
-            if (b < (unsigned)F3DG_R4_WIN && (half_or_all == 2u || (b >> 5) == half_or_all)) st.max_contributor = sP[b] + 1u;
-        }
-    };
     unsigned n_staged = 0, n_fused = 0, n_slides = 0, n_lane_fused = 0, n_batches = 0, n_blend_trips = 0, n_dense_pairs = 0, n_blend_pairs = 0;
-    unsigned cursor = 0, qhead = 0, qpend = 0;    // wave-uniform: scan position, ring index of the first pending entry, pending entries
-    unsigned flip = 0;                            // physical half (slots 32 flip ..) that holds the OLDER half of the window
-    unsigned long long pass = 0ull;               // per pixel: bits 0..31 older half, 32..63 newer half, in list order
-    unsigned idn = lane < n ? point_list[range.x + lane] : 0u;
+    F3dgHalfWindow<SAVE_AUX> win(sR, sQ, sQpos, sP, qd, lane, P, T, hdr, ranges, point_list, rec, cull);
+    unsigned long long& pass = win.pass;
     if (__ballot(!done) != 0ull)
     for (;;) {
-        // ---- scan: keep the entries whose box reaches this quadrant until 32 are pending
-        while (qpend < 32u && cursor < n) {
-            const unsigned idm = idn, pos = cursor + lane;
-            cursor += 64u;
-            idn = cursor + lane < n ? point_list[range.x + cursor + lane] : 0u;
-            const bool keep = pos < n && (idm & qbit) != 0u;
-            const unsigned long long kb = __ballot(keep);
-            if (keep) {
-                const unsigned slot = (qhead + qpend + __builtin_amdgcn_mbcnt_hi((unsigned)(kb >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)kb, 0u))) & (F3DG_R4_RING - 1);
-                sQ[slot] = idm & F3DG_ID_MASK;
-                if (SAVE_AUX) sQpos[slot] = pos;
-            }
-            qpend += (unsigned)__popcll(kb);
-        }
-        const unsigned m = qpend < 32u ? qpend : 32u;
-        // every live pixel has finished the older half (bits 0..31 of `pass` are clear): retire it
-        translate(flip);
-        if (m == 0u && __ballot(pass != 0ull) == 0ull)
+        win.translate(win.flip, st.last_contributor, st.max_contributor);     // the older half retires
+        if (!win.slide(done))
             break;                                // nothing left to stage, nothing left in the newer half
-        wave_lds_fence();
-
-        // ---- stage m entries into the retired half; lanes e and e + 32 both take entry e
-        const unsigned base = flip * 32u;
-        float4 e4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        float ec = 0.0f;
-        if (hl < m) {
-            const unsigned id = sQ[(qhead + hl) & (F3DG_R4_RING - 1)];
-            if (lane < 32u) {
-                const float4* src = reinterpret_cast<const float4*>(vrec + id);
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + c),
-                                                     (__attribute__((address_space(3))) void*)&sR[c][base], 16, 0, 0);
-                if (SAVE_AUX) sP[base + lane] = sQpos[(qhead + hl) & (F3DG_R4_RING - 1)];
-            }
-            e4 = vcull[id];
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        wave_lds_fence();
-        if (hl < m) ec = sR[3][base + hl].w;
-        qhead += m;
-        qpend -= m;
-        if (COUNT) { n_staged += m; n_slides++; }
-
-        // ---- phase 1: the 32 new entries against the quadrant's 64 pixels
-        int fresh = 0;
-        if (m != 0u) {
-            const float u0 = hl < m ? (float)qx0 - e4.x : __builtin_nanf("");     // NaN: every comparison below is false
-            const float v0 = (float)(qy0 + row4) - e4.y;
-            float dxx[8], adx[8], dyy[4], cdy[4];
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                dxx[q] = u0 + (float)q;
-                adx[q] = e4.z * dxx[q];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                dyy[q] = v0 + (float)q;
-                cdy[q] = ec * dyy[q] * dyy[q];
-            }
-            half_ballots<0>(fresh, fmaf(dxx[0], fmaf(e4.w, dyy[0], adx[0]), cdy[0]), dxx, adx, dyy, cdy, e4.w);
-        }
-        // ---- slide: the newer half becomes the older one, the fresh bits the newer one
-        pass = (pass >> 32) | (done ? 0ull : ((unsigned long long)(unsigned)fresh << 32));
-        flip ^= 1u;
-        const unsigned xr = flip << 5;            // logical slot j (0..31 older, 32..63 newer) lives in physical slot j ^ xr
+        if (COUNT) { n_staged += win.m; n_slides++; }
+        const unsigned xr = win.xr;
 
         // ---- phase 2a: fused trips while many pixels take part (a divergent loop: a pixel leaves it when its mask is empty; the
         // ballots are taken over the pixels still inside)
@@ -204,7 +105,7 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
             // arithmetic on the first chunks starts while the last ones are still on their way
             asm volatile("" :: "v"(q2.w), "v"(q3.w), "v"(pr.alpha));
             if (pr.alpha != 0.0f)
-                done = f3dg_pair_apply<FAST, NORMAL, DIST>(st, F3DG_R4_FLAG | j, pr, q3.x, q3.y, q3.z);
+                done = f3dg_pair_apply<FAST, NORMAL, DIST>(st, F3DG_SLOT_FLAG | j, pr, q3.x, q3.y, q3.z);
             if (done) pass = 0ull;
             if (COUNT && __builtin_ctzll(__ballot(true)) == (int)lane) n_fused++;
         }
@@ -239,14 +140,14 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                     }
                 } while (++i < R);
             }
-            wave_lds_fence();
+            f3dg_wave_fence();
 
             // dense trip: lane q evaluates pair q of the queue (lanes beyond `total` evaluate a stale pair nobody pulls)
             F3dgPair pr;
             {
                 const unsigned k = (unsigned)sK[lane];
                 const int owner = (int)((k >> 6) << 2);
-                const float rx = pull(owner, ray_x), ry = pull(owner, ray_y);
+                const float rx = f3dg_pull(owner, ray_x), ry = f3dg_pull(owner, ray_y);
                 const unsigned j = k & 63u;
                 const float4 q0 = sR[0][j], q1 = sR[1][j], q2 = sR[2][j];
                 pr = f3dg_pair_eval<FAST, NORMAL, DIST, true>(rx, ry, q0, q1, q2);
@@ -256,14 +157,14 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
 
             // park the results (every lane has read its queue entry: the queue's bytes may go), then the blend trips: a divergent loop,
             // every owning lane walks ITS pairs of the batch through the recurrence, the wave runs as long as the longest of them
-            wave_lds_fence();
+            f3dg_wave_fence();
             if (NORMAL || DIST) {
                 sPark[lane] = make_float4(pr.alpha, pr.t, pr.m, pr.nn0);
                 sPark2[lane] = make_float2(pr.nn1, pr.nn2);
             } else {
                 reinterpret_cast<float2*>(sPark)[lane] = make_float2(pr.alpha, pr.t);
             }
-            wave_lds_fence();
+            f3dg_wave_fence();
             {
                 unsigned i = 0;
                 while (i < c && !done) {
@@ -281,22 +182,22 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                     }
                     if (COUNT) n_blend_pairs++;
                     if (FAST)
-                        done = f3dg_pair_apply_flat<NORMAL, DIST>(st, F3DG_R4_FLAG | j, mine, q3.x, q3.y, q3.z);
+                        done = f3dg_pair_apply_flat<NORMAL, DIST>(st, F3DG_SLOT_FLAG | j, mine, q3.x, q3.y, q3.z);
                     else
                     if (mine.alpha != 0.0f)
-                        done = f3dg_pair_apply<FAST, NORMAL, DIST>(st, F3DG_R4_FLAG | j, mine, q3.x, q3.y, q3.z);
+                        done = f3dg_pair_apply<FAST, NORMAL, DIST>(st, F3DG_SLOT_FLAG | j, mine, q3.x, q3.y, q3.z);
                     asm volatile("" :: "v"(q3.w));
                     i++;
                 }
             }
-            wave_lds_fence();          // the next batch's queue overwrites the parking area
+            f3dg_wave_fence();          // the next batch's queue overwrites the parking area
             if (done) pass = 0ull;
         } while (__ballot((unsigned)pass != 0u) != 0ull);
 
         if (__ballot(!done) == 0ull)
             break;
     }
-    translate(2u);
+    win.translate(2u, st.last_contributor, st.max_contributor);
     if (COUNT) {
         unsigned a = n_lane_fused, b = n_blend_pairs;
 #pragma unroll
@@ -310,7 +211,7 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
         if (lane == 0) {
             unsigned long long* c = g_f3dg_counts4[blockIdx.x & 63u];
             atomicAdd(&c[0], (unsigned long long)n_staged);
-            atomicAdd(&c[1], (unsigned long long)(cursor < n ? cursor : n));
+            atomicAdd(&c[1], (unsigned long long)(win.cursor < win.n ? win.cursor : win.n));
             atomicAdd(&c[2], (unsigned long long)f);
             atomicAdd(&c[3], (unsigned long long)n_slides);
             atomicAdd(&c[4], (unsigned long long)a);
@@ -381,13 +282,10 @@ render3p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                     const float4* __restrict__ cull, const float* __restrict__ background, int bg_per_view,
                     float* __restrict__ out_color, float* __restrict__ final_T, unsigned* __restrict__ n_contrib)
 {
-    unsigned view, unit;
-    f3dg_xcd_map(blockIdx.x, (unsigned)V, 4u * (unsigned)T, view, unit);
-    const unsigned tile = unit >> 2, quad = unit & 3u;
-    const unsigned tile_x = tile % (unsigned)tiles_x, tile_y = tile / (unsigned)tiles_x;
+    const F3dgQuad qd = f3dg_quad(V, T, tiles_x);
+    const auto [view, tile, quad, qx0, qy0] = qd;
     const unsigned lane = threadIdx.x & 63u;
     const bool producer = threadIdx.x >= 64u;             // (wave-uniform)
-    const unsigned qx0 = tile_x * F3DG_TILE + (quad & 1u) * 8u, qy0 = tile_y * F3DG_TILE + (quad >> 1) * 8u;
 
     __shared__ float4 sR[3][4][F3DG_PROD_WIN];            // three windows of records, [window % 3][16-byte chunk][entry]
     __shared__ uint2 sQ[F3DG_PROD_RING];                  // (list position, Gaussian id) of the kept entries (the producer's ring)
@@ -404,13 +302,8 @@ render3p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
     }
 
     // ==================================================== wave 0: the pixels, phase 2 ====================================================
-    const unsigned pix_x = qx0 + (lane & 7u), pix_y = qy0 + (lane >> 3);
-    const bool inside = pix_x < (unsigned)W && pix_y < (unsigned)H;
+    const auto [pix_x, pix_y, inside, pix_id, ray_x, ray_y] = f3dg_quad_pixel(qd, lane, W, H, focal_x, focal_y);
     const size_t HW = (size_t)H * W;
-    const size_t pix_id = (size_t)W * pix_y + pix_x;
-    const float pixf_x = (float)pix_x + 0.5f, pixf_y = (float)pix_y + 0.5f;
-    const float ray_x = (float)((pixf_x - W / 2.) / focal_x);
-    const float ray_y = (float)((pixf_y - H / 2.) / focal_y);
     bool done = !inside;
     F3dgPixel st;
     f3dg_pixel_init(st);
@@ -445,18 +338,18 @@ render3p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                     if (FAST) {
                         F3dgPair p = pr[u];
                         p.alpha = done ? 0.0f : p.alpha;
-                        done |= f3dg_pair_apply_flat<true, true>(st, F3DG_R4_FLAG | (unsigned)j[u], p, cr[u], cg[u], cb[u]);
+                        done |= f3dg_pair_apply_flat<true, true>(st, F3DG_SLOT_FLAG | (unsigned)j[u], p, cr[u], cg[u], cb[u]);
                     } else if (!done && pr[u].alpha != 0.0f) {
-                        done = f3dg_pair_apply<false, true, true>(st, F3DG_R4_FLAG | (unsigned)j[u], pr[u], cr[u], cg[u], cb[u]);
+                        done = f3dg_pair_apply<false, true, true>(st, F3DG_SLOT_FLAG | (unsigned)j[u], pr[u], cr[u], cg[u], cb[u]);
                     }
                 }
             }
             if (SAVE_AUX) {             // slots -> 1-based list positions (the reference's `contributor`)
                 const unsigned head = sMH[buf].y;
-                if (st.last_contributor - F3DG_R4_FLAG < (unsigned)F3DG_R4_WIN)
-                    st.last_contributor = sQ[(head + (st.last_contributor - F3DG_R4_FLAG)) & (F3DG_PROD_RING - 1)].x + 1u;
-                if (st.max_contributor - F3DG_R4_FLAG < (unsigned)F3DG_R4_WIN)
-                    st.max_contributor = sQ[(head + (st.max_contributor - F3DG_R4_FLAG)) & (F3DG_PROD_RING - 1)].x + 1u;
+                if (st.last_contributor - F3DG_SLOT_FLAG < (unsigned)F3DG_R4_WIN)
+                    st.last_contributor = sQ[(head + (st.last_contributor - F3DG_SLOT_FLAG)) & (F3DG_PROD_RING - 1)].x + 1u;
+                if (st.max_contributor - F3DG_SLOT_FLAG < (unsigned)F3DG_R4_WIN)
+                    st.max_contributor = sQ[(head + (st.max_contributor - F3DG_SLOT_FLAG)) & (F3DG_PROD_RING - 1)].x + 1u;
             }
             if (__ballot(!done) == 0ull && lane == 0) sStop[buf] = 1u;  // (read by both waves after the next barrier)
             buf ^= 1u;
@@ -535,10 +428,8 @@ render3q_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                     const float4* __restrict__ cull, const float* __restrict__ background, int bg_per_view,
                     float* __restrict__ out_color, float* __restrict__ final_T, unsigned* __restrict__ n_contrib, int prof)
 {
-    unsigned view, unit;
-    f3dg_xcd_map(blockIdx.x, (unsigned)V, 4u * (unsigned)T, view, unit);
-    const unsigned tile = unit >> 2, quad = unit & 3u;
-    const unsigned tile_x = tile % (unsigned)tiles_x, tile_y = tile / (unsigned)tiles_x;
+    const F3dgQuad qd = f3dg_quad(V, T, tiles_x);
+    const auto [view, tile, quad, qx0, qy0] = qd;
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // option render_count: shader clocks of every role (f3dg_debug_render3q_clocks) -- g_f3dg_counts4 rows 32 + role: [0] total, [1] waiting
@@ -551,7 +442,6 @@ render3q_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
         atomicAdd(&g_f3dg_counts4[32 + (role)][0], tt_); atomicAdd(&g_f3dg_counts4[32 + (role)][1], t_win); atomicAdd(&g_f3dg_counts4[32 + (role)][2], t_spin); \
         atomicAdd(&g_f3dg_counts4[32 + (role)][3], n_win); atomicAdd(&g_f3dg_counts4[32 + (role)][4], n_rounds); atomicAdd(&g_f3dg_counts4[32 + (role)][5], 1ull); \
         atomicMax(&g_f3dg_counts4[40][role], tt_); } } while (0)
-    const unsigned qx0 = tile_x * F3DG_TILE + (quad & 1u) * 8u, qy0 = tile_y * F3DG_TILE + (quad >> 1) * 8u;
 
     constexpr int K = E == 2 ? 4 : 2;                     // rounds of parking (power of two): 20 KB (E = 2) / 15 KB (E = 3); four workgroups share a CU's 160 KB
     __shared__ float4 sR[2][4][F3DG_R4_WIN];              // two windows of records, [window][16-byte chunk][entry]
@@ -570,8 +460,7 @@ render3q_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
 
     if (wave == (unsigned)E + 1u) {
         // ================================================ the producer: scan, gather, phase 1 ================================================
-        uint2 range = ranges[(size_t)view * T + tile];
-        if (hdr->overflow) range = make_uint2(0, 0);
+        const uint2 range = f3dg_tile_range(hdr, ranges, view, T, tile);
         const unsigned n = range.y - range.x;
         const F3dgRec* vrec = rec + (size_t)view * P;
         const float4* vcull = cull + (size_t)view * P;
@@ -594,7 +483,7 @@ render3q_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                 if (keep) sQ[(qhead + qcount + (unsigned)__popcll(kb & lt)) & (F3DG_R3U_RING - 1)] = make_uint2(pos, idm & F3DG_ID_MASK);
                 qcount += (unsigned)__popcll(kb);
             }
-            wave_lds_fence();
+            f3dg_wave_fence();
             const unsigned m = qcount < F3DG_R4_WIN ? qcount : F3DG_R4_WIN;
             // buffer `buf` held window w - 2: every reader of its records, pass masks and ring slots must have finished it
             if (w >= 2u) {
@@ -616,7 +505,7 @@ render3q_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                 e4 = vcull[id];
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            wave_lds_fence();
+            f3dg_wave_fence();
             unsigned rounds = 0;
             if (m != 0u) {
                 const float ec = lane < m ? sR[buf][3][lane].w : 0.0f;
@@ -637,7 +526,7 @@ render3q_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                 rounds = (most + (unsigned)E - 1u) / (unsigned)E;
             }
             if (lane == 0) { sM[buf] = m; sHead[buf] = qhead; sRounds[buf] = rounds; }
-            wave_lds_fence();
+            f3dg_wave_fence();
             if (lane == 0) __hip_atomic_store(&sProd, w + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             if (m == 0u)
                 break;
@@ -649,10 +538,7 @@ render3q_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
         return;
     }
 
-    const unsigned pix_x = qx0 + (lane & 7u), pix_y = qy0 + (lane >> 3);
-    const float pixf_x = (float)pix_x + 0.5f, pixf_y = (float)pix_y + 0.5f;
-    const float ray_x = (float)((pixf_x - W / 2.) / focal_x);
-    const float ray_y = (float)((pixf_y - H / 2.) / focal_y);
+    const auto [pix_x, pix_y, inside, pix_id, ray_x, ray_y] = f3dg_quad_pixel(qd, lane, W, H, focal_x, focal_y);
 
     if (wave != 0u) {
         // ================================================ evaluator e: the stateless part of rank r E + e ================================================
@@ -688,7 +574,7 @@ render3q_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                 pk.a[lane] = make_float4(pr.alpha, pr.t, pr.m, pr.nn0);
                 pk.b[lane] = make_float4(pr.nn1, pr.nn2, q3.x, q3.y);
                 pk.c[lane] = make_float2(q3.z, __uint_as_float((unsigned)j));
-                wave_lds_fence();
+                f3dg_wave_fence();
                 if (lane == 0) __hip_atomic_store(&sEvalDone[e], rr + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
             if (!go) break;
@@ -699,9 +585,7 @@ render3q_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
     }
 
     // ==================================================== the consumer: the pixels' recurrence ====================================================
-    const bool inside = pix_x < (unsigned)W && pix_y < (unsigned)H;
     const size_t HW = (size_t)H * W;
-    const size_t pix_id = (size_t)W * pix_y + pix_x;
     bool done = !inside;
     F3dgPixel st;
     f3dg_pixel_init(st);
@@ -726,7 +610,7 @@ render3q_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                     const float2 c = pk.c[lane];
                     F3dgPair p;
                     p.alpha = a.x; p.t = a.y; p.m = a.z; p.nn0 = a.w; p.nn1 = b.x; p.nn2 = b.y;
-                    const unsigned contributor = F3DG_R4_FLAG | __float_as_uint(c.y);
+                    const unsigned contributor = F3DG_SLOT_FLAG | __float_as_uint(c.y);
                     if (FAST) {
                         p.alpha = done ? 0.0f : p.alpha;
                         done |= f3dg_pair_apply_flat<true, true>(st, contributor, p, b.z, b.w, c.x);
@@ -734,7 +618,7 @@ render3q_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                         done = f3dg_pair_apply<false, true, true>(st, contributor, p, b.z, b.w, c.x);
                     }
                 }
-                wave_lds_fence();
+                f3dg_wave_fence();
                 if (lane == 0) __hip_atomic_store(&sConsumed, rr + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 if (__ballot(!done) == 0ull) {                 // nobody needs the rest of the list
                     stop = true;
@@ -743,12 +627,12 @@ render3q_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
             }
             if (SAVE_AUX) {             // slots -> 1-based list positions (the reference's `contributor`)
                 const unsigned head = sHead[buf];
-                if (st.last_contributor - F3DG_R4_FLAG < (unsigned)F3DG_R4_WIN)
-                    st.last_contributor = sQ[(head + (st.last_contributor - F3DG_R4_FLAG)) & (F3DG_R3U_RING - 1)].x + 1u;
-                if (st.max_contributor - F3DG_R4_FLAG < (unsigned)F3DG_R4_WIN)
-                    st.max_contributor = sQ[(head + (st.max_contributor - F3DG_R4_FLAG)) & (F3DG_R3U_RING - 1)].x + 1u;
+                if (st.last_contributor - F3DG_SLOT_FLAG < (unsigned)F3DG_R4_WIN)
+                    st.last_contributor = sQ[(head + (st.last_contributor - F3DG_SLOT_FLAG)) & (F3DG_R3U_RING - 1)].x + 1u;
+                if (st.max_contributor - F3DG_SLOT_FLAG < (unsigned)F3DG_R4_WIN)
+                    st.max_contributor = sQ[(head + (st.max_contributor - F3DG_SLOT_FLAG)) & (F3DG_R3U_RING - 1)].x + 1u;
             }
-            wave_lds_fence();
+            f3dg_wave_fence();
             if (lane == 0) {
                 if (stop) __hip_atomic_store(&sStop, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 else __hip_atomic_store(&sConsWin, w + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);

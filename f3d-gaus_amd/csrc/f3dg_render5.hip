@@ -11,8 +11,8 @@
 //
 // Front-to-back compositing is a scan: with x_i = 1 - alpha_i the transmittance in front of entry i is T_front * prod_{j<i} x_j, and
 // every accumulator is a sum of terms that depend on the pair and on that product only (the distortion term needs two more prefix
-// sums). So this kernel keeps render3s's list scan / staging / phase 1 / sliding half-windows and its FUSED trips while more than
-// `th` pixels take part in a trip, and then
+// sums). So this kernel shares render3s's list scan / staging / phase 1 / sliding half-windows (F3dgHalfWindow, f3dg_quad.h), keeps its
+// FUSED trips while more than `th` pixels take part in a trip, and then
 //   * COMPACTS the pending entries (both halves of the window) of the pixels that still hold the older half back into a ring of
 //     (run position, pixel, slot) triples in pixel-major order -- a scalar loop over those pixels: the pass mask of a pixel is read
 //     into SGPRs, every lane that is a set bit of it writes its own triple at ring position tail + mbcnt(mask);
@@ -33,6 +33,7 @@
 #include "f3dg_blend.h"
 #include "f3dg_ellipse.h"
 #include "f3dg_producer.h"
+#include "f3dg_quad.h"
 #include "f3dg_segscan.h"
 
 #include <stdio.h>
@@ -49,21 +50,8 @@ __device__ unsigned long long g_f3dg_counts5[64][16];
 
 namespace {
 
-#define F3DG_R5_WIN 64
-#define F3DG_R5_RING 128
+#define F3DG_R5_KRING 128           // the compaction ring
 #define F3DG_R5_OCC 8               // 59 VGPRs (52 without normals and distortion), 5 KB of LDS: 8 waves per SIMD
-
-__device__ __forceinline__ void wave_lds_fence5()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float pull5(int addr, float v)
-{
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v)));
-}
 
 template <bool NORMAL, bool DIST, bool COUNT>
 __global__ void __launch_bounds__(64, F3DG_R5_OCC)
@@ -73,103 +61,28 @@ render5_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                    const float4* __restrict__ cull, const float* __restrict__ background, int bg_per_view,
                    float* __restrict__ out_color, int th, int min_trips)
 {
-    unsigned view, unit;
-    f3dg_xcd_map(blockIdx.x, (unsigned)V, 4u * (unsigned)T, view, unit);
-    const unsigned tile = unit >> 2, quad = unit & 3u;
-    const unsigned tile_x = tile % (unsigned)tiles_x, tile_y = tile / (unsigned)tiles_x;
+    const F3dgQuad qd = f3dg_quad(V, T, tiles_x);
+    const unsigned view = qd.view, qx0 = qd.qx0, qy0 = qd.qy0;
     const unsigned lane = threadIdx.x;
-    const unsigned qx0 = tile_x * F3DG_TILE + (quad & 1u) * 8u, qy0 = tile_y * F3DG_TILE + (quad >> 1) * 8u;
-    const unsigned pix_x = qx0 + (lane & 7u), pix_y = qy0 + (lane >> 3);
-    const bool inside = pix_x < (unsigned)W && pix_y < (unsigned)H;
-    const float pixf_x = (float)pix_x + 0.5f, pixf_y = (float)pix_y + 0.5f;
-    const float ray_x = (float)((pixf_x - W / 2.) / focal_x);
-    const float ray_y = (float)((pixf_y - H / 2.) / focal_y);
+    const auto [pix_x, pix_y, inside, pix_id, ray_x, ray_y] = f3dg_quad_pixel(qd, lane, W, H, focal_x, focal_y);
 
-    uint2 range = ranges[(size_t)view * T + tile];
-    if (hdr->overflow) range = make_uint2(0, 0);
-    const unsigned n = range.y - range.x;
-
-    __shared__ float4 sR[4][F3DG_R5_WIN];          // records, [16-byte chunk][slot]; slots 0..31 and 32..63 are the two halves of the window
-    __shared__ unsigned sQ[F3DG_R5_RING];          // ids of kept entries not staged yet, ring
-    __shared__ unsigned sK[F3DG_R5_RING];          // (position in the pixel's run << 12) | (owning lane << 6) | physical slot, ring
-
-    const F3dgRec* vrec = rec + (size_t)view * P;
-    const float4* vcull = cull + (size_t)view * P;
-    const unsigned qbit = 1u << (F3DG_ID_BITS + quad);
-    const unsigned hl = lane & 31u;               // entry of a half this lane tests in phase 1 ...
-    const unsigned row4 = (lane >> 5) * 4u;       // ... against the pixels of rows row4 .. row4 + 3
+    __shared__ float4 sR[4][64];                   // records, [16-byte chunk][slot]; slots 0..31 and 32..63 are the two halves of the window
+    __shared__ unsigned sQ[F3DG_QUAD_RING];        // ids of kept entries not staged yet, ring
+    __shared__ unsigned sK[F3DG_R5_KRING];         // (position in the pixel's run << 12) | (owning lane << 6) | physical slot, ring
 
     bool done = !inside;
     F3dgPixel st;
     f3dg_pixel_init(st);
 
     unsigned n_staged = 0, n_fused = 0, n_slides = 0, n_lane_fused = 0, n_batches = 0, n_batch_pairs = 0, n_compact = 0, n_cslides = 0;
-    unsigned cursor = 0, qhead = 0, qpend = 0;    // wave-uniform: scan position, ring index of the first pending entry, pending entries
-    unsigned flip = 0;                            // physical half (slots 32 flip ..) that holds the OLDER half of the window
-    unsigned long long pass = 0ull;               // per pixel: bits 0..31 older half, 32..63 newer half, in list order
-    unsigned idn = lane < n ? point_list[range.x + lane] : 0u;
+    F3dgHalfWindow<false> win(sR, sQ, nullptr, nullptr, qd, lane, P, T, hdr, ranges, point_list, rec, cull);
+    unsigned long long& pass = win.pass;
     if (__ballot(!done) != 0ull)
     for (;;) {
-        // ---- scan: keep the entries whose box reaches this quadrant until 32 are pending
-        while (qpend < 32u && cursor < n) {
-            const unsigned idm = idn, pos = cursor + lane;
-            cursor += 64u;
-            idn = cursor + lane < n ? point_list[range.x + cursor + lane] : 0u;
-            const bool keep = pos < n && (idm & qbit) != 0u;
-            const unsigned long long kb = __ballot(keep);
-            if (keep)
-                sQ[(qhead + qpend + __builtin_amdgcn_mbcnt_hi((unsigned)(kb >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)kb, 0u))) & (F3DG_R5_RING - 1)] = idm & F3DG_ID_MASK;
-            qpend += (unsigned)__popcll(kb);
-        }
-        const unsigned m = qpend < 32u ? qpend : 32u;
-        if (m == 0u && __ballot(pass != 0ull) == 0ull)
+        if (!win.slide(done))
             break;                                // nothing left to stage, nothing left in the newer half
-        wave_lds_fence5();
-
-        // ---- stage m entries into the retired half; lanes e and e + 32 both take entry e
-        const unsigned base = flip * 32u;
-        float4 e4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        float ec = 0.0f;
-        if (hl < m) {
-            const unsigned id = sQ[(qhead + hl) & (F3DG_R5_RING - 1)];
-            if (lane < 32u) {
-                const float4* src = reinterpret_cast<const float4*>(vrec + id);
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + c),
-                                                     (__attribute__((address_space(3))) void*)&sR[c][base], 16, 0, 0);
-            }
-            e4 = vcull[id];
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        wave_lds_fence5();
-        if (hl < m) ec = sR[3][base + hl].w;
-        qhead += m;
-        qpend -= m;
-        if (COUNT) { n_staged += m; n_slides++; }
-
-        // ---- phase 1: the 32 new entries against the quadrant's 64 pixels
-        int fresh = 0;
-        if (m != 0u) {
-            const float u0 = hl < m ? (float)qx0 - e4.x : __builtin_nanf("");     // NaN: every comparison below is false
-            const float v0 = (float)(qy0 + row4) - e4.y;
-            float dxx[8], adx[8], dyy[4], cdy[4];
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                dxx[q] = u0 + (float)q;
-                adx[q] = e4.z * dxx[q];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                dyy[q] = v0 + (float)q;
-                cdy[q] = ec * dyy[q] * dyy[q];
-            }
-            half_ballots<0>(fresh, fmaf(dxx[0], fmaf(e4.w, dyy[0], adx[0]), cdy[0]), dxx, adx, dyy, cdy, e4.w);
-        }
-        // ---- slide: the newer half becomes the older one, the fresh bits the newer one
-        pass = (pass >> 32) | (done ? 0ull : ((unsigned long long)(unsigned)fresh << 32));
-        flip ^= 1u;
-        const unsigned xr = flip << 5;            // logical slot j (0..31 older, 32..63 newer) lives in physical slot j ^ xr
+        if (COUNT) { n_staged += win.m; n_slides++; }
+        const unsigned xr = win.xr;
 
         // ---- phase 2a: fused trips while many pixels take part (a divergent loop: a pixel leaves it when its mask is empty; the
         // ballots are taken over the pixels still inside)
@@ -243,7 +156,7 @@ render5_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                     const unsigned word = lane < 32u ? mlo : mhi;
                     const bool take = ((word >> (lane & 31u)) & 1u) != 0u && r < cnt;
                     if (take)
-                        sK[(qt + r) & (F3DG_R5_RING - 1)] = (r << 12) | ((unsigned)p << 6) | (lane ^ xr);
+                        sK[(qt + r) & (F3DG_R5_KRING - 1)] = (r << 12) | ((unsigned)p << 6) | (lane ^ xr);
                     const unsigned left = mhi & ~(unsigned)(__ballot(take) >> 32);       // newer-half entries that stay pending
                     // lane p: its run's ring positions; its pending mask loses what was taken (v_writelane_b32 ignores EXEC; lane in M0)
                     asm volatile("s_mov_b32 m0, %[p]\n\t"
@@ -259,11 +172,11 @@ render5_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                     if (COUNT) n_compact++;
                 }
                 const unsigned nb = qt - qh < 64u ? qt - qh : 64u;
-                wave_lds_fence5();
+                f3dg_wave_fence();
                 if (COUNT) { n_batches++; n_batch_pairs += nb; }
 
                 // ---- one dense batch: lane q takes triple q of the ring
-                const unsigned kk = sK[(qh + lane) & (F3DG_R5_RING - 1)];
+                const unsigned kk = sK[(qh + lane) & (F3DG_R5_KRING - 1)];
                 const bool valid = lane < nb;
                 // (lanes beyond the batch re-evaluate pair 0 -- finite numbers -- with alpha forced to 0, each its own run)
                 const unsigned k = valid ? kk : (unsigned)__builtin_amdgcn_readfirstlane((int)kk);
@@ -271,10 +184,10 @@ render5_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                 const unsigned rr = valid ? (rrun < lane ? rrun : lane) : 0u;       // lanes between this pair and the start of its run INSIDE the batch
                 const int oaddr = (int)(((k >> 6) & 63u) << 2);
                 const unsigned j = k & 63u;
-                const float rx = pull5(oaddr, ray_x), ry = pull5(oaddr, ray_y);
-                const float Tf = pull5(oaddr, done ? 0.0f : st.Tr);                    // a pixel that has stopped: every later pair of it is killed
+                const float rx = f3dg_pull(oaddr, ray_x), ry = f3dg_pull(oaddr, ray_y);
+                const float Tf = f3dg_pull(oaddr, done ? 0.0f : st.Tr);                    // a pixel that has stopped: every later pair of it is killed
                 float D1 = 0.0f, D2 = 0.0f;
-                if (DIST) { D1 = pull5(oaddr, st.dist1); D2 = pull5(oaddr, st.dist2); }
+                if (DIST) { D1 = f3dg_pull(oaddr, st.dist1); D2 = f3dg_pull(oaddr, st.dist2); }
                 const float4 q0 = sR[0][j], q1 = sR[1][j], q2 = sR[2][j], q3 = sR[3][j];
                 const F3dgPair pr = f3dg_pair_eval<true, NORMAL, DIST, true>(rx, ry, q0, q1, q2);
                 asm volatile("" :: "v"(q2.w), "v"(q3.w), "v"(pr.alpha));
@@ -312,19 +225,19 @@ render5_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                 const bool mine_in = rs < qh + nb && re > qh;
                 const unsigned lastq = (re < qh + nb ? re : qh + nb) - 1u - qh;
                 const int saddr = (int)((lastq & 63u) << 2);
-                const float tTl = pull5(saddr, tT);
+                const float tTl = f3dg_pull(saddr, tT);
                 float sv[KM];
 #pragma unroll
-                for (int c = 0; c < KM; c++) sv[c] = pull5(saddr, v[c]);
+                for (int c = 0; c < KM; c++) sv[c] = f3dg_pull(saddr, v[c]);
                 float s1 = 0.0f, s2 = 0.0f;
-                if (DIST) { s1 = pull5(saddr, a[0]); s2 = pull5(saddr, a[1]); }
+                if (DIST) { s1 = f3dg_pull(saddr, a[0]); s2 = f3dg_pull(saddr, a[1]); }
                 // median depth (forward.cu:571-575): the last blended pair of the run in front of which T was still above 0.5
                 const unsigned long long G = __ballot(!killed && alpha != 0.0f && Tb > 0.5f);
                 if (G != 0ull) {
                     const unsigned firstq = (rs > qh ? rs : qh) - qh;
                     const unsigned long long sel = mine_in ? ((G >> (firstq & 63u)) << (firstq & 63u)) & (~0ull >> (63u - (lastq & 63u))) : 0ull;
                     const unsigned Lq = sel != 0ull ? 63u - (unsigned)__builtin_clzll(sel) : 0u;
-                    const float tl = pull5((int)(Lq << 2), pr.t);
+                    const float tl = f3dg_pull((int)(Lq << 2), pr.t);
                     if (sel != 0ull) st.C6 = tl;
                 }
                 if (mine_in) {
@@ -337,7 +250,7 @@ render5_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                     done = done || stop;
                 }
                 qh += nb;
-                wave_lds_fence5();          // the next compaction overwrites ring slots this batch has read
+                f3dg_wave_fence();          // the next compaction overwrites ring slots this batch has read
             } while (tk != 0ull || qt != qh);
             pass = done ? 0ull : ((unsigned long long)phi << 32) | plo;      // (a pixel that stopped in a batch drops the newer-half entries it kept)
         }
@@ -355,7 +268,7 @@ render5_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
         if (lane == 0) {
             unsigned long long* c = g_f3dg_counts5[blockIdx.x & 63u];
             atomicAdd(&c[0], (unsigned long long)n_staged);
-            atomicAdd(&c[1], (unsigned long long)(cursor < n ? cursor : n));
+            atomicAdd(&c[1], (unsigned long long)(win.cursor < win.n ? win.cursor : win.n));
             atomicAdd(&c[2], (unsigned long long)f);
             atomicAdd(&c[3], (unsigned long long)n_slides);
             atomicAdd(&c[4], (unsigned long long)a);
@@ -412,14 +325,11 @@ render5p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
                     const float4* __restrict__ cull, const float* __restrict__ background, int bg_per_view,
                     float* __restrict__ out_color)
 {
-    unsigned view, unit;
-    f3dg_xcd_map(blockIdx.x, (unsigned)V, 4u * (unsigned)T, view, unit);
-    const unsigned tile = unit >> 2, quad = unit & 3u;
-    const unsigned tile_x = tile % (unsigned)tiles_x, tile_y = tile / (unsigned)tiles_x;
+    const F3dgQuad qd = f3dg_quad(V, T, tiles_x);
+    const auto [view, tile, quad, qx0, qy0] = qd;
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wv = threadIdx.x >> 6;                 // 0..3: consumers, 4: the producer (wave-uniform)
     const bool producer = wv == 4u;
-    const unsigned qx0 = tile_x * F3DG_TILE + (quad & 1u) * 8u, qy0 = tile_y * F3DG_TILE + (quad >> 1) * 8u;
 
     __shared__ float4 sR[3][4][F3DG_PROD_WIN];            // three windows of records, [window % 3][16-byte chunk][entry]
     __shared__ uint2 sQ[F3DG_PROD_RING];                   // (list position, Gaussian id) of the kept entries (the producer's ring)
@@ -438,11 +348,7 @@ render5p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
     // ================================================== waves 0..3: 16 pixels x 4 lanes each ==================================================
     const unsigned sub = lane & 3u;                       // which of the pixel's next four entries this lane takes
     const unsigned q = 16u * wv + lane / 4u;              // the pixel, 0..63 in the quadrant
-    const unsigned pix_x = qx0 + (q & 7u), pix_y = qy0 + (q >> 3);
-    const bool inside = pix_x < (unsigned)W && pix_y < (unsigned)H;
-    const float pixf_x = (float)pix_x + 0.5f, pixf_y = (float)pix_y + 0.5f;
-    const float ray_x = (float)((pixf_x - W / 2.) / focal_x);
-    const float ray_y = (float)((pixf_y - H / 2.) / focal_y);
+    const auto [pix_x, pix_y, inside, pix_id, ray_x, ray_y] = f3dg_quad_pixel(qd, q, W, H, focal_x, focal_y);
     bool done = !inside;
     float Tf = 1.0f, D1 = 0.0f, D2 = 0.0f;               // per pixel (the same in its four lanes): T, the distortion's running sums
     float C0 = 0, C1 = 0, C2 = 0, C3 = 0, C4 = 0, C5 = 0, C7 = 0, Cd = 0;      // per LANE: the sums of its own entries
