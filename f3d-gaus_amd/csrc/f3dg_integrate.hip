@@ -7,11 +7,13 @@
 // results only depend on per-pixel and per-point quantities, so the work is reorganised MI355X-first without changing
 // a single value:
 //
-//   pass 1  (one workgroup per tile, one pixel per lane)  the first loop of integrateCUDA: five rays per pixel
-//           (centre + 4 corners), colour / alpha / maximal depth of the pixel, and the pixel's list of contributing
-//           Gaussians -- written to a global [pixel][1024] u16 table instead of a private array. The conservative
-//           alpha >= 1/255 ellipse of the compositing kernel is reused (widened by the half pixel of the corner rays); it
-//           only removes (ray, Gaussian) pairs the reference `continue`s on.
+//   pass 1  (one workgroup per tile)  the first loop of integrateCUDA: five rays per pixel (centre + 4 corners), colour /
+//           alpha / maximal depth of the pixel, and the pixel's list of contributing Gaussians -- written to a global
+//           [pixel][1024] u16 table instead of a private array. A corner ray belongs to four pixels, so a tile walks 545
+//           shared rays instead of 1,280 (integrate_pass1_rays_kernel), culled by the conservative alpha >= 1/255 ellipse
+//           of the compositing kernel; it only removes (ray, Gaussian) pairs the reference `continue`s on. The plain
+//           transcription, one pixel per lane (integrate_pass1_kernel), is the bit-identity reference and redoes the rare
+//           tile in which a pixel stops at 1,024 contributors.
 //   points  (one LANE PER POINT, visited in pixel order)  preprocessPointsCUDA fused with the second loop of integrateCUDA:
 //           the point finds its pixel, walks that pixel's contributor list and accumulates its alpha. Loop interchange
 //           (points outside, Gaussians inside) is exact because every point's recurrence is independent. The tile's
@@ -41,7 +43,7 @@ struct Pass1State {
 };
 
 // One (ray, Gaussian) evaluation of forward.cu:903-962. Returns true when the ray "used" the Gaussian.
-template <bool FILTER, int K>
+template <int K>
 __device__ __forceinline__ bool ray_entry(Pass1State& st, float rx, float ry, const float4& q0, const float4& q1,
                                           const float4& q2, const float4& q3)
 {
@@ -50,13 +52,6 @@ __device__ __forceinline__ bool ray_entry(Pass1State& st, float rx, float ry, co
     const float n2 = q0.z * rx + q1.x * ry + q1.y;
     const float AA = rx * n0 + ry * n1 + n2;
     const float bhalf = q1.z * rx + q1.w * ry + q2.x;
-    if (FILTER) {
-        // Conservative pre-test (f3dg_preprocess.hip pretest_constant): certainly alpha < 1/255. This loop divides
-        // BB / AA in float32 (the compositing loop in float64); the extra relative error 2^-24 of b^2/a is inside the
-        // 5e-7 margin of K (3.2e-7 used by the product roundings and K's own narrowing).
-        if (bhalf * bhalf < q2.w * AA)
-            return false;
-    }
     const float BB = 2 * bhalf;
     const float CC = q2.y;
     const float q = BB / AA;                            // one float32 division: -BB / (2 * AA) == -0.5f * (BB / AA) exactly
@@ -97,7 +92,10 @@ __device__ __forceinline__ RayEval ray_eval(float rx, float ry, const float4& q0
     const float n2 = q0.z * rx + q1.x * ry + q1.y;
     const float AA = rx * n0 + ry * n1 + n2;
     const float bhalf = q1.z * rx + q1.w * ry + q2.x;
-    const bool pre = bhalf * bhalf < q2.w * AA;          // certainly alpha < 1/255 (see ray_entry)
+    // Conservative pre-test (f3dg_preprocess.hip pretest_constant): certainly alpha < 1/255. This loop divides BB / AA in float32 (the
+    // compositing loop in float64); the extra relative error 2^-24 of b^2/a is inside the 5e-7 margin of K (3.2e-7 used by the product
+    // roundings and K's own narrowing).
+    const bool pre = bhalf * bhalf < q2.w * AA;
     const float BB = 2 * bhalf;
     const float CC = q2.y;
     const float q = BB / AA;
@@ -130,16 +128,28 @@ __device__ __forceinline__ bool ray_apply(Pass1State& st, const RayEval& e, cons
     return true;
 }
 
-// ---- the plain transcription of pass 1: every ray of every pixel visits every list entry (option reference_kernels; the baseline the
-// bit-identity tests hold the shared-ray pass below to). One camera per launch.
+// ---- the plain transcription of pass 1: every ray of every pixel visits every list entry. It runs in two roles: on every tile under
+// option reference_kernels (the baseline the bit-identity tests hold the shared-ray pass below to), and behind the shared-ray pass on
+// the tiles which that pass flagged in `redo` (a pixel reached 1,024 contributors). One workgroup per (camera, tile) of a batched prepare.
+// It deliberately shares nothing with the shared-ray pass beyond Pass1State -- its own ray_entry against ray_eval + ray_apply, its own
+// contributor append and pixel write-out: a helper common to both could be wrong in both, and the tests would not see it.
 __global__ void __launch_bounds__(F3DG_BLOCK)
-integrate_pass1_kernel(int W, int H, int tiles_x, float focal_x, float focal_y, const F3dgHeader* __restrict__ hdr,
+integrate_pass1_kernel(int V, int P, int T, int W, int H, int tiles_x, float focal_x, float focal_y, const F3dgHeader* __restrict__ hdr,
                        const uint2* __restrict__ ranges, const unsigned* __restrict__ point_list, const F3dgRec* __restrict__ rec,
                        const float* __restrict__ background, float* __restrict__ out_color,
                        float* __restrict__ final_T, unsigned* __restrict__ n_contrib,
-                       unsigned short* __restrict__ contrib_ids, unsigned* __restrict__ contrib_n)
+                       unsigned short* __restrict__ contrib_ids, unsigned* __restrict__ contrib_n,
+                       const unsigned* __restrict__ only /* null, or [V*T] flags: the tiles to compute */)
 {
-    const unsigned tile = blockIdx.x;
+    unsigned view, tile;
+    f3dg_xcd_map(blockIdx.x, (unsigned)V, (unsigned)T, view, tile);
+    if (only != nullptr && only[(size_t)view * T + tile] == 0u)
+        return;
+    const size_t HW = (size_t)H * W;
+    // every per-camera array is the camera's slice of a [V, ...] array
+    ranges += (size_t)view * T; rec += (size_t)view * P;
+    out_color += (size_t)view * F3DG_OUT_CHANNELS * HW; final_T += (size_t)view * 4 * HW; n_contrib += (size_t)view * 2 * HW;
+    contrib_ids += (size_t)view * HW * F3DG_MAX_CONTRIB; contrib_n += (size_t)view * HW;
     const unsigned tile_x = tile % (unsigned)tiles_x, tile_y = tile / (unsigned)tiles_x;
     // lane -> pixel: wave = 8x8 quadrant, 16-lane group = 4x4 block
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -148,7 +158,6 @@ integrate_pass1_kernel(int W, int H, int tiles_x, float focal_x, float focal_y, 
     const unsigned lx = blk_x * 4u + (gi & 3u), ly = blk_y * 4u + (gi >> 2);
     const unsigned pix_x = tile_x * F3DG_TILE + lx, pix_y = tile_y * F3DG_TILE + ly;
     const bool inside = pix_x < (unsigned)W && pix_y < (unsigned)H;
-    const size_t HW = (size_t)H * W;
     const size_t pix_id = (size_t)W * pix_y + pix_x;
     const float pixf_x = (float)pix_x + 0.5f, pixf_y = (float)pix_y + 0.5f;
     // the five rays of forward.cu:864-866, 905: offsets (0,0) (-.5,-.5) (.5,-.5) (-.5,.5) (.5,.5)
@@ -213,11 +222,11 @@ integrate_pass1_kernel(int W, int H, int tiles_x, float focal_x, float focal_y, 
         for (int j = 0; !done && j < count; j++) {
             const float4 q0 = sq0[j], q1 = sq1[j], q2 = sq2[j], q3 = sq3[j];
             bool used = false;
-            used |= ray_entry<false, 0>(st, rx0, ry0, q0, q1, q2, q3);
-            used |= ray_entry<false, 1>(st, rxm, rym, q0, q1, q2, q3);
-            used |= ray_entry<false, 2>(st, rxp, rym, q0, q1, q2, q3);
-            used |= ray_entry<false, 3>(st, rxm, ryp, q0, q1, q2, q3);
-            used |= ray_entry<false, 4>(st, rxp, ryp, q0, q1, q2, q3);
+            used |= ray_entry<0>(st, rx0, ry0, q0, q1, q2, q3);
+            used |= ray_entry<1>(st, rxm, rym, q0, q1, q2, q3);
+            used |= ray_entry<2>(st, rxp, rym, q0, q1, q2, q3);
+            used |= ray_entry<3>(st, rxm, ryp, q0, q1, q2, q3);
+            used |= ray_entry<4>(st, rxp, ryp, q0, q1, q2, q3);
             if (used) {
                 const unsigned contributor = round_base + (unsigned)j + 1u;
                 st.last_contributor = contributor;
@@ -225,211 +234,6 @@ integrate_pass1_kernel(int W, int H, int tiles_x, float focal_x, float focal_y, 
                 st.nloc += 1;
                 if (st.nloc >= F3DG_MAX_CONTRIB)
                     done = true;                                    // "Maximal contributors are met", forward.cu:972-976
-            }
-        }
-    }
-
-    if (inside) {                                                  // forward.cu:984-996
-        final_T[pix_id] = st.Ts[0];
-        n_contrib[pix_id] = st.last_contributor;
-        contrib_n[pix_id] = st.nloc;
-        out_color[0 * HW + pix_id] = st.C0 + st.Ts[0] * background[0];
-        out_color[1 * HW + pix_id] = st.C1 + st.Ts[0] * background[1];
-        out_color[2 * HW + pix_id] = st.C2 + st.Ts[0] * background[2];
-        out_color[3 * HW + pix_id] = 0.0f;                         // the caller's zero fill, rasterize_points.cu:273
-        out_color[4 * HW + pix_id] = 0.0f;
-        out_color[5 * HW + pix_id] = 0.0f;
-        out_color[6 * HW + pix_id] = st.C6;
-        out_color[7 * HW + pix_id] = st.C7;
-    }
-}
-
-// The same pass with the culling machinery of the compositing forward: a per-ray K pre-test (ray_entry<true>) costs
-// ~25 instructions per (ray, Gaussian) = 125 per (pixel, list entry), and no pixel ever leaves the loop early here (a saturated ray
-// `continue`s), so the pass was 60-90 % of an integrate call. A list entry is instead tested ONCE per pixel against the record's
-// conservative alpha >= 1/255 ellipse, Gaussians across the lanes (two FMAs per pixel, one comparison = one wave ballot), and only
-// the passing (pixel, entry) pairs go through the five rays. The corner rays leave the pixel centre by (+-0.5, +-0.5) px: the ellipse
-// is scaled uniformly about its centre by 1 + 0.7072 px / semi-minor axis, which contains its Minkowski sum with that square
-// (a >= b: (a + r, b + r) fits inside (a, b) (b + r) / b). As everywhere, this only removes pairs the reference `continue`s on.
-__global__ void __launch_bounds__(F3DG_BLOCK)
-integrate_pass1_cull_kernel(int V, int P, int T, int W, int H, int tiles_x, float focal_x, float focal_y, const F3dgHeader* __restrict__ hdr,
-                            const uint2* __restrict__ ranges, const unsigned* __restrict__ point_list,
-                            const F3dgRec* __restrict__ rec, const float4* __restrict__ cull,
-                            const float* __restrict__ background, float* __restrict__ out_color,
-                            float* __restrict__ final_T, unsigned* __restrict__ n_contrib,
-                            unsigned short* __restrict__ contrib_ids, unsigned* __restrict__ contrib_n,
-                            const unsigned* __restrict__ only /* null, or [V*T] flags: the tiles to compute */)
-{
-    constexpr int ROUND = F3DG_BLOCK;             // staged entries per round (byte indices 0..255)
-    if (only != nullptr) {                        // the tiles integrate_pass1_rays_kernel handed back (a pixel reached 1,024 contributors)
-        unsigned view_, tile_;
-        f3dg_xcd_map(blockIdx.x, (unsigned)V, (unsigned)T, view_, tile_);
-        if (only[(size_t)view_ * T + tile_] == 0u) return;
-    }
-    // several cameras of the same Gaussians in one launch (f3dg_integrate_prepare_batched): one 256^2 camera is 256 workgroups,
-    // a wave per SIMD and nothing to overlap its latencies with; every per-camera array is the camera's slice of a [V, ...] array
-    unsigned view, tile;
-    f3dg_xcd_map(blockIdx.x, (unsigned)V, (unsigned)T, view, tile);
-    {
-        const size_t HWv = (size_t)H * W;
-        ranges += (size_t)view * T; rec += (size_t)view * P; cull += (size_t)view * P;
-        out_color += (size_t)view * F3DG_OUT_CHANNELS * HWv; final_T += (size_t)view * 4 * HWv; n_contrib += (size_t)view * 2 * HWv;
-        contrib_ids += (size_t)view * HWv * F3DG_MAX_CONTRIB; contrib_n += (size_t)view * HWv;
-    }
-    const unsigned tile_x = tile % (unsigned)tiles_x, tile_y = tile / (unsigned)tiles_x;
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const unsigned grp = lane >> 4, gi = lane & 15u;
-    const unsigned blk_x = (wave & 1u) * 2u + (grp & 1u), blk_y = (wave >> 1) * 2u + (grp >> 1);
-    const unsigned lx = blk_x * 4u + (gi & 3u), ly = blk_y * 4u + (gi >> 2);
-    const unsigned pix_x = tile_x * F3DG_TILE + lx, pix_y = tile_y * F3DG_TILE + ly;
-    const bool inside = pix_x < (unsigned)W && pix_y < (unsigned)H;
-    const size_t HW = (size_t)H * W;
-    const size_t pix_id = (size_t)W * pix_y + pix_x;
-    const float pixf_x = (float)pix_x + 0.5f, pixf_y = (float)pix_y + 0.5f;
-    const float rx0 = (float)((pixf_x + 0.0f - W / 2.) / focal_x), ry0 = (float)((pixf_y + 0.0f - H / 2.) / focal_y);
-    const float rxm = (float)((pixf_x + -0.5f - W / 2.) / focal_x), rym = (float)((pixf_y + -0.5f - H / 2.) / focal_y);
-    const float rxp = (float)((pixf_x + 0.5f - W / 2.) / focal_x), ryp = (float)((pixf_y + 0.5f - H / 2.) / focal_y);
-    const float blk_px0 = (float)(tile_x * F3DG_TILE + blk_x * 4u), blk_py0 = (float)(tile_y * F3DG_TILE + blk_y * 4u);
-    const float tile_px0 = (float)(tile_x * F3DG_TILE), tile_py0 = (float)(tile_y * F3DG_TILE);
-
-    uint2 range = ranges[tile];
-    if (hdr->overflow) range = make_uint2(0, 0);
-    const int rounds = (int)((range.y - range.x + ROUND - 1) / ROUND);
-
-    __shared__ float4 sq0[ROUND], sq1[ROUND], sq2[ROUND], sq3[ROUND];      // v0..v3 | v4..v7 | v8 v9 opac K | r g b -
-    __shared__ float4 sE[ROUND];                  // inflated ellipse: cx cy a b
-    __shared__ float sF[ROUND];                   //                    c
-    __shared__ unsigned short sM[ROUND];          // which of the tile's 16 4x4 blocks its box touches
-    __shared__ __align__(16) unsigned char lists[F3DG_BLOCK / 64][4][ROUND];
-    __shared__ int done_cnt[2];
-    if (threadIdx.x < 2) done_cnt[threadIdx.x] = 0;
-    __syncthreads();
-
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    const unsigned pull = (gi + 16u * (grp >> 1)) * 4u;       // ds_bpermute source of this pixel's ballot half
-    const unsigned pull_shift = 16u * (grp & 1u);
-    const unsigned char* my_list = lists[wave][grp];
-
-    bool done = !inside;
-    Pass1State st;
-#pragma unroll
-    for (int k = 0; k < 5; k++) st.Ts[k] = 1.0f;
-    st.C0 = st.C1 = st.C2 = st.C6 = st.C7 = 0;
-    st.last_contributor = 0; st.nloc = 0;
-    unsigned short* my_ids = contrib_ids + pix_id * F3DG_MAX_CONTRIB;
-
-    for (int i = 0; i < rounds; i++) {
-        const unsigned long long alive = __ballot(!done);
-        if (lane == 0)
-            atomicAdd(&done_cnt[i & 1], 64 - __popcll(alive));
-        __syncthreads();
-        const int num_done = done_cnt[i & 1];
-        if (threadIdx.x == 0)
-            done_cnt[(i + 1) & 1] = 0;
-        if (num_done == F3DG_BLOCK)
-            break;
-
-        const unsigned progress = (unsigned)i * ROUND + threadIdx.x;
-        unsigned short m16 = 0;
-        if (range.x + progress < range.y) {
-            const unsigned id = point_list[range.x + progress] & F3DG_ID_MASK;
-            const float4* src = reinterpret_cast<const float4*>(rec + id);
-            const float4 a = src[0], b = src[1], c = src[2], d = src[3];
-            float4 e = cull[id];
-            float ec = d.w;
-            // scale about the centre by s = 1 + 0.7072 sqrt(lmax) (lmax = 1 / semi-minor axis^2), rounded outwards; "everything"
-            // records (a = b = c = 0) stay what they are, an overflowing lmax ends as a = b = c = 0 = "everything"
-            const float hd = 0.5f * (e.z - ec);
-            const float lmax = 0.5f * (e.z + ec) + sqrtf(hd * hd + 0.25f * e.w * e.w);
-            const float sc = 1.0f + 0.70715f * sqrtf(lmax) * 1.0001f;
-            const float inv = (1.0f / (sc * sc)) * 0.99999f;
-            e.z *= inv; e.w *= inv; ec *= inv;
-            if (!(e.z == e.z) || !(e.w == e.w) || !(ec == ec)) { e.z = 0.0f; e.w = 0.0f; ec = 0.0f; }
-            sq0[threadIdx.x] = a; sq1[threadIdx.x] = b; sq2[threadIdx.x] = c; sq3[threadIdx.x] = d;
-            sE[threadIdx.x] = e;
-            sF[threadIdx.x] = ec;
-            m16 = (unsigned short)ellipse_block_mask(e, ec, tile_px0, tile_py0);
-        }
-        sM[threadIdx.x] = m16;
-        __syncthreads();
-
-        // four compacted lists per wave, one per 16-lane group (4x4 block), in list order
-        int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-        {
-            const unsigned qx2 = (wave & 1u) * 2u, qy2 = (wave >> 1) * 2u;
-            const bool g0 = (alive & 0xFFFFull) != 0, g1 = (alive & 0xFFFF0000ull) != 0, g2 = (alive & 0xFFFF00000000ull) != 0,
-                       g3 = (alive >> 48) != 0;
-#pragma unroll
-            for (int c = 0; c < ROUND / 64; c++) {
-                const unsigned e = c * 64 + lane;
-                const unsigned m = sM[e];
-                const bool b0 = g0 && ((m >> ((qy2 + 0u) * 4u + qx2 + 0u)) & 1u), b1 = g1 && ((m >> ((qy2 + 0u) * 4u + qx2 + 1u)) & 1u);
-                const bool b2 = g2 && ((m >> ((qy2 + 1u) * 4u + qx2 + 0u)) & 1u), b3 = g3 && ((m >> ((qy2 + 1u) * 4u + qx2 + 1u)) & 1u);
-                const unsigned long long l0 = __ballot(b0), l1 = __ballot(b1), l2 = __ballot(b2), l3 = __ballot(b3);
-                if (b0) lists[wave][0][c0 + __popcll(l0 & lt)] = (unsigned char)e;
-                if (b1) lists[wave][1][c1 + __popcll(l1 & lt)] = (unsigned char)e;
-                if (b2) lists[wave][2][c2 + __popcll(l2 & lt)] = (unsigned char)e;
-                if (b3) lists[wave][3][c3 + __popcll(l3 & lt)] = (unsigned char)e;
-                c0 += __popcll(l0); c1 += __popcll(l1); c2 += __popcll(l2); c3 += __popcll(l3);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-        const int count = max(max(c0, c1), max(c2, c3));
-        const int my_len = grp == 0 ? c0 : grp == 1 ? c1 : grp == 2 ? c2 : c3;
-        const unsigned round_base = (unsigned)i * ROUND;
-
-        for (int w0 = 0; w0 < count; w0 += 64) {
-            // ---- phase 1: lane (g, e) tests entry w0 + 16 sub + e of group g's list against the 16 pixels of g's block
-            unsigned pass_lo = 0, pass_hi = 0;
-#pragma unroll 1
-            for (int sub = 0; sub < 4; sub++) {
-                const int base = w0 + 16 * sub;
-                if (base >= count)
-                    break;
-                const int pos = base + (int)gi;
-                const int j = (int)my_list[pos];
-                const float4 e = sE[j];
-                const float cc = sF[j];
-                const float u0 = pos < my_len ? blk_px0 - e.x : __builtin_nanf("");     // NaN: every comparison below is false
-                const float v0 = blk_py0 - e.y;
-                float dxx[4], adx[4], dyy[4], cdy[4];
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    dxx[q] = u0 + (float)q;
-                    adx[q] = e.z * dxx[q];
-                    dyy[q] = v0 + (float)q;
-                    cdy[q] = cc * dyy[q] * dyy[q];
-                }
-                int stage = 0;
-                ellipse_ballots<0>(stage, fmaf(dxx[0], fmaf(e.w, dyy[0], adx[0]), cdy[0]), dxx, adx, dyy, cdy, e.w);
-                const unsigned piece = ((unsigned)__builtin_amdgcn_ds_bpermute((int)pull, stage) >> pull_shift) & 0xFFFFu;
-                if (sub & 2) pass_hi |= piece << (16 * (sub & 1));
-                else pass_lo |= piece << (16 * (sub & 1));
-            }
-            unsigned long long pass = done ? 0ull : ((unsigned long long)pass_hi << 32) | pass_lo;
-
-            // ---- phase 2: the five rays of this pixel through its own passing entries, in list order
-            while (pass != 0 && !done) {
-                const int kk = __builtin_ctzll(pass);
-                pass &= pass - 1;
-                const int j = (int)my_list[w0 + kk];
-                const float4 q0 = sq0[j], q1 = sq1[j], q2 = sq2[j], q3 = sq3[j];
-                bool used = false;
-                used |= ray_entry<true, 0>(st, rx0, ry0, q0, q1, q2, q3);
-                used |= ray_entry<true, 1>(st, rxm, rym, q0, q1, q2, q3);
-                used |= ray_entry<true, 2>(st, rxp, rym, q0, q1, q2, q3);
-                used |= ray_entry<true, 3>(st, rxm, ryp, q0, q1, q2, q3);
-                used |= ray_entry<true, 4>(st, rxp, ryp, q0, q1, q2, q3);
-                if (used) {
-                    const unsigned contributor = round_base + (unsigned)j + 1u;
-                    st.last_contributor = contributor;
-                    my_ids[st.nloc] = (unsigned short)contributor;     // (u_int16_t) cast of forward.cu:969
-                    st.nloc += 1;
-                    if (st.nloc >= F3DG_MAX_CONTRIB)
-                        done = true;                                    // "Maximal contributors are met", forward.cu:972-976
-                }
             }
         }
     }
@@ -464,15 +268,15 @@ integrate_pass1_cull_kernel(int V, int P, int T, int W, int H, int tiles_x, floa
 // (waves 4-7, while waves 0-3 still merge the previous round) with a 5-bit mask per entry: which quadrants' ray positions / the edge
 // the box of its conservative ellipse reaches. Every wave compacts the round to the entries of its region and takes them in 64-entry
 // windows: phase 1 with the Gaussians across the lanes (the record's ellipse at the wave's 64 ray positions -- corners are half-
-// integer positions of the same grid, no inflation as in integrate_pass1_cull_kernel --, quad_ballots), phase 2 with the rays
+// integer positions of the same grid, so the ellipse needs no inflation --, quad_ballots), phase 2 with the rays
 // across the lanes, each through its own passing entries; a used entry sets its bit in the ray's 256-bit mask of the round (LDS),
 // and after the round's second barrier the pixel lanes OR their five rays' masks and append the contributors.
 // A ray is FINISHED once fl(T fl(1 - 1/255)) < 0.0001: every later entry either has alpha < 1/255 or fails `test_T < 0.0001`
 // (forward.cu:934-938; rounding is monotone and 1 - alpha <= 1 - 1/255), both a bare `continue` before anything is written -- the
 // reference walks on through the rest of the list for nothing. Finished rays leave phase 2, a tile whose rays are all finished
-// stops staging: the saturation exit of the compositing kernel, which integrate_pass1_cull_kernel does not have.
+// stops staging: the saturation exit of the compositing kernel.
 // The one thing a shared ray cannot reproduce is a pixel that stops at 1,024 contributors (forward.cu:972-976: its rays end there
-// while its neighbours' go on): such a tile raises its `redo` flag and integrate_pass1_cull_kernel, launched behind this kernel on
+// while its neighbours' go on): such a tile raises its `redo` flag and integrate_pass1_kernel, launched behind this kernel on
 // the flagged tiles only, computes it pixel by pixel.
 #define F3DG_RAYS_THREADS 512
 __global__ void __launch_bounds__(F3DG_RAYS_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
@@ -580,7 +384,8 @@ integrate_pass1_rays_kernel(int V, int P, int T, int W, int H, int tiles_x, floa
                 sq0[t] = src[0]; sq1[t] = src[1]; sq2[t] = src[2]; sq3[t] = d3;
                 const float4 e = cull[id];
                 sE[t] = e;
-                // box of the ellipse (as ellipse_block_mask) against the ray positions: quadrant q's are q8 - 0.5 .. q8 + 7, the edge's 15.5
+                // box of the ellipse a x^2 + b x y + c y^2 <= 1 (half extents sqrt(c / det), sqrt(a / det), det = a c - b^2 / 4, widened by
+                // 0.05 % + 2e-3 px; "everything" records have det = 0) against the ray positions: quadrant q's are q8 - 0.5 .. q8 + 7, the edge's 15.5
                 const float det = fmaf(e.z, d3.w, -0.25f * e.w * e.w);
                 m5 = 31u;
                 if (det > 0.0f) {
@@ -984,14 +789,6 @@ int f3dg_launch_integrate_fill(hipStream_t s, int W, int H, int PN, float* out_c
     return F3DG_OK;
 }
 
-// diagnostic (tools): resident workgroups per CU of the two pass-1 kernels as the runtime computes it
-extern "C" int f3dg_debug_pass1_occupancy(int* rays_blocks, int* cull_blocks)
-{
-    F3DG_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(rays_blocks, integrate_pass1_rays_kernel, F3DG_RAYS_THREADS, 0));
-    F3DG_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(cull_blocks, integrate_pass1_cull_kernel, F3DG_BLOCK, 0));
-    return F3DG_OK;
-}
-
 // pass 1: depends on the Gaussians and the camera only (not on the points), so its result -- colours, last contributors and
 // the per-pixel contributor table inside the workspace -- can be kept and reused for any number of point sets
 int f3dg_launch_integrate_pass1(hipStream_t s, int V, int P, int W, int H, float focal_x, float focal_y, const F3dgLayout& L,
@@ -999,7 +796,6 @@ int f3dg_launch_integrate_pass1(hipStream_t s, int V, int P, int W, int H, float
 {
     const int tiles_x = (W + F3DG_TILE - 1) / F3DG_TILE, tiles_y = (H + F3DG_TILE - 1) / F3DG_TILE;
     const int T = tiles_x * tiles_y;
-    const size_t HW = (size_t)W * H;
     const F3dgHeader* hdr = reinterpret_cast<const F3dgHeader*>(ws + L.header);
     const uint2* ranges = reinterpret_cast<const uint2*>(ws + L.ranges);
     const unsigned* point_list = reinterpret_cast<const unsigned*>(ws + L.vals[0]);
@@ -1008,21 +804,18 @@ int f3dg_launch_integrate_pass1(hipStream_t s, int V, int P, int W, int H, float
     unsigned* n_contrib = reinterpret_cast<unsigned*>(ws + L.n_contrib);
     unsigned short* contrib_ids = reinterpret_cast<unsigned short*>(ws + I.contrib_ids);
     unsigned* contrib_n = reinterpret_cast<unsigned*>(ws + I.contrib_n);
-    if (g_f3dg_reference_kernels) {
-        for (int v = 0; v < V; v++)         // the plain transcription, one camera per launch
-            F3DG_KLAUNCH(integrate_pass1_kernel, dim3(T), dim3(F3DG_BLOCK), 0, s, W, H, tiles_x, focal_x, focal_y, hdr, ranges + (size_t)v * T,
-                         point_list, rec + (size_t)v * P, background, out_color + (size_t)v * F3DG_OUT_CHANNELS * HW, final_T + (size_t)v * 4 * HW,
-                         n_contrib + (size_t)v * 2 * HW, contrib_ids + (size_t)v * HW * F3DG_MAX_CONTRIB, contrib_n + (size_t)v * HW);
-    } else {
-        // 545 shared rays per tile, then the per-pixel kernel on the tiles that hit the contributor limit (normally none)
+    // default: 545 shared rays per tile, then the plain kernel on the tiles that hit the contributor limit (normally none).
+    // reference_kernels: the plain kernel on every tile
+    const unsigned* only = nullptr;
+    if (!g_f3dg_reference_kernels) {
         unsigned* redo = reinterpret_cast<unsigned*>(ws + I.redo);
         F3DG_KLAUNCH(integrate_pass1_rays_kernel, dim3((unsigned)V * (unsigned)T), dim3(F3DG_RAYS_THREADS), 0, s, V, P, T, W, H, tiles_x, focal_x, focal_y,
                            hdr, ranges, point_list, rec, reinterpret_cast<const float4*>(ws + L.cull), background,
                            out_color, final_T, n_contrib, contrib_ids, contrib_n, redo);
-        F3DG_KLAUNCH(integrate_pass1_cull_kernel, dim3((unsigned)V * (unsigned)T), dim3(F3DG_BLOCK), 0, s, V, P, T, W, H, tiles_x, focal_x, focal_y,
-                           hdr, ranges, point_list, rec, reinterpret_cast<const float4*>(ws + L.cull), background,
-                           out_color, final_T, n_contrib, contrib_ids, contrib_n, redo);
+        only = redo;
     }
+    F3DG_KLAUNCH(integrate_pass1_kernel, dim3((unsigned)V * (unsigned)T), dim3(F3DG_BLOCK), 0, s, V, P, T, W, H, tiles_x, focal_x, focal_y,
+                       hdr, ranges, point_list, rec, background, out_color, final_T, n_contrib, contrib_ids, contrib_n, only);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }

@@ -258,8 +258,9 @@ int f3dg_integrate_points_view(void* stream, void* workspace, size_t workspace_b
                                float* out_alpha_integrated, float* out_color_integrated, float* alpha_min);
 
 /* Diagnostic, BLOCKING: how many (camera, tile) pairs of the last preparation on this workspace reached the reference's limit of 1,024
- * contributors in some pixel (forward.cu:972-976) and were therefore computed by the per-pixel kernel behind the shared-ray kernel
- * (f3dg_integrate.hip: integrate_pass1_rays_kernel). Same shape arguments as the preparation. */
+ * contributors in some pixel (forward.cu:972-976) and were therefore computed again, one pixel per lane, by the plain transcription
+ * (f3dg_integrate.hip: integrate_pass1_kernel, launched behind integrate_pass1_rays_kernel on the flagged tiles only). Same shape
+ * arguments as the preparation. */
 int f3dg_debug_integrate_redo(void* stream, const void* workspace, int P, int PN_max, int W, int H, int n_views, long long max_rendered,
                               int* h_tiles);
 
@@ -402,7 +403,8 @@ int f3dg_residual_join_f16(void* stream, int N, int C, int HW, int nhwc, const u
  *                   (default 0) 1 = the compositing forward and pass 1 of f3dg_integrate take the plain transcriptions of the reference
  *                   (render_fwd_kernel, integrate_pass1_kernel: every pixel visits every entry of its tile's list, nothing is filtered) in
  *                   the reference's arithmetic whatever the call's flags say, and no call takes the small-call path. The baseline the
- *                   tests hold every other compositing path to, bit for bit; slow.
+ *                   tests hold every other compositing path to, bit for bit; slow. (integrate_pass1_kernel is also what the default path
+ *                   runs on the tiles f3dg_debug_integrate_redo counts.)
  * Any other name is F3DG_ERR_BAD_ARG, among them the switches of the kernel generations that were measured and retired (NOTES.md has
  * their measurements). */
 int f3dg_set_option(const char* name, int value);
@@ -442,8 +444,6 @@ int f3dg_debug_render5_counts(unsigned long long* h_out, int reset);
  * evaluators, producer } x { total, waiting at the window barrier, waiting for a round counter, windows, rounds, waves }; row 3 =
  * the longest { consumer, evaluator, producer } wave of any workgroup. */
 int f3dg_debug_render3q_clocks(unsigned long long* h_out);
-/* Diagnostic (tools/pmc_pass1.sh): resident workgroups per CU of the two pass-1 kernels of f3dg_integrate as the runtime computes it. */
-int f3dg_debug_pass1_occupancy(int* rays_blocks, int* cull_blocks);
 
 /* BLOCKING: number of contributing (pixel, Gaussian) pairs the last f3dg_backward on this workspace blended back through --
  * "C" of the byte formula 80 R + 60 W H + 68 C of the compositing backward. */

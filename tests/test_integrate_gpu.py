@@ -48,7 +48,7 @@ def test_integrate_matches_oracle(name):
                                 dict(P=60000, res=(64, 64), s0=0.004, view="canonical")],               # sub-pixel splats
                          ids=["mid", "large_aniso", "tiny"])
 def test_integrate_filters_are_bit_identical(kw):
-    """The filters of pass 1 (545 shared rays per tile, the per-pixel ellipse test) only remove (ray, Gaussian) pairs the reference
+    """The filters of pass 1 (545 shared rays per tile, the conservative ellipse test at the ray positions) only remove (ray, Gaussian) pairs the reference
     `continue`s on: the default pass must match the plain transcription (option reference_kernels) bit for bit."""
     scene = make_scene(**kw)
     pts = make_points(scene, 50000)
@@ -66,7 +66,7 @@ def test_integrate_filters_are_bit_identical(kw):
 
 def test_contributor_limit_tiles_are_redone_per_pixel():
     """Pixels that reach the reference's 1,024 contributors (forward.cu:972-976) stop there while the rays they share with their
-    neighbours go on: the shared-ray kernel hands such tiles to the per-pixel kernel. Thousands of nearly transparent, large
+    neighbours go on: the shared-ray kernel hands such tiles to the plain per-pixel kernel. Thousands of nearly transparent, large
     splats per pixel; the result must be the plain transcription's bit for bit and the oracle's within tolerance."""
     import ctypes as C
     from f3dgaus_amd.diff_gof_rasterization import GaussianRasterizationSettings_GOF, integrate_prepare

@@ -137,7 +137,7 @@ def main():
         st = glob.glob(os.path.join(src, "p1_stats", "*kernel_stats.csv"))
         if st:
             out += ["rocprofv3 --kernel-trace --stats of `python tools/prof_pass1.py` (three preparations of 16 cameras of 589,824 Gaussians; "
-                    "integrate_pass1_cull_kernel behind the ray kernel only computes tiles that reached 1,024 contributors: none here):", ""] + kernel_table(st[0], 6) + [""]
+                    "integrate_pass1_kernel behind the ray kernel only computes tiles that reached 1,024 contributors: none here):", ""] + kernel_table(st[0], 6) + [""]
         rows = {}
         for d in ("sq1", "sq2"):
             f = glob.glob(os.path.join(src, "p1_pmc", d, "*counter_collection.csv"))
@@ -148,7 +148,7 @@ def main():
         if rows:
             m = {k: sum(v) / len(v) for k, v in rows.items()}
             out += ["`integrate_pass1_rays_kernel`, SQ counters per 16-camera launch (rocprofv3 --pmc, PMC-only passes; round 2's "
-                    "integrate_pass1_cull_kernel on the same input: SQ_INSTS_VALU 9.0e9, SQ_INSTS_VALU_MUL_F64 2.46e8, lane utilisation 0.58, 13.4 ms):", "",
+                    "per-pixel kernel with the ellipse filter, since retired, on the same input: SQ_INSTS_VALU 9.0e9, SQ_INSTS_VALU_MUL_F64 2.46e8, lane utilisation 0.58, 13.4 ms):", "",
                     "| counter | value |", "|---|---:|"] + [f"| {k} | {v:.4g} |" for k, v in sorted(m.items())]
             if m.get("SQ_ACTIVE_INST_VALU"):
                 out += [f"| VALU lane utilisation = SQ_THREAD_CYCLES_VALU / (64 SQ_ACTIVE_INST_VALU) | {m.get('SQ_THREAD_CYCLES_VALU', 0) / (64 * m['SQ_ACTIVE_INST_VALU']):.2f} |"]

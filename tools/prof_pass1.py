@@ -1,5 +1,5 @@
 """AlphaSweep preparation (f3dg_integrate_prepare_batched) of 16 cameras of 589,824 Gaussians in a loop, for rocprofv3 runs on
-integrate_pass1_cull_kernel (tools/pmc_pass1.sh). Prints the time per camera."""
+the pass-1 kernels of integrate (tools/pmc_pass1.sh). Prints the time per camera."""
 import os
 import sys
 import time
