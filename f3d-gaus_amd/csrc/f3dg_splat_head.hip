@@ -9,11 +9,53 @@
 // chain of the cycle loop (visualize.py:336-340) -- ~15 small torch kernels + permutes + 9 reallocations become
 // one bandwidth-bound pass: 96 B read + 96 B written per Gaussian.
 //
+// splat_head_backward_kernel is its vector-Jacobian product with respect to net_out and depth (what torch.autograd derives from those
+// same reference lines): the same grid, the forward's intermediates recomputed through shared __device__ helpers, no saved state, no atomics.
+//
 // epilogue_kernel fuses the post-processing of render_predicted_more_v2_gof
 // (src/gaussian_renderer/__init__.py:1043-1053 world normals, :881-909 depth_to_normal).
 #include "f3dg_common.h"
 
 namespace {
+
+// ---- per-pixel arithmetic shared by splat_head_kernel and splat_head_backward_kernel: the backward saves nothing and recomputes the
+// forward's intermediates with these very float32 expressions
+struct SplatPos { float den, X, Y, Z; };       // perspective divide, BEFORE the squre_clip clamp
+
+__device__ __forceinline__ SplatPos splat_position(const float* __restrict__ net, const float* __restrict__ ray_dirs,
+                                                   const float* __restrict__ M, int HW, int n, float d)
+{
+    // pos = ray_dirs * depth + offset  (two roundings, as torch evaluates it)
+    const float p0 = ray_dirs[n] * d + net[0 * HW];
+    const float p1 = ray_dirs[HW + n] * d + net[1 * HW];
+    const float p2 = ray_dirs[2 * HW + n] * d + net[2 * HW];
+    // [p,1] @ M
+    const float w0 = p0 * M[0] + p1 * M[4] + p2 * M[8] + M[12];
+    const float w1 = p0 * M[1] + p1 * M[5] + p2 * M[9] + M[13];
+    const float w2 = p0 * M[2] + p1 * M[6] + p2 * M[10] + M[14];
+    const float w3 = p0 * M[3] + p1 * M[7] + p2 * M[11] + M[15];
+    SplatPos r;
+    r.den = w3 + 1e-10f;
+    r.X = w0 / r.den; r.Y = w1 / r.den; r.Z = w2 / r.den;
+    return r;
+}
+
+__device__ __forceinline__ float splat_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// |q| before F.normalize's clamp_min(1e-12)
+__device__ __forceinline__ float splat_quat_norm(float bw, float bx, float by, float bz)
+{
+    return sqrtf(bw * bw + bx * bx + by * by + bz * bz);
+}
+
+// T = sh_to_v @ R @ v_to_sh with R = M[:3,:3]; the two constant matrices are signed permutations:
+//   X = sh_to_v @ R : rows (-R[1], R[2], -R[0]);   T[i] = (-X[i][1], X[i][2], -X[i][0])
+__device__ __forceinline__ void splat_sh_matrix(const float* __restrict__ M, float Tm[3][3])
+{
+    const float Xr[3][3] = { { -M[4], -M[5], -M[6] }, { M[8], M[9], M[10] }, { -M[0], -M[1], -M[2] } };
+#pragma unroll
+    for (int i = 0; i < 3; i++) { Tm[i][0] = -Xr[i][1]; Tm[i][1] = Xr[i][2]; Tm[i][2] = -Xr[i][0]; }
+}
 
 __global__ void __launch_bounds__(F3DG_BLOCK)
 splat_head_kernel(int HW, const float* __restrict__ net_out, const float* __restrict__ depth,
@@ -31,18 +73,9 @@ splat_head_kernel(int HW, const float* __restrict__ net_out, const float* __rest
     const float* qc = cam_quat + 4 * b;
 
     const float d = depth[(size_t)b * HW + n];
-    // pos = ray_dirs * depth + offset  (two roundings, as torch evaluates it)
-    const float p0 = ray_dirs[n] * d + net[0 * HW];
-    const float p1 = ray_dirs[HW + n] * d + net[1 * HW];
-    const float p2 = ray_dirs[2 * HW + n] * d + net[2 * HW];
-    // [p,1] @ M
-    const float w0 = p0 * M[0] + p1 * M[4] + p2 * M[8] + M[12];
-    const float w1 = p0 * M[1] + p1 * M[5] + p2 * M[9] + M[13];
-    const float w2 = p0 * M[2] + p1 * M[6] + p2 * M[10] + M[14];
-    const float w3 = p0 * M[3] + p1 * M[7] + p2 * M[11] + M[15];
-    const float den = w3 + 1e-10f;
-    float X = w0 / den, Y = w1 / den;
-    const float Z = w2 / den;
+    const SplatPos pos = splat_position(net, ray_dirs, M, HW, n, d);
+    float X = pos.X, Y = pos.Y;
+    const float Z = pos.Z;
     if (squre_clip < 10.0f) {
         X = fminf(fmaxf(X, -squre_clip), squre_clip);
         Y = fminf(fmaxf(Y, -squre_clip), squre_clip);
@@ -51,14 +84,14 @@ splat_head_kernel(int HW, const float* __restrict__ net_out, const float* __rest
     const size_t o = (size_t)b * (size_t)n_total + (size_t)n_offset + n;
     xyz[3 * o + 0] = X; xyz[3 * o + 1] = Y; xyz[3 * o + 2] = Z;
 
-    opacity[o] = 1.0f / (1.0f + expf(-net[3 * HW]));
+    opacity[o] = splat_sigmoid(net[3 * HW]);
     scaling[3 * o + 0] = expf(net[4 * HW]);
     scaling[3 * o + 1] = expf(net[5 * HW]);
     scaling[3 * o + 2] = expf(net[6 * HW]);
 
     // F.normalize(dim=channel, eps=1e-12) then Hamilton product cam_quat (x) q, real part first
     float bw = net[7 * HW], bx = net[8 * HW], by = net[9 * HW], bz = net[10 * HW];
-    const float nrm = fmaxf(sqrtf(bw * bw + bx * bx + by * by + bz * bz), 1e-12f);
+    const float nrm = fmaxf(splat_quat_norm(bw, bx, by, bz), 1e-12f);
     bw /= nrm; bx /= nrm; by /= nrm; bz /= nrm;
     const float aw = qc[0], ax = qc[1], ay = qc[2], az = qc[3];
     rotation[4 * o + 0] = aw * bw - ax * bx - ay * by - az * bz;
@@ -70,14 +103,8 @@ splat_head_kernel(int HW, const float* __restrict__ net_out, const float* __rest
     features_dc[3 * o + 1] = net[12 * HW];
     features_dc[3 * o + 2] = net[13 * HW];
 
-    // T = sh_to_v @ R @ v_to_sh with R = M[:3,:3]; the two constant matrices are signed permutations:
-    //   X = sh_to_v @ R : rows (-R[1], R[2], -R[0]);   T[i] = (-X[i][1], X[i][2], -X[i][0])
     float Tm[3][3];
-    {
-        const float Xr[3][3] = { { -M[4], -M[5], -M[6] }, { M[8], M[9], M[10] }, { -M[0], -M[1], -M[2] } };
-#pragma unroll
-        for (int i = 0; i < 3; i++) { Tm[i][0] = -Xr[i][1]; Tm[i][1] = Xr[i][2]; Tm[i][2] = -Xr[i][0]; }
-    }
+    splat_sh_matrix(M, Tm);
     // rest'[t][c] = sum_s rest[s][c] * T[s][t], rest channel index = 14 + 3*s + c
 #pragma unroll
     for (int c = 0; c < 3; c++) {
@@ -87,6 +114,106 @@ splat_head_kernel(int HW, const float* __restrict__ net_out, const float* __rest
             features_rest[9 * o + 3 * t + c] = s0 * Tm[0][t] + s1 * Tm[1][t] + s2 * Tm[2][t];
     }
     unet_depth[o] = d;
+}
+
+// Backward of splat_head_kernel with respect to net_out and depth (the cameras and ray_dirs are data): one thread per (image, pixel),
+// the same grid. A Gaussian's seven outputs depend on that pixel's 23 + 1 inputs only, so there is nothing to reduce: no atomics, no
+// LDS, no saved state -- the forward's intermediates are recomputed from net_out / depth through the helpers above. A NULL g_* counts as
+// all-zero upstream gradient; every element of d_net_out (and of d_depth unless NULL) is written.
+__global__ void __launch_bounds__(F3DG_BLOCK)
+splat_head_backward_kernel(int HW, const float* __restrict__ net_out, const float* __restrict__ depth,
+                           const float* __restrict__ ray_dirs, const float* __restrict__ view_to_world,
+                           const float* __restrict__ cam_quat, float squre_clip, long long n_total, long long n_offset,
+                           const float* __restrict__ g_xyz, const float* __restrict__ g_opacity, const float* __restrict__ g_scaling,
+                           const float* __restrict__ g_rotation, const float* __restrict__ g_features_dc,
+                           const float* __restrict__ g_features_rest, const float* __restrict__ g_unet_depth,
+                           float* __restrict__ d_net_out, float* __restrict__ d_depth)
+{
+    const int n = blockIdx.x * F3DG_BLOCK + threadIdx.x;
+    const int b = blockIdx.y;
+    if (n >= HW) return;
+    const float* net = net_out + (size_t)b * 23 * HW + n;
+    float* dnet = d_net_out + (size_t)b * 23 * HW + n;
+    const float* M = view_to_world + 16 * b;
+    const float* qc = cam_quat + 4 * b;
+    const size_t o = (size_t)b * (size_t)n_total + (size_t)n_offset + n;
+
+    // ---- position (gaussian_predictor.py:879, :961-970)
+    float dp0 = 0.0f, dp1 = 0.0f, dp2 = 0.0f;
+    if (g_xyz) {
+        const SplatPos pos = splat_position(net, ray_dirs, M, HW, n, depth[(size_t)b * HW + n]);
+        float gX = g_xyz[3 * o + 0], gY = g_xyz[3 * o + 1];
+        const float gZ = g_xyz[3 * o + 2];
+        if (squre_clip < 10.0f) {       // clamp_ passes the gradient where -c <= x <= c
+            if (!(pos.X >= -squre_clip && pos.X <= squre_clip)) gX = 0.0f;
+            if (!(pos.Y >= -squre_clip && pos.Y <= squre_clip)) gY = 0.0f;
+        }
+        const float dw0 = gX / pos.den, dw1 = gY / pos.den, dw2 = gZ / pos.den;
+        const float dw3 = -(gX * pos.X + gY * pos.Y + gZ * pos.Z) / pos.den;
+        dp0 = M[0] * dw0 + M[1] * dw1 + M[2] * dw2 + M[3] * dw3;
+        dp1 = M[4] * dw0 + M[5] * dw1 + M[6] * dw2 + M[7] * dw3;
+        dp2 = M[8] * dw0 + M[9] * dw1 + M[10] * dw2 + M[11] * dw3;
+    }
+    dnet[0 * HW] = dp0; dnet[1 * HW] = dp1; dnet[2 * HW] = dp2;
+    if (d_depth) {
+        const float gd = g_unet_depth ? g_unet_depth[o] : 0.0f;
+        d_depth[(size_t)b * HW + n] = ray_dirs[n] * dp0 + ray_dirs[HW + n] * dp1 + ray_dirs[2 * HW + n] * dp2 + gd;
+    }
+
+    // ---- opacity: sigmoid (:975)
+    float dop = 0.0f;
+    if (g_opacity) {
+        const float s = splat_sigmoid(net[3 * HW]);
+        dop = g_opacity[o] * s * (1.0f - s);
+    }
+    dnet[3 * HW] = dop;
+
+    // ---- scaling: exp (:976)
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+        dnet[(4 + c) * HW] = g_scaling ? g_scaling[3 * o + c] * expf(net[(4 + c) * HW]) : 0.0f;
+
+    // ---- rotation: transpose of the Hamilton product cam_quat (x) q (:45-64, :839-855), then F.normalize (:977)
+    float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f, d3 = 0.0f;
+    if (g_rotation) {
+        const float g0 = g_rotation[4 * o + 0], g1 = g_rotation[4 * o + 1], g2 = g_rotation[4 * o + 2], g3 = g_rotation[4 * o + 3];
+        const float aw = qc[0], ax = qc[1], ay = qc[2], az = qc[3];
+        const float q0 = g0 * aw + g1 * ax + g2 * ay + g3 * az;
+        const float q1 = -g0 * ax + g1 * aw + g2 * az - g3 * ay;
+        const float q2 = -g0 * ay - g1 * az + g2 * aw + g3 * ax;
+        const float q3 = -g0 * az + g1 * ay - g2 * ax + g3 * aw;
+        const float bw = net[7 * HW], bx = net[8 * HW], by = net[9 * HW], bz = net[10 * HW];
+        const float raw = splat_quat_norm(bw, bx, by, bz);
+        if (raw >= 1e-12f) {
+            const float hw = bw / raw, hx = bx / raw, hy = by / raw, hz = bz / raw;
+            const float dot = hw * q0 + hx * q1 + hy * q2 + hz * q3;
+            d0 = (q0 - hw * dot) / raw; d1 = (q1 - hx * dot) / raw; d2 = (q2 - hy * dot) / raw; d3 = (q3 - hz * dot) / raw;
+        } else {                        // clamp_min(1e-12) is active: the norm gets no gradient
+            d0 = q0 / 1e-12f; d1 = q1 / 1e-12f; d2 = q2 / 1e-12f; d3 = q3 / 1e-12f;
+        }
+    }
+    dnet[7 * HW] = d0; dnet[8 * HW] = d1; dnet[9 * HW] = d2; dnet[10 * HW] = d3;
+
+    // ---- features_dc: pass-through (:978)
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+        dnet[(11 + c) * HW] = g_features_dc ? g_features_dc[3 * o + c] : 0.0f;
+
+    // ---- features_rest (:821-837): d_rest[s][c] = sum_t g[t][c] * T[s][t]
+    if (g_features_rest) {
+        float Tm[3][3];
+        splat_sh_matrix(M, Tm);
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float t0 = g_features_rest[9 * o + 0 + c], t1 = g_features_rest[9 * o + 3 + c], t2 = g_features_rest[9 * o + 6 + c];
+#pragma unroll
+            for (int s = 0; s < 3; s++)
+                dnet[(14 + 3 * s + c) * HW] = t0 * Tm[s][0] + t1 * Tm[s][1] + t2 * Tm[s][2];
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 9; c++) dnet[(14 + c) * HW] = 0.0f;
+    }
 }
 
 // inverse of a 4x4 (row-major) by cofactors in float64, rounded to float32 (the camera-to-world matrix of the epilogue: one thread)
@@ -262,6 +389,25 @@ extern "C" int f3dg_splat_head(void* stream, int B, int H, int W, const float* n
     F3DG_KLAUNCH(splat_head_kernel, grid, dim3(F3DG_BLOCK), 0, (hipStream_t)stream, (int)HW, net_out, depth,
                        ray_dirs, view_to_world, cam_quat, squre_clip, n_total, n_offset, xyz, opacity, scaling,
                        rotation, features_dc, features_rest, unet_depth);
+    F3DG_HIP_CHECK(hipGetLastError());
+    return F3DG_OK;
+}
+
+extern "C" int f3dg_splat_head_backward(void* stream, int B, int H, int W, const float* net_out, const float* depth,
+                                        const float* ray_dirs, const float* view_to_world, const float* cam_quat,
+                                        float squre_clip, long long n_total, long long n_offset,
+                                        const float* g_xyz, const float* g_opacity, const float* g_scaling, const float* g_rotation,
+                                        const float* g_features_dc, const float* g_features_rest, const float* g_unet_depth,
+                                        float* d_net_out, float* d_depth)
+{
+    if (B <= 0 || H <= 0 || W <= 0 || !net_out || !depth || !ray_dirs || !view_to_world || !cam_quat || !d_net_out)
+        return F3DG_ERR_BAD_ARG;
+    const long long HW = (long long)H * W;
+    if (n_offset < 0 || n_total < n_offset + HW) return F3DG_ERR_BAD_ARG;
+    dim3 grid((unsigned)((HW + F3DG_BLOCK - 1) / F3DG_BLOCK), (unsigned)B);
+    F3DG_KLAUNCH(splat_head_backward_kernel, grid, dim3(F3DG_BLOCK), 0, (hipStream_t)stream, (int)HW, net_out, depth,
+                       ray_dirs, view_to_world, cam_quat, squre_clip, n_total, n_offset, g_xyz, g_opacity, g_scaling,
+                       g_rotation, g_features_dc, g_features_rest, g_unet_depth, d_net_out, d_depth);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }

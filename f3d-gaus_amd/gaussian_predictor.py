@@ -15,6 +15,8 @@ What is different by design (MI355X-first):
     composition, SH rotation, NCHW -> N x C flattening, multi-view union -- is libf3dg_hip's ``f3dg_splat_head``
     (one pass, 96 B read + 96 B written per Gaussian) instead of ~15 torch kernels and permute copies;
   * ``forward(..., out=, n_offset=)`` lets the cycle loop write each pass straight into the aggregated buffers;
+  * under autograd the head is a ``torch.autograd.Function`` over ``f3dg_splat_head_backward``, so the rasterizer's gradients reach
+    the network (``net_out``, ``unet_depth``); the cameras and ``ray_dirs`` get none, and ``out=`` stays an inference form;
   * the backbone's x2 up / down resampling uses nearest-upsample / 2x2 mean (identical maths to the reference's
     depthwise [1,1] filter convolutions) and the 1-head attention uses scaled_dot_product_attention.
 """
@@ -353,10 +355,54 @@ def allocate_gaussians(B, N, device):
     return {k: torch.empty((B, N) + _KEY_SHAPE[k], dtype=torch.float32, device=device) for k in GAUSSIAN_KEYS}
 
 
+def _splat_head_call(net_out, depth, ray_dirs, v2w, quat, squre_clip, out, n_total, n_offset):
+    """The raw kernel call on prepared (contiguous float32, same device) tensors."""
+    B, _, H, W = net_out.shape
+    rc = _lib.lib().f3dg_splat_head(
+        _stream(), B, H, W, _lib.ptr(net_out), _lib.ptr(depth), _lib.ptr(ray_dirs), _lib.ptr(v2w), _lib.ptr(quat),
+        float(squre_clip), int(n_total), int(n_offset), *[_lib.ptr(out[k]) for k in GAUSSIAN_KEYS])
+    _lib.check(rc, "f3dg_splat_head")
+    return out
+
+
+class _SplatHead(torch.autograd.Function):
+    """``f3dg_splat_head`` with ``f3dg_splat_head_backward`` behind it. Only the inputs are saved: the backward kernel recomputes the
+    forward's intermediates. Gradients reach ``net_out`` and ``depth``; the cameras and ``ray_dirs`` are data (``splat_head`` refuses
+    them when they require grad)."""
+
+    @staticmethod
+    def forward(ctx, net_out, depth, ray_dirs, v2w, quat, squre_clip):
+        B, _, H, W = net_out.shape
+        ctx.set_materialize_grads(False)        # an unused output arrives in backward as None, not as a zero tensor
+        out = allocate_gaussians(B, H * W, net_out.device)
+        _splat_head_call(net_out, depth, ray_dirs, v2w, quat, squre_clip, out, H * W, 0)
+        ctx.save_for_backward(net_out, depth, ray_dirs, v2w, quat)
+        ctx.squre_clip = float(squre_clip)
+        return tuple(out[k] for k in GAUSSIAN_KEYS)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        net_out, depth, ray_dirs, v2w, quat = ctx.saved_tensors
+        B, _, H, W = net_out.shape
+        # a None cotangent ("this output was not used") goes to the kernel as NULL; expanded / strided ones are made dense
+        gs = [None if g is None else g.to(device=net_out.device, dtype=torch.float32).contiguous() for g in grads]
+        d_net = torch.empty_like(net_out)
+        d_depth = torch.empty_like(depth) if ctx.needs_input_grad[1] else None
+        rc = _lib.lib().f3dg_splat_head_backward(
+            _stream(), B, H, W, _lib.ptr(net_out), _lib.ptr(depth), _lib.ptr(ray_dirs), _lib.ptr(v2w), _lib.ptr(quat),
+            ctx.squre_clip, H * W, 0, *[_lib.ptr(g) for g in gs], _lib.ptr(d_net), _lib.ptr(d_depth))
+        _lib.check(rc, "f3dg_splat_head_backward")
+        return (d_net if ctx.needs_input_grad[0] else None), d_depth, None, None, None, None
+
+
 def splat_head(net_out, depth, ray_dirs, view_to_world, cam_quat, squre_clip=10000.0, out=None, n_offset=0):
     """Fused cycle-aggregative projection (f3dg_splat_head). net_out [B,23,H,W], depth [B,1,H,W], ray_dirs [1,3,H,W],
     view_to_world [B,4,4] (row-vector convention), cam_quat [B,4]. Writes image b's H*W Gaussians at
-    ``out[key][b, n_offset : n_offset + H*W]`` (allocating [B,H*W,...] buffers when ``out`` is None)."""
+    ``out[key][b, n_offset : n_offset + H*W]`` (allocating [B,H*W,...] buffers when ``out`` is None).
+
+    Differentiable in ``net_out`` and ``depth`` (f3dg_splat_head_backward) when grad mode is on and one of them requires grad; the
+    cameras and ``ray_dirs`` get no gradient, and the in-place form (``out=``) is for inference only."""
     B, Cc, H, W = net_out.shape
     if Cc != 23:
         raise RuntimeError("splat head expects the 23-channel with-offset / SH-degree-1 layout [3,1,3,4,3,9]")
@@ -364,21 +410,29 @@ def splat_head(net_out, depth, ray_dirs, view_to_world, cam_quat, squre_clip=100
     if device.type != "cuda":
         raise RuntimeError("f3dgaus_amd splat head needs tensors on a HIP device (no CPU fallback)")
     HW = H * W
-    if out is None:
-        out = allocate_gaussians(B, HW, device)
-    n_total = out["xyz"].shape[1]
+    grad_on = torch.is_grad_enabled()
+    if grad_on:
+        for name, t in (("ray_dirs", ray_dirs), ("view_to_world", view_to_world), ("cam_quat", cam_quat)):
+            if t.requires_grad:
+                raise NotImplementedError(f"the splat head produces no gradient for `{name}` (cameras and ray directions are data in "
+                                          "every caller): detach it")
+    differentiable = grad_on and (net_out.requires_grad or depth.requires_grad)
+    if differentiable and out is not None:
+        raise RuntimeError("splat_head(out=...) writes into preallocated buffers and is an inference form: it cannot carry the "
+                           "autograd graph of a `net_out` / `depth` that requires grad (call it under torch.no_grad(), or without out=)")
     f = lambda t: t.to(device=device, dtype=torch.float32).contiguous()
     net_out, depth, ray_dirs = f(net_out), f(depth), f(ray_dirs)
     v2w, quat = f(view_to_world).reshape(B, 16), f(cam_quat).reshape(B, 4)
+    if differentiable:
+        return dict(zip(GAUSSIAN_KEYS, _SplatHead.apply(net_out, depth, ray_dirs, v2w, quat, float(squre_clip))))
+    if out is None:
+        out = allocate_gaussians(B, HW, device)
+    n_total = out["xyz"].shape[1]
     for k in GAUSSIAN_KEYS:
         t = out[k]
         if not (t.is_contiguous() and t.dtype == torch.float32 and t.shape[0] == B and t.shape[1] == n_total):
             raise RuntimeError(f"aggregated buffer '{k}' must be contiguous float32 [B, n_total, ...]")
-    rc = _lib.lib().f3dg_splat_head(
-        _stream(), B, H, W, _lib.ptr(net_out), _lib.ptr(depth), _lib.ptr(ray_dirs), _lib.ptr(v2w), _lib.ptr(quat),
-        float(squre_clip), int(n_total), int(n_offset), *[_lib.ptr(out[k]) for k in GAUSSIAN_KEYS])
-    _lib.check(rc, "f3dg_splat_head")
-    return out
+    return _splat_head_call(net_out, depth, ray_dirs, v2w, quat, squre_clip, out, n_total, n_offset)
 
 
 class GaussianSplatPredictor_gtunet(nn.Module):

@@ -26,6 +26,8 @@
  *   f3dg_splat_head
  *       the post-network half of GaussianSplatPredictor_gtunet.forward   src/gaussian_predictor.py:857-881, 961-1007
  *       (python-only in the reference; there is no native FFI for it -- this is the build's fused kernel)
+ *   f3dg_splat_head_backward
+ *       what torch.autograd derives from those same lines                src/gaussian_predictor.py:857-881, 961-1002
  *   f3dg_render_epilogue
  *       the torch post-processing of render_predicted_more_v2_gof  src/gaussian_renderer/__init__.py:881-909, 1043-1053
  *
@@ -282,6 +284,26 @@ int f3dg_splat_head(void* stream, int B, int H, int W, const float* net_out, con
                     long long n_total, long long n_offset,
                     float* xyz, float* opacity, float* scaling, float* rotation,
                     float* features_dc, float* features_rest, float* unet_depth);
+
+/* Backward of f3dg_splat_head with respect to net_out and depth: the vector-Jacobian product that torch.autograd derives from the
+ * reference's differentiable lines (src/gaussian_predictor.py:857-881 back-projection, :961-970 bmm / perspective divide / clamp_,
+ * :975-979 sigmoid / exp / F.normalize / flatten, :839-855 with :45-64 quaternion product, :821-837 transform_SHs, :991-994).
+ * The first twelve arguments are those of f3dg_splat_head. Nothing is saved by the forward: the kernel recomputes its intermediates
+ * from net_out / depth with the forward's own float32 expressions (one thread per (image, pixel), no atomics: bit-reproducible).
+ *   g_xyz, g_opacity, g_scaling, g_rotation, g_features_dc, g_features_rest, g_unet_depth: upstream gradients in the layout of the
+ *       forward's outputs, [B,n_total,...] with image b's rows at n_offset .. n_offset + H*W; rows outside that window are never
+ *       read. Each may be NULL = "this output was not used": all of its entries count as zero.
+ *   d_net_out [B,23,H,W]: every element is written (no accumulation, the caller need not zero it).
+ *   d_depth   [B,1,H,W]:  every element is written; NULL skips it.
+ * squre_clip < 10: x / y receive no gradient where the forward clamped them (clamp_ passes it where -c <= x <= c).
+ * view_to_world, cam_quat and ray_dirs are data: no gradients are produced for them.
+ * F3DG_ERR_BAD_ARG: a NULL required pointer (the five inputs, d_net_out), non-positive sizes, n_offset < 0 or n_total < n_offset + H*W. */
+int f3dg_splat_head_backward(void* stream, int B, int H, int W, const float* net_out, const float* depth,
+                             const float* ray_dirs, const float* view_to_world, const float* cam_quat, float squre_clip,
+                             long long n_total, long long n_offset,
+                             const float* g_xyz, const float* g_opacity, const float* g_scaling, const float* g_rotation,
+                             const float* g_features_dc, const float* g_features_rest, const float* g_unet_depth,
+                             float* d_net_out, float* d_depth);
 
 /* Fused epilogue of render_predicted_more_v2_gof (gaussian_renderer/__init__.py:881-909, 1043-1053) for n_views
  * rendered frames raster [n_views,9,H,W]:
