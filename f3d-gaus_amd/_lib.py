@@ -9,7 +9,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libf3dg_hip.so")
 
 OK, ERR_BAD_ARG, ERR_WORKSPACE, ERR_OVERFLOW, ERR_HIP, ERR_UNSUPPORTED, ERR_STATE = 0, -1, -2, -3, -4, -5, -6
 FLAG_SAVE_AUX, FLAG_BG_PER_VIEW, FLAG_SKIP_NORMAL, FLAG_SKIP_DISTORTION = 1, 2, 4, 8
-FLAG_EXACT, FLAG_FAST, FLAG_NO_TILE_CULL, FLAG_NO_SMALL_PATH, FLAG_SCAN = 16, 32, 64, 128, 256
+FLAG_EXACT, FLAG_FAST, FLAG_NO_TILE_CULL, FLAG_NO_SMALL_PATH, FLAG_SCAN, FLAG_SETS_AUX = 16, 32, 64, 128, 256, 512
 PENDING = 1
 
 _ERR_TEXT = {
@@ -39,6 +39,9 @@ SIGNATURES = {
                            _f, _f, _f, _i, _p, _p, _u, C.POINTER(_ll)]),
     "f3dg_backward": (_i, [_p, _p, _sz, _ll, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _p,
                            _f, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _u]),
+    # as f3dg_backward with (n_sets, views_per_set) in place of n_views
+    "f3dg_backward_sets": (_i, [_p, _p, _sz, _ll, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _p,
+                                _f, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _u]),
     "f3dg_integrate_workspace_bytes": (_sz, [_i, _i, _i, _i, _ll]),
     # stream, ws, ws_bytes, cap | PN P D M | bg W H | points3D means3D shs colors opac scales | mod | rot cov3D v2g view
     # proj campos | tanx tany ks | subpix | prefiltered | out_color radii alpha_i color_i | h_needed
@@ -57,6 +60,7 @@ SIGNATURES = {
     "f3dg_splat_head_backward": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _f, _ll, _ll, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "f3dg_render_epilogue": (_i, [_p, _i, _i, _i, _p, _p, _f, _f, _p, _p]),
     "f3dg_render_epilogue_view": (_i, [_p, _i, _i, _i, _p, _p, _f, _f, _p, _p]),
+    "f3dg_render_epilogue_backward": (_i, [_p, _i, _i, _i, _p, _p, _f, _f, _p, _p, _p]),
     "f3dg_cycle_inputs": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
     "f3dg_pack_frames": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "f3dg_pack_frames_host": (_i, [_p, _i, _i, _i, _i, _p, _p, _i]),

@@ -387,9 +387,10 @@ extern "C" int f3dg_forward_sets(void* stream, void* workspace, size_t workspace
     const size_t HW = (size_t)W * H;
 
     const int save_aux = (flags & F3DG_FLAG_SAVE_AUX) ? 1 : 0;
-    // several Gaussian sets in one call are an inference path: f3dg_backward and the per-Gaussian backward index the Gaussian inputs
-    // without a set offset, and view2gaussian_precomp is [n_views, P, 10] of ONE set
-    if (n_sets > 1 && (save_aux || view2gaussian_precomp != nullptr)) return F3DG_ERR_BAD_ARG;
+    // several Gaussian sets in one call keep the auxiliary planes only on the caller's promise (F3DG_FLAG_SETS_AUX) that f3dg_backward_sets
+    // follows: f3dg_backward indexes the Gaussian inputs of ONE set. view2gaussian_precomp is [n_views, P, 10] of ONE set
+    if ((flags & F3DG_FLAG_SETS_AUX) && !save_aux) return F3DG_ERR_BAD_ARG;
+    if (n_sets > 1 && ((save_aux && !(flags & F3DG_FLAG_SETS_AUX)) || view2gaussian_precomp != nullptr)) return F3DG_ERR_BAD_ARG;
     // small-call path (f3dg_small.hip): inference calls of one or two views of a modest set go projection -> per-tile sort -> compositing
     // what this call runs with: the process-wide defaults of f3dg_set_option, overridden by the call's own flags
     // (option reference_kernels: the plain transcription, which knows the reference's arithmetic only)

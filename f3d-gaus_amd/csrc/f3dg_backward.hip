@@ -397,10 +397,12 @@ __device__ __constant__ float B_SH_C3[7] = { -0.5900435899266435f, 2.89061144264
                                              0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
                                              -0.5900435899266435f };
 
-// One thread per GAUSSIAN, looping over the views of the call: view2gaussian backward + SH backward. The per-Gaussian
+// One thread per GAUSSIAN (blockIdx.y: its set), looping over the views of its set: view2gaussian backward + SH backward. The per-Gaussian
 // parameter gradients (mean, scale, rotation, SH) are summed over the views in registers and added to the caller's
 // zero-filled outputs once, by their single writer: no atomics (a (view, Gaussian) grid with 22+ float atomics per
 // thread measured 4.4 ms at 1 M Gaussians x 8 views, all of it contention), and a deterministic view order.
+// Several sets (f3dg_backward_sets): the Gaussian inputs and the per-Gaussian sums are [n_sets, P, ...] and are indexed at set * P + g,
+// the per-view planes at view * P + g with view in [set * V, (set + 1) * V) -- a set's sums never see another set's views.
 __global__ void __launch_bounds__(F3DG_BLOCK)
 preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, const int* __restrict__ radii,
                       const float* __restrict__ shs, const unsigned char* __restrict__ clamped,
@@ -408,12 +410,14 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
                       const float* __restrict__ viewmatrices, const float* __restrict__ cam_positions,
                       const double* __restrict__ dL_dv2g_acc, float* __restrict__ dL_dv2g_out,
                       float* __restrict__ dL_dcolor, float* __restrict__ dL_dmeans, float* __restrict__ dL_dsh,
-                      float* __restrict__ dL_dscale, float* __restrict__ dL_drot, int V,
+                      float* __restrict__ dL_dscale, float* __restrict__ dL_drot, int V /* views per set */,
                       int acc_stride /* doubles per (view, Gaussian) of dL_dv2g_acc: 10, or 16 = the packed records of the dense compositing backward */,
                       float* __restrict__ dL_dmean2D, float* __restrict__ dL_dopacity)
 {
     const int g = blockIdx.x * F3DG_BLOCK + threadIdx.x;
     if (g >= P) return;
+    const int set = blockIdx.y;
+    const size_t gs = (size_t)set * P + g;
     float sum_mean[3] = { 0, 0, 0 }, sum_scale[3] = { 0, 0, 0 }, sum_rot[4] = { 0, 0, 0, 0 };
     float sum_sh[48];
 #pragma unroll
@@ -421,7 +425,7 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
     bool any = false;
     float op_sum = 0.0f;
 
-    for (int v = 0; v < V; v++) {
+    for (int v = set * V; v < (set + 1) * V; v++) {
     const size_t idx = (size_t)v * P + g;
 
     float dv[10];
@@ -450,9 +454,9 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
 
     float dmean[3] = { 0, 0, 0 };
     if (scales && rotations) {
-        const float sx = scales[3 * (size_t)g], sy = scales[3 * (size_t)g + 1], sz = scales[3 * (size_t)g + 2];
-        const float4 rot = reinterpret_cast<const float4*>(rotations)[g];
-        const float mx = means3D[3 * (size_t)g], my = means3D[3 * (size_t)g + 1], mz = means3D[3 * (size_t)g + 2];
+        const float sx = scales[3 * gs], sy = scales[3 * gs + 1], sz = scales[3 * gs + 2];
+        const float4 rot = reinterpret_cast<const float4*>(rotations)[gs];
+        const float mx = means3D[3 * gs], my = means3D[3 * gs + 1], mz = means3D[3 * gs + 2];
         const float r = rot.x, x = rot.y, y = rot.z, z = rot.w;
         M3 R;
         R.m[0][0] = 1.f - 2.f * (y * y + z * z); R.m[0][1] = 2.f * (x * y - r * z);       R.m[0][2] = 2.f * (x * z + r * y);
@@ -567,10 +571,10 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
 
     if (shs) {
         const float* campos = cam_positions + 3 * v;
-        const float o0 = means3D[3 * (size_t)g] - campos[0], o1 = means3D[3 * (size_t)g + 1] - campos[1], o2 = means3D[3 * (size_t)g + 2] - campos[2];
+        const float o0 = means3D[3 * gs] - campos[0], o1 = means3D[3 * gs + 1] - campos[1], o2 = means3D[3 * gs + 2] - campos[2];
         const float len = sqrtf(o0 * o0 + o1 * o1 + o2 * o2);
         const float x = o0 / len, y = o1 / len, z = o2 / len;
-        const float* sh = shs + (size_t)g * M * 3;
+        const float* sh = shs + gs * M * 3;
         const unsigned char cl = clamped[idx];
         float dRGB[3];
 #pragma unroll
@@ -652,18 +656,18 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
     sum_mean[0] += dmean[0]; sum_mean[1] += dmean[1]; sum_mean[2] += dmean[2];
     }   // views
 
-    if (acc_stride == 16) dL_dopacity[g] += op_sum;
+    if (acc_stride == 16) dL_dopacity[gs] += op_sum;
     if (!any) return;
 #pragma unroll
-    for (int q = 0; q < 3; q++) dL_dmeans[3 * (size_t)g + q] += sum_mean[q];
+    for (int q = 0; q < 3; q++) dL_dmeans[3 * gs + q] += sum_mean[q];
     if (scales && rotations) {
 #pragma unroll
-        for (int q = 0; q < 3; q++) dL_dscale[3 * (size_t)g + q] += sum_scale[q];
+        for (int q = 0; q < 3; q++) dL_dscale[3 * gs + q] += sum_scale[q];
 #pragma unroll
-        for (int q = 0; q < 4; q++) dL_drot[4 * (size_t)g + q] += sum_rot[q];
+        for (int q = 0; q < 4; q++) dL_drot[4 * gs + q] += sum_rot[q];
     }
     if (shs) {
-        float* dsh = dL_dsh + (size_t)g * M * 3;
+        float* dsh = dL_dsh + gs * M * 3;
         const int ncoef = (D + 1) * (D + 1);
 #pragma unroll
         for (int i = 0; i < 48; i++)
@@ -673,22 +677,22 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
 
 } // namespace
 
-extern "C" int f3dg_backward(void* stream, void* workspace, size_t workspace_bytes, long long max_rendered,
-                             int n_views, int P, int D, int M, const float* background, int W, int H,
-                             const float* means3D, const float* shs, const float* colors_precomp,
-                             const float* scales, float scale_modifier, const float* rotations,
-                             const float* cov3D_precomp, const float* view2gaussian_precomp,
-                             const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                             float tan_fovx, float tan_fovy, float kernel_size,
-                             const int* radii, const float* dL_dpix,
-                             float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                             float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                             float* dL_dview2gaussian, unsigned flags)
+namespace {
+
+int backward_sets(void* stream, void* workspace, size_t workspace_bytes, long long max_rendered,
+                  int n_sets, int views_per_set, int P, int D, int M, const float* background, int W, int H,
+                  const float* means3D, const float* shs, const float* scales, const float* rotations,
+                  const float* viewmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+                  const int* radii, const float* dL_dpix,
+                  float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor,
+                  float* dL_dmean3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                  float* dL_dview2gaussian, unsigned flags)
 {
-    (void)scale_modifier; (void)projmatrix; (void)kernel_size; (void)dL_dconic; (void)dL_dcov3D;
-    (void)cov3D_precomp; (void)colors_precomp; (void)view2gaussian_precomp;
     hipStream_t s = (hipStream_t)stream;
-    if (n_views <= 0 || P < 0 || W <= 0 || H <= 0 || !workspace || !dL_dpix || !background) return F3DG_ERR_BAD_ARG;
+    if (n_sets <= 0 || views_per_set <= 0 || (long long)n_sets * views_per_set > 0x7FFFFFF0ll) return F3DG_ERR_BAD_ARG;
+    const int n_views = n_sets * views_per_set;
+    if (P < 0 || W <= 0 || H <= 0 || !workspace || !dL_dpix || !background) return F3DG_ERR_BAD_ARG;
+    if ((long long)n_views * P > 0xFFFFFFF0ll || n_sets > 65535) return F3DG_ERR_BAD_ARG;      // 32-bit (view, Gaussian) indices; the set is a grid's y
     if (P == 0) return F3DG_OK;
     if (!means3D || !viewmatrix || !cam_pos || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D ||
         !dL_dview2gaussian)
@@ -708,7 +712,9 @@ extern "C" int f3dg_backward(void* stream, void* workspace, size_t workspace_byt
 
     // float64 accumulator of dL/dview2gaussian (its own region of the workspace)
     double* acc = reinterpret_cast<double*>(ws + L.bwd_acc);
-    const bool dense = g_f3dg_bwd_dense != 0;
+    // (the lock-step walk adds dL/dopacity at the bare Gaussian id, which is right for one set only: several sets always take the dense
+    // kernel, whose opacity sums stay in the per-(view, Gaussian) records until the per-Gaussian stage folds them set by set)
+    const bool dense = g_f3dg_bwd_dense != 0 || n_sets > 1;
     const int acc_stride = dense ? 16 : 10;           // the dense kernel's 128-byte records (ten float64 + seven float32 sums) or [V*P][10]
     F3DG_HIP_CHECK(hipMemsetAsync(acc, 0, sizeof(double) * (size_t)acc_stride * (size_t)n_views * P, s));
     F3DG_HIP_CHECK(hipMemsetAsync(&hdr->bwd_pairs, 0, sizeof(hdr->bwd_pairs), s));
@@ -741,11 +747,52 @@ extern "C" int f3dg_backward(void* stream, void* workspace, size_t workspace_byt
 #undef F3DG_LAUNCH_BWD3
     }
     f3dg_prof_bwd_mark(prof, 0, s);
-    F3DG_KLAUNCH(preprocess_bwd_kernel, dim3((P + F3DG_BLOCK - 1) / F3DG_BLOCK), dim3(F3DG_BLOCK), 0, s, P,
+    F3DG_KLAUNCH(preprocess_bwd_kernel, dim3((P + F3DG_BLOCK - 1) / F3DG_BLOCK, (unsigned)n_sets), dim3(F3DG_BLOCK), 0, s, P,
                        D, M, means3D, radii_used, shs, reinterpret_cast<const unsigned char*>(ws + L.clamped), scales,
                        rotations, viewmatrix, cam_pos, acc, dL_dview2gaussian, dL_dcolor, dL_dmean3D, dL_dsh, dL_dscale,
-                       dL_drot, n_views, acc_stride, dL_dmean2D, dL_dopacity);
+                       dL_drot, views_per_set, acc_stride, dL_dmean2D, dL_dopacity);
     f3dg_prof_bwd_mark(prof, 1, s);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
+}
+
+} // namespace
+
+extern "C" int f3dg_backward(void* stream, void* workspace, size_t workspace_bytes, long long max_rendered,
+                             int n_views, int P, int D, int M, const float* background, int W, int H,
+                             const float* means3D, const float* shs, const float* colors_precomp,
+                             const float* scales, float scale_modifier, const float* rotations,
+                             const float* cov3D_precomp, const float* view2gaussian_precomp,
+                             const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                             float tan_fovx, float tan_fovy, float kernel_size,
+                             const int* radii, const float* dL_dpix,
+                             float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                             float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                             float* dL_dview2gaussian, unsigned flags)
+{
+    (void)scale_modifier; (void)projmatrix; (void)kernel_size; (void)dL_dconic; (void)dL_dcov3D;
+    (void)cov3D_precomp; (void)colors_precomp; (void)view2gaussian_precomp;
+    return backward_sets(stream, workspace, workspace_bytes, max_rendered, 1, n_views, P, D, M, background, W, H, means3D, shs, scales,
+                         rotations, viewmatrix, cam_pos, tan_fovx, tan_fovy, radii, dL_dpix, dL_dmean2D, dL_dopacity, dL_dcolor,
+                         dL_dmean3D, dL_dsh, dL_dscale, dL_drot, dL_dview2gaussian, flags);
+}
+
+extern "C" int f3dg_backward_sets(void* stream, void* workspace, size_t workspace_bytes, long long max_rendered,
+                                  int n_sets, int views_per_set, int P, int D, int M, const float* background, int W, int H,
+                                  const float* means3D, const float* shs, const float* colors_precomp,
+                                  const float* scales, float scale_modifier, const float* rotations,
+                                  const float* cov3D_precomp, const float* view2gaussian_precomp,
+                                  const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                                  float tan_fovx, float tan_fovy, float kernel_size,
+                                  const int* radii, const float* dL_dpix,
+                                  float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                                  float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                  float* dL_dview2gaussian, unsigned flags)
+{
+    (void)scale_modifier; (void)projmatrix; (void)kernel_size; (void)dL_dconic; (void)dL_dcov3D;
+    (void)cov3D_precomp; (void)colors_precomp;
+    if (n_sets > 1 && view2gaussian_precomp != nullptr) return F3DG_ERR_BAD_ARG;       // [n_views, P, 10] of ONE set, as in the forward
+    return backward_sets(stream, workspace, workspace_bytes, max_rendered, n_sets, views_per_set, P, D, M, background, W, H, means3D, shs,
+                         scales, rotations, viewmatrix, cam_pos, tan_fovx, tan_fovy, radii, dL_dpix, dL_dmean2D, dL_dopacity, dL_dcolor,
+                         dL_dmean3D, dL_dsh, dL_dscale, dL_drot, dL_dview2gaussian, flags);
 }

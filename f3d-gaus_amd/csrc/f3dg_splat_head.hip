@@ -14,6 +14,9 @@
 //
 // epilogue_kernel fuses the post-processing of render_predicted_more_v2_gof
 // (src/gaussian_renderer/__init__.py:1043-1053 world normals, :881-909 depth_to_normal).
+//
+// epilogue_backward_kernel is its vector-Jacobian product with respect to the raster: the same grid, the forward's points and cross
+// products recomputed through the shared __device__ helpers, the depth channel as a gather over the pixel's axial neighbours.
 #include "f3dg_common.h"
 
 namespace {
@@ -242,6 +245,43 @@ __device__ void invert4x4(const float* m_, float* out)
     for (int i = 0; i < 16; i++) out[i] = (float)(inv[i] * r);
 }
 
+// ---- per-pixel arithmetic shared by epilogue_kernel and epilogue_backward_kernel
+// ray(yy, xx) = [xx,yy,1] @ Kinv^T @ R^T with Kinv = [[ax,0,bx],[0,ay,by],[0,0,1]], R = Cw[:3,:3] (Cw row-major 4x4)
+__device__ __forceinline__ void epilogue_ray(const float* Cw, float ax, float bx, float ay, float by, int yy, int xx,
+                                             float& dx, float& dy, float& dz)
+{
+    const float cx = xx * ax + bx, cy = yy * ay + by;
+    dx = cx * Cw[0] + cy * Cw[1] + Cw[2];
+    dy = cx * Cw[4] + cy * Cw[5] + Cw[6];
+    dz = cx * Cw[8] + cy * Cw[9] + Cw[10];
+}
+// point(yy, xx) = depth * ray(yy, xx) + origin
+__device__ __forceinline__ void epilogue_point(const float* __restrict__ dep, const float* Cw, int W, float ax, float bx, float ay, float by,
+                                               int yy, int xx, float& px, float& py, float& pz)
+{
+    float dx, dy, dz;
+    epilogue_ray(Cw, ax, bx, ay, by, yy, xx, dx, dy, dz);
+    const float dd = dep[yy * W + xx];
+    px = dd * dx + Cw[3]; py = dd * dy + Cw[7]; pz = dd * dz + Cw[11];
+}
+// the two difference vectors of the interior pixel (y, x): e = point(y+1, x) - point(y-1, x) ("dx": along rows),
+// g = point(y, x+1) - point(y, x-1) ("dy": along columns), and their cross product c = e x g
+struct EpilogueCross { float ex, ey, ez, gx, gy, gz, cx, cy, cz; };
+__device__ __forceinline__ EpilogueCross epilogue_cross(const float* __restrict__ dep, const float* Cw, int W, float ax, float bx, float ay,
+                                                        float by, int y, int x)
+{
+    float ux, uy, uz, lx, ly, lz, rx, ry, rz, dx_, dy_, dz_;
+    epilogue_point(dep, Cw, W, ax, bx, ay, by, y + 1, x, ux, uy, uz);
+    epilogue_point(dep, Cw, W, ax, bx, ay, by, y - 1, x, lx, ly, lz);
+    epilogue_point(dep, Cw, W, ax, bx, ay, by, y, x + 1, rx, ry, rz);
+    epilogue_point(dep, Cw, W, ax, bx, ay, by, y, x - 1, dx_, dy_, dz_);
+    EpilogueCross r;
+    r.ex = ux - lx; r.ey = uy - ly; r.ez = uz - lz;
+    r.gx = rx - dx_; r.gy = ry - dy_; r.gz = rz - dz_;
+    r.cx = r.ey * r.gz - r.ez * r.gy; r.cy = r.ez * r.gx - r.ex * r.gz; r.cz = r.ex * r.gy - r.ey * r.gx;
+    return r;
+}
+
 // from_view: `c2w` holds the world_view matrices (row-vector convention, as the renderer receives them) and the kernel inverts their
 // transposes itself -- the caller saves a torch.linalg.inv (a solver call and several launches per one-view call)
 template <bool FROM_VIEW>
@@ -282,30 +322,91 @@ epilogue_kernel(int H, int W, const float* __restrict__ raster, const float* __r
         if (x >= 1 && x < W - 1 && y >= 1 && y < H - 1) {
             const float* dep = ras + 6 * HW;
             const float ax = 1.0f / fx, bx = -(W / 2.0f) / fx, ay = 1.0f / fy, by = -(H / 2.0f) / fy;
-            // point(yy, xx) = depth * ([xx,yy,1] @ Kinv^T @ R^T) + origin
-            auto point = [&](int yy, int xx, float& px, float& py, float& pz) {
-                const float cx = xx * ax + bx, cy = yy * ay + by;
-                const float dx = cx * Cw[0] + cy * Cw[1] + Cw[2];
-                const float dy = cx * Cw[4] + cy * Cw[5] + Cw[6];
-                const float dz = cx * Cw[8] + cy * Cw[9] + Cw[10];
-                const float dd = dep[yy * W + xx];
-                px = dd * dx + Cw[3]; py = dd * dy + Cw[7]; pz = dd * dz + Cw[11];
-            };
-            float ux, uy, uz, lx, ly, lz, rx, ry, rz, dx_, dy_, dz_;
-            point(y + 1, x, ux, uy, uz);
-            point(y - 1, x, lx, ly, lz);
-            point(y, x + 1, rx, ry, rz);
-            point(y, x - 1, dx_, dy_, dz_);
-            const float ex = ux - lx, ey = uy - ly, ez = uz - lz;          // "dx": along rows
-            const float gx = rx - dx_, gy = ry - dy_, gz = rz - dz_;       // "dy": along columns
-            const float cx_ = ey * gz - ez * gy, cy_ = ez * gx - ex * gz, cz_ = ex * gy - ey * gx;
-            const float nrm = fmaxf(sqrtf(cx_ * cx_ + cy_ * cy_ + cz_ * cz_), 1e-12f);
-            r0 = cx_ / nrm; r1 = cy_ / nrm; r2 = cz_ / nrm;
+            const EpilogueCross k = epilogue_cross(dep, Cw, W, ax, bx, ay, by, y, x);
+            const float nrm = fmaxf(sqrtf(k.cx * k.cx + k.cy * k.cy + k.cz * k.cz), 1e-12f);
+            r0 = k.cx / nrm; r1 = k.cy / nrm; r2 = k.cz / nrm;
         }
         o[n] = r0; o[HW + n] = r1; o[2 * HW + n] = r2;
     }
 }
 
+// Backward of F.normalize(v, eps = 1e-12) for one 3-vector: (g - n^ (n^ . g)) / |v|, or g / 1e-12 where the clamp is active (what
+// torch.autograd gives for v / clamp_min(|v|, 1e-12): the clamped norm gets no gradient)
+__device__ __forceinline__ void normalize3_backward(float a, float b, float c, float& g0, float& g1, float& g2)
+{
+    const float raw = sqrtf(a * a + b * b + c * c);
+    if (raw >= 1e-12f) {
+        const float ha = a / raw, hb = b / raw, hc = c / raw;
+        const float dot = ha * g0 + hb * g1 + hc * g2;
+        g0 = (g0 - ha * dot) / raw; g1 = (g1 - hb * dot) / raw; g2 = (g2 - hc * dot) / raw;
+    } else {
+        g0 = g0 / 1e-12f; g1 = g1 / 1e-12f; g2 = g2 / 1e-12f;
+    }
+}
+
+// Adjoint of epilogue_kernel<true>: one thread per (view, pixel), the same grid. Channels 3..5 depend on this pixel's normal only.
+// Channel 6 in GATHER form: the depth of pixel (y, x) is read by the depth normals of its axial neighbours that are interior pixels --
+// as the "y + 1" point of centre (y - 1, x), the "y - 1" point of (y + 1, x), the "x + 1" point of (y, x - 1) and the "x - 1" point of
+// (y, x + 1). For each such centre the thread recomputes the forward's two difference vectors and cross product from `raster`, takes the
+// centre's cotangent through the normalisation and through c = e x g (dL/de = g x w, dL/dg = w x e), and dots the result with its own
+// ray: d point / d depth. The up to four terms are summed in that order. No atomics, no LDS beyond the matrix, nothing saved by the
+// forward; the kernel ADDS into channels 3..5 and 6 of dL_dpix and touches no other channel.
+__global__ void __launch_bounds__(F3DG_BLOCK)
+epilogue_backward_kernel(int H, int W, const float* __restrict__ raster, const float* __restrict__ world_view, float fx, float fy,
+                         const float* __restrict__ g_normal_world, const float* __restrict__ g_depth_normal, float* __restrict__ dL_dpix)
+{
+    const int HW = H * W;
+    const int n = blockIdx.x * F3DG_BLOCK + threadIdx.x;
+    const int v = blockIdx.y;
+    __shared__ float s_c2w[16];
+    if (threadIdx.x == 0) {         // c2w = inverse(world_view^T), as epilogue_kernel<true> forms it
+        float t[16];
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) t[4 * r + c] = world_view[16 * v + 4 * c + r];
+        invert4x4(t, s_c2w);
+    }
+    __syncthreads();
+    if (n >= HW) return;
+    const int y = n / W, x = n % W;
+    const float* ras = raster + (size_t)v * F3DG_OUT_CHANNELS * HW;
+    float* dpix = dL_dpix + (size_t)v * F3DG_OUT_CHANNELS * HW;
+    const float* Cw = s_c2w;
+
+    if (g_normal_world) {
+        const float* gw = g_normal_world + (size_t)v * 3 * HW;
+        const float w0 = gw[n], w1 = gw[HW + n], w2 = gw[2 * HW + n];
+        // c2w[:3,:3]^T applied to the cotangent, then the normalisation
+        float g0 = Cw[0] * w0 + Cw[4] * w1 + Cw[8] * w2;
+        float g1 = Cw[1] * w0 + Cw[5] * w1 + Cw[9] * w2;
+        float g2 = Cw[2] * w0 + Cw[6] * w1 + Cw[10] * w2;
+        normalize3_backward(ras[3 * HW + n], ras[4 * HW + n], ras[5 * HW + n], g0, g1, g2);
+        dpix[3 * HW + n] += g0; dpix[4 * HW + n] += g1; dpix[5 * HW + n] += g2;
+    }
+    if (g_depth_normal) {
+        const float* gd = g_depth_normal + (size_t)v * 3 * HW;
+        const float* dep = ras + 6 * HW;
+        const float ax = 1.0f / fx, bx = -(W / 2.0f) / fx, ay = 1.0f / fy, by = -(H / 2.0f) / fy;
+        float rx, ry, rz;
+        epilogue_ray(Cw, ax, bx, ay, by, y, x, rx, ry, rz);
+        // the cotangent of centre (cy, cx) taken back to its difference vectors: along_rows selects dL/de (else dL/dg), dotted with this ray
+        auto term = [&](int cy, int cx, bool along_rows) -> float {
+            if (!(cx >= 1 && cx < W - 1 && cy >= 1 && cy < H - 1)) return 0.0f;
+            const EpilogueCross k = epilogue_cross(dep, Cw, W, ax, bx, ay, by, cy, cx);
+            const int m = cy * W + cx;
+            float w0 = gd[m], w1 = gd[HW + m], w2 = gd[2 * HW + m];
+            normalize3_backward(k.cx, k.cy, k.cz, w0, w1, w2);
+            float p0, p1, p2;
+            if (along_rows) { p0 = k.gy * w2 - k.gz * w1; p1 = k.gz * w0 - k.gx * w2; p2 = k.gx * w1 - k.gy * w0; }      // g x w
+            else            { p0 = w1 * k.ez - w2 * k.ey; p1 = w2 * k.ex - w0 * k.ez; p2 = w0 * k.ey - w1 * k.ex; }      // w x e
+            return rx * p0 + ry * p1 + rz * p2;
+        };
+        float sum = term(y - 1, x, true);
+        sum -= term(y + 1, x, true);
+        sum += term(y, x - 1, false);
+        sum -= term(y, x + 1, false);
+        dpix[6 * HW + n] += sum;
+    }
+}
 
 // 8-bit RGB frames for the video writer / the multi-GPU gather: dst[n][y][x][c] = (uint8)(255 * clamp(src[n][c][y][x], 0, 1))
 // exactly as visualize.py:407,416 does on the host ((255 * np.clip(x, 0, 1)).astype(np.uint8): float32 product, truncation).
@@ -434,6 +535,20 @@ extern "C" int f3dg_render_epilogue_view(void* stream, int n_views, int H, int W
     dim3 grid((unsigned)(((long long)H * W + F3DG_BLOCK - 1) / F3DG_BLOCK), (unsigned)n_views);
     F3DG_KLAUNCH(epilogue_kernel<true>, grid, dim3(F3DG_BLOCK), 0, (hipStream_t)stream, H, W, raster, world_view, fx, fy,
                        normal_world, depth_normal);
+    F3DG_HIP_CHECK(hipGetLastError());
+    return F3DG_OK;
+}
+
+extern "C" int f3dg_render_epilogue_backward(void* stream, int n_views, int H, int W, const float* raster,
+                                             const float* world_view, float fx, float fy,
+                                             const float* dL_dnormal_world, const float* dL_ddepth_normal, float* dL_dpix)
+{
+    // (the kernel forms channel * HW + pixel, channel < 9, in int)
+    if (n_views <= 0 || H <= 0 || W <= 0 || 9ll * H * W > 0x7FFFFFF0ll || !raster || !world_view || !dL_dpix) return F3DG_ERR_BAD_ARG;
+    if (!dL_dnormal_world && !dL_ddepth_normal) return F3DG_OK;
+    dim3 grid((unsigned)(((long long)H * W + F3DG_BLOCK - 1) / F3DG_BLOCK), (unsigned)n_views);
+    F3DG_KLAUNCH(epilogue_backward_kernel, grid, dim3(F3DG_BLOCK), 0, (hipStream_t)stream, H, W, raster, world_view, fx, fy,
+                       dL_dnormal_world, dL_ddepth_normal, dL_dpix);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }

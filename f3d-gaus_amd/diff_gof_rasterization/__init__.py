@@ -20,6 +20,7 @@ import torch.nn as nn
 from .. import _lib
 
 __all__ = ["GaussianRasterizationSettings_GOF", "GaussianRasterizer_GOF", "rasterize_gaussians", "rasterize_views",
+           "rasterize_views_autograd",
            "set_deferred_status", "deferred_status", "flush",
            "integrate_gaussians_to_points", "integrate_prepare", "integrate_points", "PreparedIntegration", "Workspace"]
 
@@ -78,6 +79,8 @@ class Workspace:
         self.buffer = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
         self.num_rendered = None
         self.save_aux = False         # whether the last forward on this workspace kept the planes f3dg_backward reads
+        self.n_sets = 1               # Gaussian sets of that forward (> 1: the planes are for f3dg_backward_sets)
+        self.generation = 0           # bumped by every forward on this workspace: a backward checks that its planes are still there
 
     @property
     def nbytes(self):
@@ -170,6 +173,8 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, camposs, bg,
     ``n_sets`` > 1 (f3dg_forward_sets): the Gaussian tensors hold n_sets sets of equal size one after the other
     ([n_sets * P, ...]) and the V cameras are n_sets groups of V / n_sets (set-major): camera i renders set i // (V / n_sets).
     This is how the cycle aggregation renders the 8 novel views of every image of a batch in one launch sequence.
+    With ``save_aux=True`` such a call keeps the auxiliary planes for ``rasterize_backward_raw(..., n_sets=n_sets)``
+    (F3DG_FLAG_SAVE_AUX | F3DG_FLAG_SETS_AUX -> f3dg_backward_sets); ``rasterize_views_autograd`` wraps the pair for autograd.
 
     ``channels="rgb_depth_alpha"`` (inference only; the build's own batched loops): the compositing kernel neither accumulates nor
     writes the normal (3..5) and distortion (8) planes of ``color`` -- they hold whatever the buffer held -- and the channels it
@@ -193,8 +198,8 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, camposs, bg,
     V = vm.size(0)
     if n_sets < 1 or V % n_sets or (means3D.ndim == 2 and means3D.size(0) % n_sets):
         raise RuntimeError("n_sets must divide the number of views and the number of Gaussians")
-    if n_sets > 1 and (save_aux or view2gaussian_precomp is not None):
-        raise RuntimeError("n_sets > 1 is an inference path: no SAVE_AUX / backward, no view2gaussian_precomp")
+    if n_sets > 1 and view2gaussian_precomp is not None and view2gaussian_precomp.numel():
+        raise RuntimeError("n_sets > 1 takes no view2gaussian_precomp (it is [n_views, P, 10] of one set)")
     _check_inputs(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, view2gaussian_precomp, V)
     P = means3D.size(0) // n_sets
     pm = _dev_f32(projmatrices, device).reshape(-1, 16)
@@ -203,6 +208,8 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, camposs, bg,
     if pm.size(0) != V or cp.size(0) != V or bgt.size(0) not in (1, V):
         raise RuntimeError("viewmatrices, projmatrices, camposs (and bg if per view) must agree on the number of views")
     flags = (_lib.FLAG_SAVE_AUX if save_aux else 0) | (_lib.FLAG_BG_PER_VIEW if (bgt.size(0) == V and V > 1) else 0)
+    if save_aux and n_sets > 1:
+        flags |= _lib.FLAG_SETS_AUX         # the planes are kept for f3dg_backward_sets (rasterize_backward_raw(n_sets=...))
     if channels == "rgb_depth_alpha":
         if save_aux:
             raise RuntimeError('channels="rgb_depth_alpha" is an inference option (the backward reads all nine channels\' state)')
@@ -249,6 +256,8 @@ def rasterize_views(means3D, opacities, viewmatrices, projmatrices, camposs, bg,
             float(tanfovx), float(tanfovy), float(kernel_size), _lib.ptr(out), _lib.ptr(radii), flags)
         _lib.check(rc, "f3dg_forward_sets")
         workspace.save_aux = bool(save_aux)
+        workspace.n_sets = n_sets
+        workspace.generation += 1
         if not check:
             workspace.num_rendered = None
             return out, radii, workspace
@@ -477,6 +486,108 @@ class _RasterizeGaussians(torch.autograd.Function):
             print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
             raise ex
         return grads
+
+
+class _RasterizeViews(torch.autograd.Function):
+    """n_sets Gaussian sets x V / n_sets cameras, differentiable, in ONE forward and ONE backward launch sequence:
+    ``rasterize_views(save_aux=True, n_sets=...)`` in the reference arithmetic + the fused render epilogue; the backward adds the
+    cotangents of the two derived maps into the raster's (f3dg_render_epilogue_backward) and runs f3dg_backward_sets once.
+    The Gaussian tensors are flattened set-major ([n_sets * P, ...]); cameras and background are data. ``cfg``: a dict of the
+    call's constants, read only; ``holder``: a list that receives the workspace the forward used.
+    Returns (raster [V,9,H,W], normal_world [V,3,H,W], depth_normal [V,3,H,W], radii [V,P]); with ``cfg["epilogue"]`` false the
+    epilogue kernel is not launched and the two maps are None."""
+
+    @staticmethod
+    def forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, viewmatrices, projmatrices, camposs, bg, cfg, holder):
+        device = means3D.device
+        H, W = int(cfg["image_height"]), int(cfg["image_width"])
+        vm = _dev_f32(viewmatrices, device).reshape(-1, 16)
+        V = vm.size(0)
+        raster, radii, ws = rasterize_views(
+            means3D, opacities, vm, projmatrices, camposs, bg, image_height=H, image_width=W, tanfovx=cfg["tanfovx"],
+            tanfovy=cfg["tanfovy"], sh=sh, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
+            sh_degree=cfg["sh_degree"], scale_modifier=cfg["scale_modifier"], kernel_size=cfg["kernel_size"],
+            workspace=cfg.get("workspace"), save_aux=True, check=True, n_sets=cfg["n_sets"], exact=True)
+        nw = dn = None
+        if cfg["epilogue"]:
+            nw = torch.empty((V, 3, H, W), dtype=torch.float32, device=device)
+            dn = torch.empty((V, 3, H, W), dtype=torch.float32, device=device)
+            rc = _lib.lib().f3dg_render_epilogue_view(_stream(), V, H, W, _lib.ptr(raster), _lib.ptr(vm), float(cfg["fx"]), float(cfg["fy"]),
+                                                      _lib.ptr(nw), _lib.ptr(dn))
+            _lib.check(rc, "f3dg_render_epilogue_view")
+        ctx.cfg = cfg
+        holder.append(ws)
+        ctx.workspace, ctx.generation = ws, ws.generation
+        ctx.cameras = (vm, projmatrices, camposs, bg)
+        none = lambda t: t if t is not None else torch.empty(0, device=device)
+        ctx.save_for_backward(means3D, none(sh), none(colors_precomp), scales, rotations, radii, raster)
+        ctx.opacity_shape = opacities.shape
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)        # an unused map's cotangent arrives as None: a NULL pointer, not a plane of zeros
+        return raster, nw, dn, radii
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_raster, g_normal_world, g_depth_normal, _g_radii):
+        from .backward import rasterize_backward_raw
+        cfg, ws = ctx.cfg, ctx.workspace
+        means3D, sh, colors_precomp, scales, rotations, radii, raster = ctx.saved_tensors
+        if ws.generation != ctx.generation:
+            raise RuntimeError("backward of a batched render whose workspace has been used by another forward since (generation "
+                               f"{ws.generation}, this call's was {ctx.generation}): the auxiliary planes it reads are overwritten. "
+                               "Give every forward that is still to be differentiated its own workspace")
+        device = raster.device
+        V, H, W, n_sets = raster.size(0), raster.size(2), raster.size(3), int(cfg["n_sets"])
+        gn = None if g_normal_world is None else _dev_f32(g_normal_world, device)
+        gd = None if g_depth_normal is None else _dev_f32(g_depth_normal, device)
+        if g_raster is None:
+            dpix = torch.zeros_like(raster)
+        elif gn is None and gd is None:
+            dpix = _dev_f32(g_raster, device)       # nothing is added into it: read as it is
+        else:
+            dpix = torch.empty_like(raster).copy_(g_raster)         # dense, and ours to add into
+        if gn is not None or gd is not None:
+            vm = ctx.cameras[0]
+            rc = _lib.lib().f3dg_render_epilogue_backward(_stream(), V, H, W, _lib.ptr(raster), _lib.ptr(vm), float(cfg["fx"]),
+                                                          float(cfg["fy"]), _lib.ptr(gn), _lib.ptr(gd), _lib.ptr(dpix))
+            _lib.check(rc, "f3dg_render_epilogue_backward")
+        vm, pm, cp, bg = ctx.cameras
+        g = rasterize_backward_raw(ws, means3D, sh if sh.numel() else None, colors_precomp if colors_precomp.numel() else None, scales,
+                                   rotations, radii, dpix, cfg["sh_degree"], vm, pm, cp, bg, cfg["tanfovx"], cfg["tanfovy"],
+                                   cfg["kernel_size"], cfg["scale_modifier"], n_sets=n_sets)
+        need = ctx.needs_input_grad
+        P = ws.P
+        d_colors = None
+        if colors_precomp.numel() and need[2]:       # per-view [V,P,3] -> per Gaussian of each set: summed over the set's views
+            d_colors = g["dL_dcolors"].reshape(n_sets, V // n_sets, P, 3).sum(1).reshape(n_sets * P, 3)
+        return (g["dL_dmeans3D"] if need[0] else None, g["dL_dsh"] if (sh.numel() and need[1]) else None, d_colors,
+                g["dL_dopacity"].reshape(ctx.opacity_shape) if need[3] else None, g["dL_dscales"] if need[4] else None,
+                g["dL_drotations"] if need[5] else None, None, None, None, None, None, None)
+
+
+def rasterize_views_autograd(means3D, opacities, viewmatrices, projmatrices, camposs, bg, *, image_height, image_width, tanfovx, tanfovy,
+                             fx=None, fy=None, sh=None, colors_precomp=None, scales=None, rotations=None, sh_degree=0, scale_modifier=1.0,
+                             kernel_size=0.0, workspace=None, n_sets=1, epilogue=True):
+    """Differentiable ``rasterize_views`` + render epilogue of ``n_sets`` Gaussian sets ([n_sets * P, ...], set-major) from
+    V = n_sets * views_per_set cameras (set-major): one forward and one backward launch sequence (``_RasterizeViews``).
+    Returns (raster [V,9,H,W], normal_world [V,3,H,W], depth_normal [V,3,H,W], radii [V,P], workspace); gradients reach means3D, sh or
+    colors_precomp, opacities, scales and rotations. Cameras and background are data. ``fx``, ``fy``: the focal lengths of the depth
+    normal (default W / (2 tanfovx), H / (2 tanfovy)). A ``workspace`` must not serve another forward before this call's backward
+    has run (the backward raises then). ``epilogue=False``: the two derived maps are not computed (None). Always the reference
+    arithmetic, and the forward always reads the status (an overflowed render must not reach a backward). No double backward."""
+    for name, t in (("viewmatrices", viewmatrices), ("projmatrices", projmatrices), ("camposs", camposs), ("bg", bg)):
+        if torch.is_tensor(t) and t.requires_grad:
+            raise NotImplementedError(f"the batched render produces no gradient for `{name}` (cameras and background are data): detach it")
+    if scales is None or rotations is None:
+        raise RuntimeError("the differentiable batched render needs scales and rotations (cov3D_precomp has no backward)")
+    cfg = dict(image_height=int(image_height), image_width=int(image_width), tanfovx=float(tanfovx), tanfovy=float(tanfovy),
+               fx=float(image_width / (2.0 * tanfovx) if fx is None else fx), fy=float(image_height / (2.0 * tanfovy) if fy is None else fy),
+               sh_degree=int(sh_degree), scale_modifier=float(scale_modifier), kernel_size=float(kernel_size), workspace=workspace,
+               n_sets=int(n_sets), epilogue=bool(epilogue))
+    holder = []
+    out = _RasterizeViews.apply(means3D, sh, colors_precomp, opacities, scales, rotations, viewmatrices, projmatrices, camposs, bg, cfg,
+                                holder)
+    return out + (holder[0],)
 
 
 _INTEG_WS = _StreamCache()      # (device index, stream) -> (key, capacity, buffer) reused by integrate calls on that stream

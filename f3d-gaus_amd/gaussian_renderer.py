@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from .diff_gof_rasterization import (GaussianRasterizationSettings_GOF, GaussianRasterizer_GOF, _stream, add_redo, deferred_status,
                                      integrate_points, integrate_prepare, integrate_prepare_batched, rasterize_nograd,
-                                     rasterize_views)
+                                     rasterize_views, rasterize_views_autograd)
 
 
 def _raster_exact(cfg):
@@ -313,7 +313,7 @@ def render_predicted_more_v3_gof(pc, bs, world_view_transform, full_proj_transfo
 
 def render_views(pc: dict, bs, world_view_transforms, full_proj_transforms, camera_centers, bg_color, cfg,
                  kernel_size=0.0, scaling_modifier=1.0, override_color=None, workspace=None, epilogue=True,
-                 check=True, channels="all"):
+                 check=True, channels="all", differentiable=False):
     """All V cameras of image ``bs`` in one launch sequence (no per-view Python loop, no per-view host sync).
     Returns a dict with the same keys as ``render_predicted_more_v2_gof`` but a leading view axis:
     render [V,3,H,W], rendered_normal [V,3,H,W], rendered_depth [V,1,H,W], depth_normal [V,3,H,W],
@@ -323,7 +323,27 @@ def render_views(pc: dict, bs, world_view_transforms, full_proj_transforms, came
     axis is then B * V, image-major (frame b * V + v).
 
     ``channels="rgb_depth_alpha"``: what visualize.py:304-306, 400-402 consume. The compositing kernel skips the normal and distortion
-    accumulators; ``rendered_normal`` and ``distortion_map`` are None, the other maps bit-identical to the 9-channel call."""
+    accumulators; ``rendered_normal`` and ``distortion_map`` are None, the other maps bit-identical to the 9-channel call.
+
+    ``differentiable=True`` (with grad mode on; under ``torch.no_grad()`` it is the inference call): ``render``, ``rendered_normal``,
+    ``rendered_depth``, ``depth_normal``, ``rendered_alpha``, ``distortion_map`` and ``raster`` carry the autograd graph back to
+    the Gaussian tensors of ``pc`` -- ONE forward and ONE backward launch sequence for all B sets x V views (f3dg_forward_sets /
+    f3dg_backward_sets, the epilogue and its adjoint as one kernel each), in the reference arithmetic. The training shape:
+
+        pc = predictor(...)                                                          # [B, N, ...] Gaussians that require grad
+        out = render_views(pc, None, world_views, full_projs, centers, bg, cfg, differentiable=True)
+        loss(out["render"], out["rendered_normal"], out["depth_normal"], ...).backward()
+
+    All nine planes are needed by the backward: ``channels="rgb_depth_alpha"`` raises. There is no per-view means2D leaf
+    (``viewspace_points`` belongs to the one-view drop-in API). A ``workspace=`` handed in must not serve another forward before
+    ``backward()`` has run: the backward raises ``RuntimeError`` then. ``epilogue=False`` skips the two derived maps (None) as in the
+    inference call. The status is always read (an overflowed render must not reach a backward): ``check=False`` raises. The
+    arithmetic is the reference's whatever ``raster_exact`` / ``raster_scan`` say -- those pick among inference kernels, as in the
+    one-view route."""
+    if differentiable and channels != "all":
+        raise RuntimeError('differentiable=True needs channels="all": the backward reads the state of all nine planes')
+    if differentiable and not check and torch.is_grad_enabled():
+        raise RuntimeError("differentiable=True reads the forward's status (check=True): an overflowed render must not reach a backward")
     fov = cfg['model']['fov']
     tanfov = math.tan(fov * np.pi / 360)
     res = int(cfg['model']['training_resolution'])
@@ -340,6 +360,17 @@ def render_views(pc: dict, bs, world_view_transforms, full_proj_transforms, came
         colors = None
     else:
         shs, colors = None, take(pc["rgbs"])
+    if differentiable and torch.is_grad_enabled():
+        FoV = fov * np.pi / 180
+        raster, nw, dn, radii, ws = rasterize_views_autograd(
+            take(pc["xyz"]), take(pc["opacity"]), wv, fp, cc, bg_color, image_height=res, image_width=res, tanfovx=tanfov, tanfovy=tanfov,
+            fx=res / (2 * math.tan(FoV / 2.)), fy=res / (2 * math.tan(FoV / 2.)),       # as _epilogue forms them
+            sh=shs, colors_precomp=colors, scales=take(pc["scaling"]), rotations=take(pc["rotation"]),
+            sh_degree=cfg['model']['max_sh_degree'], scale_modifier=scaling_modifier, kernel_size=kernel_size, workspace=workspace,
+            n_sets=n_sets, epilogue=epilogue)
+        return {"render": raster[:, :3], "rendered_normal": nw, "rendered_depth": raster[:, 6:7], "depth_normal": dn,
+                "rendered_alpha": raster[:, 7:8], "distortion_map": raster[:, 8:9], "visibility_filter": radii > 0,
+                "radii": radii, "raster": raster, "workspace": ws}
     with torch.no_grad():
         raster, radii, ws = rasterize_views(
             take(pc["xyz"]), take(pc["opacity"]), wv, fp, cc, bg_color,

@@ -17,6 +17,9 @@
  *       CudaRasterizer::Rasterizer::backward     RAST/cuda_rasterizer/rasterizer.h:57-90,
  *                                                RAST/cuda_rasterizer/rasterizer_impl.cu:409-526
  *       reached from pybind `rasterize_gaussians_backward` RAST/ext.cpp:18, RAST/rasterize_points.cu:124-211
+ *   f3dg_backward_sets
+ *       the same for the n_sets Gaussian sets x views_per_set views of one f3dg_forward_sets call (the reference runs
+ *       n_sets * views_per_set separate backward calls)
  *   f3dg_mark_visible
  *       CudaRasterizer::Rasterizer::markVisible  RAST/cuda_rasterizer/rasterizer.h:23-29,
  *                                                RAST/cuda_rasterizer/rasterizer_impl.cu:172-186 (pybind `mark_visible`)
@@ -30,6 +33,8 @@
  *       what torch.autograd derives from those same lines                src/gaussian_predictor.py:857-881, 961-1002
  *   f3dg_render_epilogue
  *       the torch post-processing of render_predicted_more_v2_gof  src/gaussian_renderer/__init__.py:881-909, 1043-1053
+ *   f3dg_render_epilogue_backward
+ *       what torch.autograd derives from those same lines (they are plain torch ops on the raster in the reference)
  *
  * Memory ownership mirrors the reference: outputs and the workspace are allocated and owned by the caller
  * (torch tensors on the Python side). Instead of growing buffers through callbacks in the middle of the call
@@ -91,6 +96,10 @@ extern "C" {
 #define F3DG_FLAG_NO_TILE_CULL 64u
 #define F3DG_FLAG_NO_SMALL_PATH 128u
 #define F3DG_FLAG_SCAN 256u
+/* f3dg_forward_sets with n_sets > 1 keeps the auxiliary planes only with F3DG_FLAG_SAVE_AUX | F3DG_FLAG_SETS_AUX: the caller's promise that
+ * f3dg_backward_sets (not f3dg_backward, which indexes the Gaussian inputs of one set) follows on that workspace. Without F3DG_FLAG_SAVE_AUX
+ * the flag is F3DG_ERR_BAD_ARG; with n_sets == 1 it changes nothing. */
+#define F3DG_FLAG_SETS_AUX 512u
 
 #define F3DG_TILE 16             /* BLOCK_X = BLOCK_Y = 16, RAST/cuda_rasterizer/config.h:16-17 */
 #define F3DG_OUT_CHANNELS 9      /* RGB, normal xyz, median depth, alpha, distortion: auxiliary.h:21-24 */
@@ -132,8 +141,9 @@ int f3dg_forward_batched(void* stream, void* workspace, size_t workspace_bytes, 
  * means3D ... rotations are [n_sets, P, ...], the cameras [n_sets * views_per_set, ...] (set-major), out_color
  * [n_sets * views_per_set, 9, H, W], radii [n_sets * views_per_set, P]; view i renders set i / views_per_set.
  * f3dg_forward_batched is the n_sets = 1 case. Workspace: f3dg_workspace_bytes(P, W, H, n_sets * views_per_set, max_rendered).
- * n_sets > 1 is an inference path: with F3DG_FLAG_SAVE_AUX or view2gaussian_precomp it returns F3DG_ERR_BAD_ARG (f3dg_backward
- * indexes the Gaussian inputs of ONE set). */
+ * n_sets > 1 with view2gaussian_precomp, or with F3DG_FLAG_SAVE_AUX alone, returns F3DG_ERR_BAD_ARG (f3dg_backward indexes the
+ * Gaussian inputs of ONE set); F3DG_FLAG_SAVE_AUX | F3DG_FLAG_SETS_AUX keeps the auxiliary planes for f3dg_backward_sets. Calls of
+ * several sets always take the general launch sequence. */
 int f3dg_forward_sets(void* stream, void* workspace, size_t workspace_bytes, long long max_rendered,
                       int n_sets, int views_per_set, int P, int D, int M,
                       const float* background, int W, int H,
@@ -195,6 +205,25 @@ int f3dg_backward(void* stream, void* workspace, size_t workspace_bytes, long lo
                   float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                   float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                   float* dL_dview2gaussian, unsigned flags /* F3DG_FLAG_BG_PER_VIEW as in the forward */);
+
+/* The same for a f3dg_forward_sets call made with F3DG_FLAG_SAVE_AUX | F3DG_FLAG_SETS_AUX (same n_sets, views_per_set, P, W, H, max_rendered):
+ * ONE compositing backward over all n_sets * views_per_set views and ONE per-Gaussian stage. means3D, shs, scales, rotations are
+ * [n_sets, P, ...]; the cameras, radii and dL_dpix are set-major [n_sets * views_per_set, ...]; the per-view outputs (dL_dmean2D,
+ * dL_dcolor, dL_dview2gaussian) are [n_sets * views_per_set, P, ...] and written in full; the per-Gaussian sums (dL_dopacity,
+ * dL_dmean3D, dL_dsh, dL_dscale, dL_drot) are [n_sets, P, ...], added into as in f3dg_backward, each summed over the views of its OWN
+ * set only, by one writer per Gaussian in a fixed view order. view2gaussian_precomp with n_sets > 1 is F3DG_ERR_BAD_ARG.
+ * f3dg_backward is the n_sets = 1 case of the same code. */
+int f3dg_backward_sets(void* stream, void* workspace, size_t workspace_bytes, long long max_rendered,
+                       int n_sets, int views_per_set, int P, int D, int M, const float* background, int W, int H,
+                       const float* means3D, const float* shs, const float* colors_precomp,
+                       const float* scales, float scale_modifier, const float* rotations,
+                       const float* cov3D_precomp, const float* view2gaussian_precomp,
+                       const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                       float tan_fovx, float tan_fovy, float kernel_size,
+                       const int* radii, const float* dL_dpix,
+                       float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                       float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                       float* dL_dview2gaussian, unsigned flags /* F3DG_FLAG_BG_PER_VIEW as in the forward */);
 
 /* Gaussians -> points integration: Rasterizer::integrate (rasterizer.h:92-123, rasterizer_impl.cu:530-792) as bound by
  * IntegrateGaussiansToPointsCUDA (rasterize_points.cu:233-343, `_C.integrate_gaussians_to_points`). One view.
@@ -320,6 +349,14 @@ int f3dg_render_epilogue(void* stream, int n_views, int H, int W, const float* r
 int f3dg_render_epilogue_view(void* stream, int n_views, int H, int W, const float* raster,
                               const float* world_view, float fx, float fy,
                               float* normal_world, float* depth_normal);
+/* Vector-Jacobian product of f3dg_render_epilogue_view with respect to raster: the cotangents dL_dnormal_world and dL_ddepth_normal
+ * ([n_views,3,H,W]; either may be NULL = all zero) are ADDED into channels 3..5 and 6 of dL_dpix [n_views,9,H,W]; no other channel
+ * is touched. One thread per (view, pixel); the depth channel is a gather over the up to four interior axial neighbours whose
+ * depth normal reads this pixel, summed in a fixed order: no atomics, bit-reproducible. F.normalize's backward, with g / 1e-12
+ * where its clamp is active. */
+int f3dg_render_epilogue_backward(void* stream, int n_views, int H, int W, const float* raster,
+                                  const float* world_view, float fx, float fy,
+                                  const float* dL_dnormal_world, const float* dL_ddepth_normal, float* dL_dpix);
 
 /* 8-bit RGB frames for the video writer and the multi-GPU gather: dst [n_frames,H,W,3] uint8 =
  * (uint8)(255 * clamp(src[:, 0:3], 0, 1)) with src [n_frames,src_channels,H,W] float32 planar (src_channels = 9 for the
