@@ -1,0 +1,233 @@
+"""Mesh extraction (the reference's scripts/test_mesh.sh route, visualize.py:440-548): everything between the opacity sweeps.
+
+    points, points_scale = tetra_points(world_views, near, far, fov, rotation, xyz, scale)      # visualize.py:120-144
+    cells = ...                                   # any [F,4] tetrahedralisation of `points` (the reference: CGAL, on the host)
+    mesh = extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, camera_centers, bg, cfg)
+    ply.save_mesh_ply(path, mesh["vertices_filtered"], mesh["faces_filtered"])
+
+``marching_tetrahedra`` has the signature and return structure of src/utils_tetmesh.py:141-190. Its integer topology (which edges cross
+the level set, their order, the triangles) is the HIP library's (f3dg_marching_tets_count / _emit, csrc/f3dg_mesh.hip); the three
+gathers are plain torch indexing, so the result stays differentiable in ``vertices`` and ``sdf`` exactly as in the reference.
+No CPU fallback: tensors that are not on a HIP device raise."""
+import ctypes as C
+import math
+
+import torch
+
+from . import _lib
+from .diff_gof_rasterization import _stream
+
+# largest workspace that is sized for the worst case (four crossing edges per tetrahedron, 32 B each) without looking at the data
+_WORST_CASE_BYTES = 4 << 30
+
+
+def _require_hip(*tensors):
+    for t in tensors:
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError("f3dgaus_amd.mesh needs tensors on a HIP device (no CPU fallback)")
+
+
+def marching_tets_topology(sdf, tets, max_edges=None):
+    """sdf [N] float32, tets [F,4] int64 (or int32), both on one HIP device -> (interp_v [E,2] int64, faces [n1 + 2 n2, 3] int64).
+
+    interp_v: the unique edges with exactly one occupied end (sdf > 0; NaN and 0 are outside) as (lo, hi), lo < hi, in ascending
+    lexicographic order. faces: rows of interp_v; first the triangles of the one-triangle surface tetrahedra in tetrahedron order, then
+    the two triangles of every two-triangle tetrahedron in tetrahedron order. That is _unbatched_marching_tetrahedra's output for up to
+    32 Mi tetrahedra; above that the reference recurses over chunks and returns ANOTHER PERMUTATION of the same faces, while this
+    function always works in one piece and keeps the unchunked order. Two blocking host reads (the counts, then E). A tetrahedron with
+    an id outside [0, N) raises (the kernel checks every id before it indexes anything). ``max_edges``: workspace capacity for the
+    crossing edges, duplicates included; default 4 F (always enough) while that workspace stays under 4 GiB, F beyond (the call is
+    repeated with the exact count if that is too small)."""
+    _require_hip(sdf, tets)
+    if sdf.dim() != 1 or sdf.dtype != torch.float32:
+        raise ValueError(f"sdf must be [N] float32, got {tuple(sdf.shape)} {sdf.dtype}")
+    if tets.dim() != 2 or tets.shape[1] != 4 or tets.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"tets must be [F,4] int64 or int32, got {tuple(tets.shape)} {tets.dtype}")
+    if tets.device != sdf.device:
+        raise ValueError("sdf and tets must be on the same device")
+    N, F = int(sdf.shape[0]), int(tets.shape[0])
+    dev = sdf.device
+    if F == 0:
+        if N <= 0:
+            raise ValueError("sdf is empty")
+        return torch.empty((0, 2), dtype=torch.int64, device=dev), torch.empty((0, 3), dtype=torch.int64, device=dev)
+    sdf, tets = sdf.detach().contiguous(), tets.contiguous()
+    L = _lib.lib()
+    is32 = int(tets.dtype == torch.int32)
+    cap = int(max_edges) if max_edges is not None else (4 * F if 32 * 4 * F <= _WORST_CASE_BYTES else F)
+    cap = max(0, min(cap, 4 * F))
+    counts = (C.c_longlong * 4)()
+    with torch.cuda.device(dev):
+        while True:
+            nbytes = L.f3dg_marching_tets_workspace_bytes(N, F, cap)
+            if nbytes == 0:
+                raise _lib.F3dgError(_lib.ERR_BAD_ARG, "f3dg_marching_tets_workspace_bytes")
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            rc = L.f3dg_marching_tets_count(_stream(), _lib.ptr(ws), nbytes, N, F, cap, _lib.ptr(sdf), _lib.ptr(tets), is32, counts)
+            if rc == _lib.ERR_OVERFLOW and counts[3] > cap:
+                cap = int(counts[3])
+                continue
+            _lib.check(rc, "f3dg_marching_tets_count")
+            break
+        E, n_one, n_two = int(counts[0]), int(counts[1]), int(counts[2])
+        interp_v = torch.empty((E, 2), dtype=torch.int64, device=dev)
+        faces = torch.empty((n_one + 2 * n_two, 3), dtype=torch.int64, device=dev)
+        if E > 0:
+            _lib.check(L.f3dg_marching_tets_emit(_stream(), _lib.ptr(ws), nbytes, N, F, cap, _lib.ptr(tets), is32, n_one,
+                                                 _lib.ptr(interp_v), _lib.ptr(faces)), "f3dg_marching_tets_emit")
+    return interp_v, faces
+
+
+def marching_tetrahedra(vertices, tets, sdf, scales):
+    """``marching_tetrahedra`` of src/utils_tetmesh.py:141-190 (the docstring there is stale: this adapted version returns endpoint
+    PAIRS, not interpolated vertices). vertices [B,N,3], tets [F,4], sdf [B,N], scales [B,N,1] ->
+    ``(verts_list, scale_list, faces_list, interp_list)``, one entry per batch item:
+        verts_list[b]  = (vertices[b][interp_v] [E,2,3], sdf[b][interp_v][..., None] [E,2,1])
+        scale_list[b]  = scales[b][interp_v] [E,2,1]
+        faces_list[b]  [n1 + 2 n2, 3] int64, interp_list[b] = interp_v [E,2] int64
+    Order of interp_v and of the faces: see ``marching_tets_topology`` (the reference's, unchunked)."""
+    _require_hip(vertices, tets, sdf, scales)
+    if vertices.dim() != 3 or vertices.shape[-1] != 3:
+        raise ValueError(f"vertices must be [B,N,3], got {tuple(vertices.shape)}")
+    B, N = vertices.shape[:2]
+    if tuple(sdf.shape) != (B, N):
+        raise ValueError(f"sdf must be [B,N] = {(B, N)}, got {tuple(sdf.shape)}")
+    if scales.dim() != 3 or tuple(scales.shape[:2]) != (B, N):
+        raise ValueError(f"scales must be [B,N,1], got {tuple(scales.shape)}")
+    if sdf.dtype != torch.float32:
+        raise ValueError(f"sdf must be float32, got {sdf.dtype}")
+    outs = []
+    for b in range(B):
+        interp_v, faces = marching_tets_topology(sdf[b], tets)
+        flat = interp_v.reshape(-1)
+        edges_to_interp = vertices[b][flat].reshape(-1, 2, 3)
+        edges_to_interp_sdf = sdf[b][flat].reshape(-1, 2, 1)
+        verts_scales = scales[b][flat].reshape(-1, 2, 1)
+        outs.append(((edges_to_interp, edges_to_interp_sdf), verts_scales, faces, interp_v))
+    return list(zip(*outs))
+
+
+def build_rotation(r):
+    """visualize.py:42-63: rotation matrices [P,3,3] of (unnormalised) quaternions [P,4] (w, x, y, z), in its float32 operation order."""
+    norm = torch.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + r[:, 2] * r[:, 2] + r[:, 3] * r[:, 3])
+    q = r / norm[:, None]
+    R = torch.zeros((q.size(0), 3, 3), device=r.device, dtype=r.dtype)
+    r, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    R[:, 0, 0] = 1 - 2 * (y * y + z * z)
+    R[:, 0, 1] = 2 * (x * y - r * z)
+    R[:, 0, 2] = 2 * (x * z + r * y)
+    R[:, 1, 0] = 2 * (x * y + r * z)
+    R[:, 1, 1] = 1 - 2 * (x * x + z * z)
+    R[:, 1, 2] = 2 * (y * z - r * x)
+    R[:, 2, 0] = 2 * (x * z - r * y)
+    R[:, 2, 1] = 2 * (y * z + r * x)
+    R[:, 2, 2] = 1 - 2 * (x * x + y * y)
+    return R
+
+
+def fov2focal(fov, pixels):
+    return pixels / (2 * math.tan(fov / 2))
+
+
+@torch.no_grad()
+def frustum_mask(points, world_views, near=0.02, far=1e6, fov=60, resolution=256):
+    """visualize.py:72-117: True where a point projects into the image of at least one context view with near <= depth <= far.
+    world_views [V,4,4] (or [V,1,4,4]) are the transposed view matrices the renderer takes. As in the reference the image is
+    ``resolution`` = 256 pixels square and the focal length is ``fov2focal(fov, 256)``, i.e. ``fov`` is read in radians there."""
+    H = W = int(resolution)
+    focal = fov2focal(fov, resolution)
+    V = world_views.reshape(-1, 4, 4).shape[0]
+    intrinsics = torch.tensor([[focal, 0, W / 2], [0, focal, H / 2], [0, 0, 1]], dtype=torch.float32, device=points.device).expand(V, 3, 3)
+    view_matrices = world_views.reshape(-1, 4, 4).transpose(1, 2)
+    homo_points = torch.cat([points, torch.ones_like(points[:, 0]).unsqueeze(-1)], dim=-1)
+    view_points = torch.einsum("vbc,nc->vnb", view_matrices, homo_points)[:, :, :3]
+    uv_points = torch.einsum("vbc,vnc->vnb", intrinsics, view_points)
+    z = uv_points[:, :, -1:]
+    uv_points = uv_points[:, :, :2] / z
+    u, v = uv_points[:, :, 0], uv_points[:, :, 1]
+    depth = view_points[:, :, -1]
+    cull_near_fars = (depth >= near) & (depth <= far)
+    return torch.any(cull_near_fars & (u >= 0) & (u <= W - 1) & (v >= 0) & (v <= H - 1), dim=0)
+
+
+@torch.no_grad()
+def tetra_points(world_views, near, far, fov, rotation, xyz, scale, return_unmasked=False):
+    """``get_tetra_points`` (visualize.py:120-144): the point set that is tetrahedralised. Every Gaussian contributes the eight corners
+    of its box, ``xyz + R (+-3 s)``, then all centres follow; the per-point scale is the largest axis of 3 s; points outside every
+    context view (``frustum_mask``) are dropped. Returns (points [n,3], points_scale [n,1]).
+
+    The reference takes the corner order from ``trimesh.creation.box()``; that order is NOT pinned here (trimesh is not a dependency):
+    the corners are in binary counting order with x slowest, (-,-,-) (-,-,+) (-,+,-) ... (+,+,+). Another corner order relabels the
+    tetrahedra and moves no vertex of the mesh. ``return_unmasked``: also return the 9 P points, their scales and the mask."""
+    _require_hip(world_views, rotation, xyz, scale)
+    rots = build_rotation(rotation)
+    scale3 = torch.sqrt(torch.square(scale) + 0) * 3.
+    signs = torch.tensor([[-1. if not (k >> (2 - a)) & 1 else 1. for k in range(8)] for a in range(3)], dtype=torch.float32, device=xyz.device)
+    vertices = signs.unsqueeze(0).repeat(xyz.shape[0], 1, 1)              # [P,3,8]
+    vertices = vertices * scale3.unsqueeze(-1)
+    vertices = torch.bmm(rots, vertices).squeeze(-1) + xyz.unsqueeze(-1)
+    vertices = vertices.permute(0, 2, 1).reshape(-1, 3).contiguous()
+    vertices = torch.cat([vertices, xyz], dim=0)
+    smax = scale3.max(dim=-1, keepdim=True)[0]
+    vertices_scale = torch.cat([smax.repeat(1, 8).reshape(-1, 1), smax], dim=0)
+    vertex_mask = frustum_mask(vertices, world_views, near, far, fov)
+    out = (vertices[vertex_mask], vertices_scale[vertex_mask])
+    return out + (vertices, vertices_scale, vertex_mask) if return_unmasked else out
+
+
+@torch.no_grad()
+def bisect_level_set(sweep, end_points, end_sdf, n_steps=8):
+    """The binary search of visualize.py:480-516 on the edges marching tetrahedra returned: ``end_points`` [E,2,3], ``end_sdf`` [E,2,1]
+    (one end on either side of the level set), ``sweep(points [n,3]) -> final_alpha [n]`` (an ``AlphaSweep``). Every step evaluates
+    sdf = (1 - sweep(mid)) - 0.5 at the midpoint (l + r) / 2 and moves the LEFT end there when the midpoint's sdf has the strict sign
+    of the left end's, the RIGHT end otherwise -- a midpoint sdf of exactly 0 moves the right end, as in the reference. Returns the
+    final midpoints [E,3]. torch.where instead of the reference's boolean-mask assignments: no host synchronisation per step, and the
+    inputs are left untouched (the reference moves the ends inside ``end_points``)."""
+    left_points, right_points = end_points[:, 0, :], end_points[:, 1, :]
+    left_sdf, right_sdf = end_sdf[:, 0, :], end_sdf[:, 1, :]
+    if end_points.shape[0] == 0:
+        return (left_points + right_points) / 2
+    for _ in range(int(n_steps)):
+        mid_points = (left_points + right_points) / 2
+        alpha = 1 - sweep(mid_points.contiguous())
+        mid_sdf = (alpha - 0.5).reshape(-1, 1)
+        ind_low = ((mid_sdf < 0) & (left_sdf < 0)) | ((mid_sdf > 0) & (left_sdf > 0))
+        left_sdf = torch.where(ind_low, mid_sdf, left_sdf)
+        right_sdf = torch.where(ind_low, right_sdf, mid_sdf)
+        left_points = torch.where(ind_low, mid_points, left_points)
+        right_points = torch.where(ind_low, right_points, mid_points)
+    return (left_points + right_points) / 2
+
+
+@torch.no_grad()
+def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, camera_centers, bg, cfg, n_binary_steps=8, sweep=None):
+    """visualize.py:447-546 for image ``bs`` of the Gaussian dict ``pc``: alpha of ``points`` [n,3] over all cameras (one ``AlphaSweep``,
+    built here unless one is handed in), marching tetrahedra of ``cells`` [F,4] (any tetrahedralisation of ``points``; the reference's
+    is CGAL on the host) on sdf = alpha - 0.5, ``n_binary_steps`` bisection steps, and the scale filter
+    ``|left - right| <= 3 (left_scale + right_scale)`` on the INITIAL edge ends (``points_scale`` [n,1]). Returns a dict:
+        vertices [E,3], faces [nf,3] int64, keep [E] bool                      the unfiltered mesh and the filter
+        vertices_filtered, faces_filtered                                      the kept vertices and the faces whose three corners
+                                                                               are kept, re-indexed (what update_vertices /
+                                                                               update_faces leave, :545-546)"""
+    from .gaussian_renderer import AlphaSweep
+    _require_hip(points, points_scale, cells)
+    own = sweep is None
+    if own:
+        sweep = AlphaSweep(pc, bs, world_views, full_projs, camera_centers, bg, cfg, max_points=points.shape[0])
+    alpha = 1 - sweep(points)
+    sdf = (alpha - 0.5)[None]
+    verts_list, scale_list, faces_list, _ = marching_tetrahedra(points[None], cells, sdf, points_scale[None])
+    end_points, end_sdf = verts_list[0]
+    end_scales = scale_list[0]
+    faces = faces_list[0]
+    E = end_points.shape[0]
+    distance = torch.norm(end_points[:, 0, :] - end_points[:, 1, :], dim=-1)
+    scale = end_scales[:, 0, 0] + end_scales[:, 1, 0]
+    if own and E > points.shape[0]:         # more crossing edges than points: the sweep's per-point arrays were sized for the points
+        sweep = AlphaSweep(pc, bs, world_views, full_projs, camera_centers, bg, cfg, max_points=E)
+    vertices = bisect_level_set(sweep, end_points, end_sdf, n_binary_steps)
+    keep = distance <= 3 * scale
+    face_mask = keep[faces].all(dim=1)
+    new_index = torch.cumsum(keep.to(torch.int64), 0) - 1
+    return {"vertices": vertices, "faces": faces, "keep": keep,
+            "vertices_filtered": vertices[keep], "faces_filtered": new_index[faces[face_mask]]}

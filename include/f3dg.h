@@ -35,6 +35,8 @@
  *       the torch post-processing of render_predicted_more_v2_gof  src/gaussian_renderer/__init__.py:881-909, 1043-1053
  *   f3dg_render_epilogue_backward
  *       what torch.autograd derives from those same lines (they are plain torch ops on the raster in the reference)
+ *   f3dg_marching_tets_count / f3dg_marching_tets_emit
+ *       the integer topology of _unbatched_marching_tetrahedra     src/utils_tetmesh.py:47-138 (torch.unique + mask indexing there)
  *
  * Memory ownership mirrors the reference: outputs and the workspace are allocated and owned by the caller
  * (torch tensors on the Python side). Instead of growing buffers through callbacks in the middle of the call
@@ -298,6 +300,30 @@ int f3dg_debug_integrate_redo(void* stream, const void* workspace, int P, int PN
 /* present[i] = (view-space z of means3D[i] > 0.2), auxiliary.h:177-202. present is uint8 [P]. */
 int f3dg_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix,
                       const float* projmatrix, uint8_t* present);
+
+/* Marching tetrahedra, the integer topology of _unbatched_marching_tetrahedra (src/utils_tetmesh.py:47-138) in two calls on one
+ * caller-owned workspace (the output sizes depend on the data; the caller allocates them between the calls):
+ *   sdf [N] float32; tets [F,4] point ids, int64 (tets_int32 == 0) or int32 (!= 0). A point is occupied when sdf > 0 (NaN and 0 are
+ *   outside); a tetrahedron is on the surface when 1..3 of its corners are; its case index is sum occ_i 2^i over its corners as given.
+ *   interp_v [E,2] int64: the unique edges with exactly one occupied end as (lo, hi), lo < hi, in ascending lexicographic order.
+ *   faces [n_one + 2 n_two, 3] int64: rows of interp_v; first the triangle of every one-triangle surface tetrahedron in tetrahedron
+ *   order, then the two triangles of every two-triangle one in tetrahedron order (triangle_table, utils_tetmesh.py:23-43). A duplicate
+ *   tetrahedron gives duplicate faces. All of F is worked in one piece: above 32 Mi tetrahedra the reference recurses over chunks and
+ *   returns another permutation of the same faces.
+ * max_edges: capacity for the crossing edges of all surface tetrahedra, duplicates included (3 or 4 per surface tetrahedron; 4 F always
+ *   suffices and is the largest value accepted).
+ * f3dg_marching_tets_count: BLOCKING, two host reads (the counts after the classification, then E; one if nothing crosses, none if
+ *   F == 0). h_counts[0..3] = E, n_one, n_two, crossing edges counted. F3DG_ERR_OVERFLOW: more crossing edges than max_edges;
+ *   h_counts[3] is the capacity to retry with. F3DG_ERR_BAD_ARG: NULL pointers, N <= 0, F < 0, N or F >= 2^31, or a tetrahedron with an
+ *   id outside [0, N) -- every id is range-checked on the device before anything is indexed with it. F3DG_ERR_UNSUPPORTED: 2^31 or more
+ *   crossing edges. F == 0 is legal (all counts 0, tets may be NULL).
+ * f3dg_marching_tets_emit: after a f3dg_marching_tets_count that returned F3DG_OK with E > 0, same workspace, sizes and tets; n_one is
+ *   h_counts[1]. Writes every element of interp_v [E,2] and faces [n_one + 2 n_two, 3]. No host read. Bit-reproducible. */
+size_t f3dg_marching_tets_workspace_bytes(long long N, long long F, long long max_edges);
+int f3dg_marching_tets_count(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, long long max_edges,
+                             const float* sdf, const void* tets, int tets_int32, long long* h_counts);
+int f3dg_marching_tets_emit(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, long long max_edges,
+                            const void* tets, int tets_int32, long long n_one, long long* interp_v, long long* faces);
 
 /* Cycle-aggregative projection ("splat head", src/gaussian_predictor.py:857-881, 961-1007) for B images:
  *   net_out [B,23,H,W] planar: offset 0:3, opacity 3, scaling 4:7, rotation 7:11, features_dc 11:14, features_rest 14:23

@@ -1,0 +1,177 @@
+"""Marching tetrahedra on the GPU (f3dg_marching_tets_count / _emit through f3dgaus_amd.mesh): the reference's own outputs
+(tests/golden/marching_tets.npz) and, on larger inputs, the numpy restatement of tests/mesh_truth.py -- everything compared exactly.
+
+The larger inputs are the smallest at which every path of csrc/f3dg_mesh.hip runs: several workgroups of tetrahedra (17^3 Kuhn grid:
+96 of 256), buckets sorted by one thread (at most 32 entries), in LDS (33 .. 8192: the small fan, 1,080 entries in one bucket) and in
+place in global memory (the fan: 11,700 entries in one bucket), and the three bucket sizes around the first threshold (30, 32, 33)."""
+import numpy as np
+import pytest
+import torch
+
+import mesh_truth
+from mesh_truth import CASES, GOLDEN
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(GOLDEN)
+
+
+def _star(n_tets, extra_inside):
+    """Vertex 0 inside, 1..20 outside, n_tets tetrahedra (0, a, b, c): 3 n_tets entries in bucket 0. extra_inside: one more tetrahedron
+    (0, 21, a, b) with 21 inside as well adds two entries to bucket 0 (and two edges that end in 21)."""
+    rng = np.random.default_rng(n_tets)
+    sdf = np.full(22, -1.0, dtype=np.float32)
+    sdf[0] = 1.0
+    tets = [np.concatenate([[0], rng.choice(np.arange(1, 21), 3, replace=False)]) for _ in range(n_tets)]
+    if extra_inside:
+        sdf[21] = 2.0
+        tets.append(np.array([0, 21, 5, 9]))
+    tets = np.stack(tets).astype(np.int64)
+    tets = np.take_along_axis(tets, np.argsort(rng.random(tets.shape), axis=1), 1)
+    return sdf, np.ascontiguousarray(tets)
+
+
+def _large(name):
+    if name == "kuhn17":
+        pts, tets = mesh_truth.kuhn_grid(17)
+        return mesh_truth.noisy_sphere_sdf(pts, 4), mesh_truth.permuted(tets, 3)
+    if name == "fan":
+        _, sdf, tets = mesh_truth.fan(False)
+        return sdf, tets
+    if name == "fan_centre_last":
+        _, sdf, tets = mesh_truth.fan(True)
+        return sdf, tets
+    if name == "fan_small":
+        _, sdf, tets = mesh_truth.fan(False, n_lat=10, n_lon=20)
+        return sdf, tets
+    return {"star30": _star(10, False), "star32": _star(10, True), "star33": _star(11, False)}[name]
+
+
+@pytest.fixture(scope="module")
+def truth():
+    """The restatement of every larger input, computed once."""
+    out = {}
+    for name in ("kuhn17", "fan", "fan_centre_last", "fan_small", "star30", "star32", "star33"):
+        sdf, tets = _large(name)
+        out[name] = (sdf, tets) + mesh_truth.marching_tets(sdf, tets)
+    return out
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_library_equals_the_reference(f3d, gpu_device, golden, name):
+    dev = gpu_device
+    g = lambda k: torch.from_numpy(golden[name + "_" + k]).to(dev)
+    verts_list, scale_list, faces_list, interp_list = f3d.mesh.marching_tetrahedra(g("vertices")[None], g("tets"), g("sdf")[None], g("scales")[None])
+    assert len(verts_list) == len(scale_list) == len(faces_list) == len(interp_list) == 1
+    (end_points, end_sdf), end_scales, faces, interp_v = verts_list[0], scale_list[0], faces_list[0], interp_list[0]
+    assert interp_v.dtype == torch.int64 and faces.dtype == torch.int64
+    assert interp_v.shape == g("interp_v").shape and torch.equal(interp_v, g("interp_v"))
+    assert faces.shape == g("faces").shape and torch.equal(faces, g("faces"))
+    assert end_points.shape == g("end_points").shape and torch.equal(_bits(end_points), _bits(g("end_points")))
+    assert end_sdf.shape == g("end_sdf").shape and torch.equal(_bits(end_sdf), _bits(g("end_sdf")))
+    assert end_scales.shape == g("end_scales").shape and torch.equal(_bits(end_scales), _bits(g("end_scales")))
+    if name != "outside":
+        assert len(interp_v) > 0 and len(faces) > 0
+    else:
+        assert interp_v.shape == (0, 2) and faces.shape == (0, 3)
+
+
+@pytest.mark.parametrize("name", ("kuhn17", "fan", "fan_centre_last", "fan_small", "star30", "star32", "star33"))
+@pytest.mark.parametrize("dtype", (torch.int64, torch.int32))
+def test_library_equals_the_restatement(f3d, gpu_device, truth, name, dtype):
+    sdf, tets, interp_v, faces, stats = truth[name]
+    if name == "kuhn17":
+        assert len(tets) == 24576 and len(sdf) == 4913
+    if name == "fan":
+        assert stats["emitted"] == 11700 and len(interp_v) == 2000 and (interp_v[:, 0] == 0).all()
+    if name == "fan_centre_last":
+        assert len(interp_v) == 2000 and (interp_v[:, 1] == 2000).all()
+    assert len(interp_v) > 0 and len(faces) > 0
+    iv, fc = f3d.mesh.marching_tets_topology(torch.from_numpy(sdf).to(gpu_device), torch.from_numpy(tets).to(gpu_device, dtype))
+    assert len(iv) > 0 and len(fc) > 0
+    assert iv.dtype == torch.int64 and torch.equal(iv.cpu(), torch.from_numpy(interp_v))
+    assert fc.dtype == torch.int64 and torch.equal(fc.cpu(), torch.from_numpy(faces))
+
+
+def test_a_small_edge_capacity_is_grown(f3d, gpu_device, truth):
+    """max_edges below the crossing-edge count: the C call reports the count it needs and the operator repeats it."""
+    from f3dgaus_amd import _lib
+    import ctypes as C
+    sdf, tets, interp_v, faces, stats = truth["star33"]
+    s, t = torch.from_numpy(sdf).to(gpu_device), torch.from_numpy(tets).to(gpu_device)
+    L = _lib.lib()
+    nbytes = L.f3dg_marching_tets_workspace_bytes(len(sdf), len(tets), 5)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=gpu_device)
+    counts = (C.c_longlong * 4)()
+    rc = L.f3dg_marching_tets_count(None, _lib.ptr(ws), nbytes, len(sdf), len(tets), 5, _lib.ptr(s), _lib.ptr(t), 0, counts)
+    assert rc == _lib.ERR_OVERFLOW and counts[3] == stats["emitted"] == 33
+    iv, fc = f3d.mesh.marching_tets_topology(s, t, max_edges=5)
+    assert torch.equal(iv.cpu(), torch.from_numpy(interp_v)) and torch.equal(fc.cpu(), torch.from_numpy(faces))
+
+
+def test_batch_of_two_and_repeatability(f3d, gpu_device, truth):
+    sdf_a, tets, iv_a, f_a, _ = truth["kuhn17"]
+    pts, _ = mesh_truth.kuhn_grid(17)
+    sdf_b = mesh_truth.noisy_sphere_sdf(pts, 9, radius=0.25, centre=(0.4, 0.55, 0.5))
+    iv_b, f_b, _ = mesh_truth.marching_tets(sdf_b, tets)
+    assert len(iv_b) > 0 and len(f_b) > 0 and len(iv_b) != len(iv_a)
+    dev = gpu_device
+    vertices = torch.from_numpy(pts).to(dev)[None].repeat(2, 1, 1)
+    vertices[1] += 1.0
+    sdf = torch.from_numpy(np.stack([sdf_a, sdf_b])).to(dev)
+    scales = torch.rand(2, len(pts), 1, device=dev)
+    t = torch.from_numpy(tets).to(dev)
+    runs = [f3d.mesh.marching_tetrahedra(vertices, t, sdf, scales) for _ in range(2)]
+    verts_list, scale_list, faces_list, interp_list = runs[0]
+    assert len(interp_list) == 2
+    for b, (iv, fc) in enumerate(((iv_a, f_a), (iv_b, f_b))):
+        assert torch.equal(interp_list[b].cpu(), torch.from_numpy(iv)) and torch.equal(faces_list[b].cpu(), torch.from_numpy(fc))
+        assert len(interp_list[b]) > 0 and len(faces_list[b]) > 0
+        assert torch.equal(verts_list[b][0], vertices[b][interp_list[b]])
+        assert torch.equal(verts_list[b][1], sdf[b][interp_list[b]][..., None])
+        assert torch.equal(scale_list[b], scales[b][interp_list[b]])
+        # two runs are bit-identical
+        assert torch.equal(runs[1][3][b], interp_list[b]) and torch.equal(runs[1][2][b], faces_list[b])
+        assert torch.equal(runs[1][0][b][0], verts_list[b][0])
+
+
+def test_gathers_stay_differentiable(f3d, gpu_device, golden):
+    g = lambda k: torch.from_numpy(golden["kuhn6_" + k]).to(gpu_device)
+    vertices, sdf = g("vertices")[None].requires_grad_(), g("sdf")[None].requires_grad_()
+    verts_list, _, _, interp_list = f3d.mesh.marching_tetrahedra(vertices, g("tets"), sdf, g("scales")[None])
+    (verts_list[0][0].sum() + 2 * verts_list[0][1].sum()).backward()
+    uses = torch.bincount(interp_list[0].reshape(-1), minlength=sdf.shape[1]).float()
+    assert uses.sum() > 0
+    assert torch.equal(vertices.grad[0], uses[:, None].expand(-1, 3)) and torch.equal(sdf.grad[0], 2 * uses)
+
+
+def test_no_tetrahedra_gives_empty_outputs(f3d, gpu_device):
+    sdf = torch.tensor([[1.0, -1.0, 0.5]], device=gpu_device)
+    tets = torch.zeros((0, 4), dtype=torch.int64, device=gpu_device)
+    verts_list, scale_list, faces_list, interp_list = f3d.mesh.marching_tetrahedra(
+        torch.zeros(1, 3, 3, device=gpu_device), tets, sdf, torch.ones(1, 3, 1, device=gpu_device))
+    assert interp_list[0].shape == (0, 2) and faces_list[0].shape == (0, 3) and interp_list[0].dtype == torch.int64
+    assert verts_list[0][0].shape == (0, 2, 3) and verts_list[0][1].shape == (0, 2, 1) and scale_list[0].shape == (0, 2, 1)
+
+
+@pytest.mark.parametrize("bad", ("equal_to_N", "negative", "beyond_int32"))
+def test_an_id_out_of_range_raises(f3d, gpu_device, bad):
+    """The kernel range-checks every id before it indexes anything: the call reports a bad argument, nothing faults, and the device
+    works afterwards."""
+    sdf = torch.tensor([-1.0, -1.0, 0.5, 0.5, 1.0], device=gpu_device)
+    value = {"equal_to_N": 5, "negative": -1, "beyond_int32": (1 << 32) + 2}[bad]
+    tets = torch.tensor([[0, 1, 2, 3], [0, 1, 2, value], [1, 2, 3, 4]], dtype=torch.int64, device=gpu_device)
+    with pytest.raises(RuntimeError, match="bad argument"):
+        f3d.mesh.marching_tets_topology(sdf, tets)
+    good = tets.clone()
+    good[1, 3] = 4
+    iv, fc = f3d.mesh.marching_tets_topology(sdf, good)
+    iv_t, fc_t, _ = mesh_truth.marching_tets(sdf.cpu().numpy(), good.cpu().numpy())
+    assert len(iv) > 0 and torch.equal(iv.cpu(), torch.from_numpy(iv_t)) and torch.equal(fc.cpu(), torch.from_numpy(fc_t))
