@@ -70,6 +70,55 @@ def per_gaussian_truth(scene, view_idx, radii, dL_dv2g, dL_dcolor):
                 dL_dsh=None if shs is None else shs.grad.numpy())
 
 
+def _views_chain(scene, views, radii, dL_dv2g, dL_dcolor, n_sets, magnitude):
+    """The float64 chain rule of the listed views, summed (magnitude False), or the sum of the absolute values of its single-input
+    parts (magnitude True: one backward pass per column of dL_dv2g, one for the colour path)."""
+    t64 = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)
+    views = list(views)
+    V = len(views)
+    radii = np.asarray(radii).reshape(V, -1)
+    P, vps = radii.shape[1], V // n_sets
+    assert vps * n_sets == V and scene["means3D"].shape[0] == n_sets * P
+    dL_dv2g, dL_dcolor = np.asarray(dL_dv2g).reshape(V, P, 10), np.asarray(dL_dcolor).reshape(V, P, 3)
+    out = dict(dL_dmean3D=np.zeros((n_sets * P, 3)), dL_dscale=np.zeros((n_sets * P, 3)), dL_drot=np.zeros((n_sets * P, 4)),
+               dL_dsh=None if scene["shs"] is None else np.zeros(tuple(scene["shs"].shape)))
+    fold = (lambda g: g.abs().numpy()) if magnitude else (lambda g: g.numpy())
+    for i, vi in enumerate(views):
+        rows = slice((i // vps) * P, (i // vps + 1) * P)            # the Gaussians of this view's set
+        means = t64(scene["means3D"][rows]).requires_grad_(True)
+        scales = t64(scene["scales"][rows]).requires_grad_(True)
+        rots = t64(scene["rotations"][rows]).requires_grad_(True)
+        vis = torch.tensor(radii[i] > 0)                            # the kernel's  if (!(radii[idx] > 0)) continue
+        prod = view2gaussian64(means, scales, rots, t64(scene["viewmatrix"][vi])) * t64(dL_dv2g[i])
+        losses = [prod[:, c][vis].sum() for c in range(10)] if magnitude else [prod[vis].sum()]
+        for L in losses:
+            grads = torch.autograd.grad(L, (means, scales, rots), retain_graph=True, allow_unused=True)
+            for k, g in zip(("dL_dmean3D", "dL_dscale", "dL_drot"), grads):
+                if g is not None:       # (columns 0..5 are the gradient of Sigma, which does not depend on the mean)
+                    out[k][rows] += fold(g)
+        if scene["shs"] is not None:
+            shs = t64(scene["shs"][rows]).requires_grad_(True)
+            col = colour64(means, shs, t64(scene["campos"][vi]), scene["sh_degree"])
+            gm, gsh = torch.autograd.grad((col * t64(dL_dcolor[i]))[vis].sum(), (means, shs))
+            out["dL_dmean3D"][rows] += fold(gm)
+            out["dL_dsh"][rows] += fold(gsh)
+    return out
+
+
+def per_gaussian_truth_views(scene, views, radii, dL_dv2g, dL_dcolor, n_sets=1):
+    """per_gaussian_truth summed over the listed views (indices into the scene's cameras): radii [V,P], dL_dv2g [V,P,10], dL_dcolor
+    [V,P,3], row i belonging to views[i]; each view restricted to its rows with radii > 0. n_sets > 1: the Gaussian tensors are
+    [n_sets * P, ...] and the views of set s are rows s * V/n_sets .. (s + 1) * V/n_sets; each set is summed over its own views only."""
+    return _views_chain(scene, views, radii, dL_dv2g, dL_dcolor, n_sets, False)
+
+
+def per_gaussian_term_magnitude(scene, views, radii, dL_dv2g, dL_dcolor, n_sets=1):
+    """A per output element: the sum over the views and over the ten columns of dL_dv2g of |the contribution of that one column alone|
+    (ten backward passes per view, the other nine columns zeroed), plus |the contribution of the colour path alone| (dL_dmean3D and
+    dL_dsh). The net gradient is a strong cancellation of these parts; 2^-24 * A is the scale of ONE float32 rounding of them."""
+    return _views_chain(scene, views, radii, dL_dv2g, dL_dcolor, n_sets, True)
+
+
 def compositing_truth(scene, o, weights, view_idx=0):
     """float64 autograd of the compositing stage for a loss  sum(weights[0:6] * out[0:6])  (RGB + normal channels:
     the channels whose gradient the reference differentiates completely). The per-tile lists, the per-pixel number of
