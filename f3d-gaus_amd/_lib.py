@@ -82,6 +82,11 @@ SIGNATURES = {
     "f3dg_residual_join_bf16": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _f, _p]),
     "f3dg_group_norm_silu_nhwc": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _f, _i, _p, _p, _sz]),
     "f3dg_group_norm_silu_nhwc_bf16": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _f, _i, _p, _p, _sz]),
+    # n_planes W H  /  stream | n_planes W H | img1 img2 | map dm_dmu1 dm_dsigma1_sq dm_dsigma12 | partials partials_bytes plane_sums
+    "f3dg_ssim_partials_bytes": (_sz, [_i, _i, _i]),
+    "f3dg_ssim_forward": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    # stream | n_planes W H | img1 img2 | dL_dmap plane_weights | dm_dmu1 dm_dsigma1_sq dm_dsigma12 | dL_dimg1
+    "f3dg_ssim_backward": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "f3dg_set_option": (_i, [C.c_char_p, _i]),
     "f3dg_profile_enable": (_i, [_i]),
     "f3dg_debug_launch_count": (C.c_longlong, [_i]),

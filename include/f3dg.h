@@ -37,6 +37,9 @@
  *       what torch.autograd derives from those same lines (they are plain torch ops on the raster in the reference)
  *   f3dg_marching_tets_count / f3dg_marching_tets_emit
  *       the integer topology of _unbatched_marching_tetrahedra     src/utils_tetmesh.py:47-138 (torch.unique + mask indexing there)
+ *   f3dg_ssim_forward / f3dg_ssim_backward
+ *       ssim / _ssim, l1_loss, l2_loss and what torch.autograd derives from them   src/gaussian-splatting/utils/loss_utils.py:17-63
+ *       (the objective of src/gaussian-splatting/train.py:92) and psnr's mean squared error, utils/image_utils.py:17-19
  *
  * Memory ownership mirrors the reference: outputs and the workspace are allocated and owned by the caller
  * (torch tensors on the Python side). Instead of growing buffers through callbacks in the middle of the call
@@ -450,6 +453,43 @@ int f3dg_residual_join_bf16(void* stream, int N, int C, int HW, int nhwc, const 
                             const float* bias_b, float scale, uint16_t* y);
 int f3dg_residual_join_f16(void* stream, int N, int C, int HW, int nhwc, const uint16_t* a, const float* bias_a, const uint16_t* b,
                            const float* bias_b, float scale, uint16_t* y);
+
+/* Fused differentiable image loss: SSIM (+ L1, L2) of n_planes pairs of H x W planes -- a plane is one channel of one frame; img1, img2
+ * and every plane set below are float32, planar and contiguous, [n_planes, H, W].
+ * Definition (utils/loss_utils.py:23-63 with window_size 11):
+ *   g[i] = float32(exp(-(i - 5)^2 / 4.5)) divided by their float32 sum, i = 0..10 (six distinct values); G*x is the windowed sum of x,
+ *   zero-padded by 5 on every side, with the window g (x) g. The library evaluates it separably (11 + 11 taps, horizontal first); the
+ *   reference uses one 121-tap window whose entries are the float32-rounded products.
+ *   C1 = float32(0.01^2), C2 = float32(0.03^2); a = img1, b = img2; per pixel
+ *     mu1 = G*a, mu2 = G*b, sigma1^2 = G*(a a) - mu1^2, sigma2^2 = G*(b b) - mu2^2, sigma12 = G*(a b) - mu1 mu2
+ *     m = (2 mu1 mu2 + C1)(2 sigma12 + C2) / ((mu1^2 + mu2^2 + C1)(sigma1^2 + sigma2^2 + C2))
+ *   every operation one float32 rounding (no contraction).
+ * f3dg_ssim_forward writes, each optional (NULL = skip):
+ *   map            m
+ *   dm_dmu1, dm_dsigma1_sq, dm_dsigma12   the partial derivatives of m that f3dg_ssim_backward reads (dm_dmu1 with G*(a a) and G*(a b)
+ *                  held fixed, i.e. including the mu1 inside sigma1^2 and sigma12)
+ *   plane_sums     [n_planes,3]: the sums over the plane of m, of |a - b| and of (a - b)^2. Needs `partials`, a scratch buffer of
+ *                  f3dg_ssim_partials_bytes(n_planes, W, H) bytes (partials_bytes = its size): every tile writes its own slot, a second
+ *                  kernel adds the slots of a plane in a fixed order. No float atomics: the sums are bit-reproducible from run to run,
+ *                  and the sums of one plane do not depend on any other plane's data.
+ * f3dg_ssim_backward writes dL/dimg1 (every element) for
+ *   L = sum_q dL_dmap(q) m(q)  +  sum_planes ( w[0] sum m + w[1] sum |a - b| + w[2] sum (a - b)^2 ),   w = plane_weights [n_planes,3]
+ * from either cotangent or both (dL_dmap [n_planes,H,W]; NULL = absent). With plane_weights alone -- the case of a mean -- no gradient
+ * plane exists in memory.
+ *   dL/da(p) = sum_q g(q - p) [ w(q) dm_dmu1(q) + 2 a(p) w(q) dm_dsigma1_sq(q) + b(p) w(q) dm_dsigma12(q) ]
+ *              + w[1] sign(a - b)(p) + 2 w[2] (a - b)(p),     w(q) = dL_dmap(q) + w[0],  sign(0) = 0 (torch.abs's gradient)
+ * The three derivative planes are those a f3dg_ssim_forward on the same img1, img2 wrote; they are required (this library saves them
+ * rather than recompute them from a 10-pixel halo). img2 gets no gradient: m is symmetric, a caller who needs it swaps the arguments.
+ * F3DG_ERR_BAD_ARG: a NULL required pointer, non-positive sizes, plane_sums without partials, a backward with neither cotangent.
+ * F3DG_ERR_WORKSPACE: partials_bytes too small. F3DG_ERR_UNSUPPORTED: more than 2^31 - 1 tiles (32 x 16 pixels) in the call.
+ * f3dg_ssim_partials_bytes returns 0 for non-positive sizes. All checks happen before any HIP call. */
+size_t f3dg_ssim_partials_bytes(int n_planes, int W, int H);
+int f3dg_ssim_forward(void* stream, int n_planes, int W, int H, const float* img1, const float* img2, float* map,
+                      float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12, float* partials, size_t partials_bytes,
+                      float* plane_sums);
+int f3dg_ssim_backward(void* stream, int n_planes, int W, int H, const float* img1, const float* img2, const float* dL_dmap,
+                       const float* plane_weights, const float* dm_dmu1, const float* dm_dsigma1_sq, const float* dm_dsigma12,
+                       float* dL_dimg1);
 
 /* Runtime switches: process-wide DEFAULTS for what a call's own flags do not say (every arithmetic / list / path choice of a call has a
  * flag, above). The library knows sixteen names and one diagnostic pair; everything else returns F3DG_ERR_BAD_ARG.
