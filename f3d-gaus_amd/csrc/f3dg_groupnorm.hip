@@ -90,6 +90,17 @@ __device__ __forceinline__ void from_f32(unsigned short& d, float x) { d = f32_t
 __device__ __forceinline__ float to_f32(_Float16 x) { return (float)x; }
 __device__ __forceinline__ void from_f32(_Float16& d, float x) { d = (_Float16)x; }
 
+// The statistics. One pass gives the variance as E[v^2] - E[v]^2, and in float32 sums that difference loses log2(1 + (mean / std)^2) bits:
+// summing v and v^2 themselves, a slab whose mean lies ten standard deviations from zero came out 20x less accurate than torch's float32
+// GroupNorm on the device in the channels-last kernels (3x NCHW), thirty 55x (10x), a constant slab 30x (12x) outside the suite's bound
+// (tests/test_backbone_kernels_gpu.py). The variance does not see a shift, so the sums are taken of v - K with a pivot K that every thread
+// and workgroup of a (sample, group) reads from the same place: the slab's FIRST value (+ its pre_bias). The float sums then hold
+// deviations of the size of the spread, the partials are combined in float64 as before, mean = K + E[v - K]; the order of the additions,
+// and with it run-to-run bit-identity, is unchanged. The apply stage takes the mean off before it scales --
+// (x + (pre_bias - mean)) * (weight * rstd) + bias -- instead of forming bias - mean * weight * rstd, which rounds at the size of
+// |mean| / std. (pre_bias - mean is rounded once per channel, by as much as x + pre_bias would be per element; without a pre_bias it is
+// exact.) A non-finite K poisons its own slab only, which a non-finite value anywhere in the slab does anyway.
+//
 // T = float, unsigned short holding bfloat16, or _Float16 (the bf16 / fp16 options of the backbone: statistics and arithmetic stay float32 / float64).
 // pre_bias (nullable, [C] float32): added to x on the way in -- the bias of the convolution that produced x, which PyTorch-ROCm would
 // otherwise apply as a separate read + write pass behind MIOpen's kernel (108 such passes per backbone pass, profiles/r04_final/unet.md).
@@ -106,23 +117,25 @@ group_norm_silu_kernel(int C, int HW, int groups, const T* __restrict__ x, const
     const T* xs = x + ((size_t)n * C + (size_t)g * Cg) * HW;
     T* ys = y + ((size_t)n * C + (size_t)g * Cg) * HW;
 
-    // ---- moments: float partial sums per thread over short runs, folded into float64
+    // ---- moments of v - K, K = the slab's first value: float partial sums per thread over short runs, folded into float64
+    const float K = to_f32(xs[0]) + (pre_bias ? pre_bias[g * Cg] : 0.0f);
     double s1 = 0.0, s2 = 0.0;
     const bool vec = HW % PN == 0;                                // true for every layer of the backbone at 256^2 / 32^2
     const size_t np = vec ? slab / PN : 0;
     const int hwp = vec ? HW / PN : 1;
+    const bool idx32 = slab <= 0x7FFFFFFFu;                       // the channel of a packet / element by a 32-bit division (a 64-bit one costs more than the packet's arithmetic)
     for (size_t i = threadIdx.x; i < np; i += GN_THREADS) {
         Packet<T> p;
         p.load(xs + i * PN);
-        const float pb = pre_bias ? pre_bias[g * Cg + (int)(i / hwp)] : 0.0f;
+        const float pb = pre_bias ? pre_bias[g * Cg + (idx32 ? (int)((unsigned)i / (unsigned)hwp) : (int)(i / hwp))] : 0.0f;
         float a = 0.0f, b = 0.0f;
 #pragma unroll
-        for (int k = 0; k < PN; k++) { const float v = p.v[k] + pb; a += v; b += v * v; }
+        for (int k = 0; k < PN; k++) { const float v = (p.v[k] + pb) - K; a += v; b = __builtin_fmaf(v, v, b); }      // (the fused multiply-add pays for the subtraction)
         s1 += (double)a;
         s2 += (double)b;
     }
     for (size_t i = np * PN + threadIdx.x; i < slab; i += GN_THREADS) {
-        const float v = to_f32(xs[i]) + (pre_bias ? pre_bias[g * Cg + (int)(i / HW)] : 0.0f);
+        const float v = (to_f32(xs[i]) + (pre_bias ? pre_bias[g * Cg + (idx32 ? (int)((unsigned)i / (unsigned)HW) : (int)(i / HW))] : 0.0f)) - K;
         s1 += v; s2 += (double)(v * v);
     }
 #pragma unroll
@@ -138,10 +151,10 @@ group_norm_silu_kernel(int C, int HW, int groups, const T* __restrict__ x, const
     if (threadIdx.x == 0) {
         double a = 0.0, b = 0.0;
         for (int w = 0; w < GN_THREADS / 64; w++) { a += w1[w]; b += w2[w]; }
-        const double mean = a / (double)slab;
-        double var = b / (double)slab - mean * mean;
+        const double d = a / (double)slab;                        // mean - K
+        double var = b / (double)slab - d * d;
         if (var < 0.0) var = 0.0;
-        s_mean = (float)mean;
+        s_mean = (float)((double)K + d);
         s_rstd = (float)(1.0 / sqrt(var + (double)eps));
     }
     __syncthreads();
@@ -150,10 +163,10 @@ group_norm_silu_kernel(int C, int HW, int groups, const T* __restrict__ x, const
     // ---- normalise, affine, (silu): the slab is re-read from L2
     if (vec) {
         for (size_t i = threadIdx.x; i < np; i += GN_THREADS) {
-            const int c = g * Cg + (int)(i / hwp);
-            const float pb = pre_bias ? pre_bias[c] : 0.0f;
+            const int c = g * Cg + (idx32 ? (int)((unsigned)i / (unsigned)hwp) : (int)(i / hwp));
+            const float pb = (pre_bias ? pre_bias[c] : 0.0f) - mean;            // (x + pre_bias) - mean as x + (pre_bias - mean): see above
             const float sc = weight[c] * rstd;
-            const float sh = bias[c] - mean * sc;
+            const float sh = bias[c];
             Packet<T> p;
             p.load(xs + i * PN);
 #pragma unroll
@@ -166,10 +179,10 @@ group_norm_silu_kernel(int C, int HW, int groups, const T* __restrict__ x, const
         }
     } else {
         for (size_t i = threadIdx.x; i < slab; i += GN_THREADS) {
-            const int c = g * Cg + (int)(i / HW);
-            const float pb = pre_bias ? pre_bias[c] : 0.0f;
+            const int c = g * Cg + (idx32 ? (int)((unsigned)i / (unsigned)HW) : (int)(i / HW));
+            const float pb = (pre_bias ? pre_bias[c] : 0.0f) - mean;
             const float sc = weight[c] * rstd;
-            float v = (to_f32(xs[i]) + pb) * sc + (bias[c] - mean * sc);
+            float v = (to_f32(xs[i]) + pb) * sc + bias[c];
             if (apply_silu) v = silu_of<T>(v);
             from_f32(ys[i], v);
         }
@@ -195,15 +208,25 @@ int launch_gn(void* stream, int N, int C, int HW, int groups, const T* x, const 
 // layout only pays if GroupNorm keeps it. x is [N][HW][C]: a group's Cg channels are 8..64 bytes of every pixel's C-vector, so a
 // workgroup takes a run of pixels with ALL channels (whole lines), and the moments of a (sample, group) are summed across workgroups:
 //   gn_nhwc_moments_kernel: thread (row, col) owns the 16-byte packet `col` of the pixels row, row + rows, ...: float sums per channel
-//       over at most GN_NHWC_PIX / rows pixels, per-channel totals over the rows in LDS, per-group totals in float64 written to
+//       over at most gn_nhwc_pix(HW) / rows pixels, per-channel totals over the rows in LDS, per-group totals in float64 written to
 //       partial[n][g][block] = (sum, sum of squares); gn_nhwc_finish_kernel adds the blocks in order -> (mean, rstd) per (sample, group);
 //   gn_nhwc_apply_kernel: the same mapping; scale / shift of the thread's PN channels once, then one pass: silu((x + pre_bias) * sc + sh).
 // Two reads (the second from L2 / MALL) and one write, as the NCHW kernel.
-constexpr int GN_NHWC_PIX = 512;      // pixels per workgroup
+// pixels per workgroup: 512 where a sample has enough of them to fill the device. Below 128 x 128 pixels a run of 512 left the backbone's 64^2 / 32^2
+// layers 8 / 2 workgroups per sample, each thread walking up to 256 pixels one load latency after the other. A function of HW alone: the
+// order of the additions, and so the result of a sample, does not depend on the batch it is in.
+constexpr int gn_nhwc_pix(int HW) { return HW >= 16384 ? 512 : 64; }
 constexpr int GN_NHWC_MAXC = 1024;
 constexpr int GN_NHWC_UNROLL = 4;     // independent 16-byte loads in flight per thread
 
+// the pivot of (sample n, group g): the first value of the slab, as the moments and the finish kernel both read it
 template <typename T>
+__device__ __forceinline__ float gn_nhwc_pivot(const T* __restrict__ x, const float* __restrict__ pre_bias, int n, int C, int HW, int Cg, int g)
+{
+    return to_f32(x[((size_t)n * HW) * C + (size_t)g * Cg]) + (pre_bias ? pre_bias[g * Cg] : 0.0f);
+}
+
+template <typename T, int KP>
 __global__ void __launch_bounds__(256)
 gn_nhwc_moments_kernel(int C, int HW, int groups, int rows, const T* __restrict__ x, const float* __restrict__ pre_bias, double* __restrict__ moments)
 {
@@ -211,12 +234,31 @@ gn_nhwc_moments_kernel(int C, int HW, int groups, int rows, const T* __restrict_
     const int ppp = C / PN;                                   // packets per pixel
     const int col = threadIdx.x % ppp, row = threadIdx.x / ppp;
     const int n = blockIdx.y;
-    const int p0 = blockIdx.x * GN_NHWC_PIX;
-    const int p1 = min(p0 + GN_NHWC_PIX, HW);
+    const int p0 = blockIdx.x * gn_nhwc_pix(HW);
+    const int p1 = min(p0 + gn_nhwc_pix(HW), HW);
+    const int Cg = C / groups;
     float a[PN], b[PN], pb[PN];
 #pragma unroll
     for (int k = 0; k < PN; k++) { a[k] = 0.0f; b[k] = 0.0f; pb[k] = (pre_bias && row < rows) ? pre_bias[col * PN + k] : 0.0f; }
     if (row < rows) {
+        // K = gn_nhwc_pivot of each of the thread's channels' group (pixel 0 of the sample, first channel of the group): the sums are of (x + pb) - K
+        // KP pivots per packet: 1 (the packet inside one group, Cg a multiple of PN), 2 (two whole groups: Cg = 4 and 8-wide packets, the
+        // 16-bit backbone's 128-channel layers) or PN (any other Cg: a pivot is loaded where the packet enters a group). Chosen by the
+        // launch: a thread has as few as 8 trips of the loop below to spread this set-up over
+        float K[KP];
+        if constexpr (KP < PN) {
+            const int g = KP == 1 ? (col * PN) / Cg : col * KP;
+#pragma unroll
+            for (int j = 0; j < KP; j++) K[j] = gn_nhwc_pivot(x, pre_bias, n, C, HW, Cg, g + j);
+        } else {
+            int g = (col * PN) / Cg, r = col * PN - g * Cg;
+            float Kg = gn_nhwc_pivot(x, pre_bias, n, C, HW, Cg, g);
+#pragma unroll
+            for (int k = 0; k < PN; k++) {
+                K[k] = Kg;
+                if (++r == Cg && k + 1 < PN) { r = 0; g++; Kg = gn_nhwc_pivot(x, pre_bias, n, C, HW, Cg, g); }
+            }
+        }
         const T* xs = x + ((size_t)n * HW) * C + (size_t)col * PN;
         for (int p = p0 + row; p < p1; p += rows * GN_NHWC_UNROLL) {
             Packet<T> q[GN_NHWC_UNROLL];
@@ -227,7 +269,7 @@ gn_nhwc_moments_kernel(int C, int HW, int groups, int rows, const T* __restrict_
             for (int u = 0; u < GN_NHWC_UNROLL; u++)
                 if (p + u * rows < p1) {
 #pragma unroll
-                    for (int k = 0; k < PN; k++) { const float v = q[u].v[k] + pb[k]; a[k] += v; b[k] += v * v; }
+                    for (int k = 0; k < PN; k++) { const float v = (q[u].v[k] + pb[k]) - K[k * KP / PN]; a[k] += v; b[k] = __builtin_fmaf(v, v, b[k]); }
                 }
         }
     }
@@ -248,7 +290,6 @@ gn_nhwc_moments_kernel(int C, int HW, int groups, int rows, const T* __restrict_
     // per-group totals in float64, one (sum, sum of squares) pair per WORKGROUP: partial[n][g][block]. No atomics -- the second stage
     // (gn_nhwc_finish_kernel) adds a sample's blocks up in block order, so the statistics, and with them the whole backbone pass, are
     // bit-reproducible from run to run (until round 5 the blocks added into 8 atomic slots in arrival order)
-    const int Cg = C / groups;
     for (int g = threadIdx.x; g < groups; g += blockDim.x) {
         double s1 = 0.0, s2 = 0.0;
         for (int c = g * Cg; c < (g + 1) * Cg; c++) { s1 += (double)ca[c]; s2 += (double)cb[c]; }
@@ -262,13 +303,16 @@ gn_nhwc_moments_kernel(int C, int HW, int groups, int rows, const T* __restrict_
 // butterfly over the lanes: the same association every run -- and leaves mean and 1 / sqrt(var + eps) as two floats behind the partials
 // (stats[n][g]): the apply kernel's threads read them instead of each recomputing them in float64. (One THREAD per pair, the first
 // version, walked 128 strided pairs serially: 12 us per launch, 78 launches per pass.)
+template <typename T>
 __global__ void __launch_bounds__(256)
-gn_nhwc_finish_kernel(int N, int groups, int nb, double cnt, float eps, const double* __restrict__ partial, float2* __restrict__ stats)
+gn_nhwc_finish_kernel(int N, int C, int HW, int groups, int nb, double cnt, float eps, const T* __restrict__ x, const float* __restrict__ pre_bias,
+                      const double* __restrict__ partial, float2* __restrict__ stats)
 {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= N * groups) return;
     const int lane = threadIdx.x & 63;
     const int n = i / groups, g = i % groups;
+    const float K = gn_nhwc_pivot(x, pre_bias, n, C, HW, C / groups, g);      // (loaded while the partials are on their way)
     double m1 = 0.0, m2 = 0.0;
     for (int b = lane; b < nb; b += 64) {
         const double* p = partial + 2 * (((size_t)n * groups + g) * nb + b);
@@ -280,10 +324,10 @@ gn_nhwc_finish_kernel(int N, int groups, int nb, double cnt, float eps, const do
         m2 += __shfl_xor(m2, m, 64);
     }
     if (lane == 0) {
-        const double m = m1 / cnt;
-        double var = m2 / cnt - m * m;
+        const double d = m1 / cnt;                                // mean - K: the partials are sums of v - K
+        double var = m2 / cnt - d * d;
         if (var < 0.0) var = 0.0;
-        stats[i] = make_float2((float)m, (float)(1.0 / sqrt(var + (double)eps)));
+        stats[i] = make_float2((float)((double)K + d), (float)(1.0 / sqrt(var + (double)eps)));
     }
 }
 
@@ -297,8 +341,8 @@ gn_nhwc_apply_kernel(int C, int HW, int groups, int rows, const T* __restrict__ 
     const int col = threadIdx.x % ppp, row = threadIdx.x / ppp;
     if (row >= rows) return;
     const int n = blockIdx.y;
-    const int p0 = blockIdx.x * GN_NHWC_PIX;
-    const int p1 = min(p0 + GN_NHWC_PIX, HW);
+    const int p0 = blockIdx.x * gn_nhwc_pix(HW);
+    const int p1 = min(p0 + gn_nhwc_pix(HW), HW);
     const int Cg = C / groups;
     float sc[PN], sh[PN], pb[PN];
 #pragma unroll
@@ -306,8 +350,8 @@ gn_nhwc_apply_kernel(int C, int HW, int groups, int rows, const T* __restrict__ 
         const int c = col * PN + k;
         const float2 st = stats[(size_t)n * groups + c / Cg];        // (mean, rstd)
         sc[k] = weight[c] * st.y;
-        sh[k] = bias[c] - st.x * sc[k];
-        pb[k] = pre_bias ? pre_bias[c] : 0.0f;
+        sh[k] = bias[c];
+        pb[k] = (pre_bias ? pre_bias[c] : 0.0f) - st.x;              // pre_bias - mean
     }
     const size_t base = ((size_t)n * HW) * C + (size_t)col * PN;
     for (int p = p0 + row; p < p1; p += rows * GN_NHWC_UNROLL) {
@@ -345,12 +389,18 @@ int launch_gn_nhwc(void* stream, int N, int C, int HW, int groups, const T* x, c
     if (((uintptr_t)x | (uintptr_t)y) & 15u) return F3DG_ERR_BAD_ARG;
     const int ppp = C / PN, rows = 256 / ppp;
     hipStream_t s = (hipStream_t)stream;
-    const int nb = (HW + GN_NHWC_PIX - 1) / GN_NHWC_PIX;
+    const int nb = (HW + gn_nhwc_pix(HW) - 1) / gn_nhwc_pix(HW);
     float2* stats = reinterpret_cast<float2*>(moments + 2 * (size_t)N * nb * groups);
     const dim3 grid((unsigned)nb, (unsigned)N);
-    F3DG_KLAUNCH(gn_nhwc_moments_kernel<T>, grid, dim3(256), 0, s, C, HW, groups, rows, x, pre_bias, moments);
-    F3DG_KLAUNCH(gn_nhwc_finish_kernel, dim3((unsigned)((N * groups + 3) / 4)), dim3(256), 0, s, N, groups, nb, (double)(C / groups) * (double)HW, eps,
-                 moments, stats);
+    const int Cg = C / groups;
+    if (Cg % PN == 0)
+        F3DG_KLAUNCH((gn_nhwc_moments_kernel<T, 1>), grid, dim3(256), 0, s, C, HW, groups, rows, x, pre_bias, moments);
+    else if (2 * Cg == PN)
+        F3DG_KLAUNCH((gn_nhwc_moments_kernel<T, 2>), grid, dim3(256), 0, s, C, HW, groups, rows, x, pre_bias, moments);
+    else
+        F3DG_KLAUNCH((gn_nhwc_moments_kernel<T, PN>), grid, dim3(256), 0, s, C, HW, groups, rows, x, pre_bias, moments);
+    F3DG_KLAUNCH(gn_nhwc_finish_kernel<T>, dim3((unsigned)((N * groups + 3) / 4)), dim3(256), 0, s, N, C, HW, groups, nb, (double)(C / groups) * (double)HW,
+                 eps, x, pre_bias, moments, stats);
     F3DG_KLAUNCH(gn_nhwc_apply_kernel<T>, grid, dim3(256), 0, s, C, HW, groups, rows, x, pre_bias, stats, weight, bias, apply_silu, y);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
@@ -461,7 +511,7 @@ extern "C" int f3dg_residual_join_f16(void* stream, int N, int C, int HW, int nh
 extern "C" size_t f3dg_group_norm_nhwc_scratch_bytes(int N, int HW, int groups)
 {
     if (N <= 0 || HW <= 0 || groups <= 0) return 0;
-    const size_t nb = (size_t)(HW + GN_NHWC_PIX - 1) / GN_NHWC_PIX;
+    const size_t nb = (size_t)(HW + gn_nhwc_pix(HW) - 1) / gn_nhwc_pix(HW);
     return sizeof(double) * 2 * (size_t)N * nb * groups + sizeof(float2) * (size_t)N * groups;
 }
 

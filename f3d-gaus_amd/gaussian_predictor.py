@@ -143,7 +143,7 @@ class GroupNorm(nn.Module):
 
     def _fusable(self, x):
         """Inference on a HIP device in a dtype the kernels take: the fused HIP kernels run (no autograd through them)."""
-        return x.is_cuda and x.dtype in _KERNEL_SUFFIX and x.dim() >= 3 and self.weight.dtype == torch.float32 and not (
+        return x.is_cuda and x.dtype in _KERNEL_SUFFIX and x.dim() >= 3 and x.numel() > 0 and self.weight.dtype == torch.float32 and not (
             torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad))
 
     def forward(self, x, N_views_xa=1, silu=False, pre_bias=None):
@@ -153,7 +153,7 @@ class GroupNorm(nn.Module):
         that of ``x + pre_bias[None, :, None, None]`` -- the bias of the convolution that produced ``x`` (``Conv2d.forward(bias=False)``)."""
         if self._fusable(x) and (pre_bias is None or pre_bias.dtype == torch.float32):
             L = _lib.lib()
-            if _is_nhwc(x) and x.shape[1] % (4 if x.dtype == torch.float32 else 8) == 0 and x.shape[1] <= 1024:
+            if _is_nhwc(x) and x.shape[1] % (4 if x.dtype == torch.float32 else 8) == 0 and x.shape[1] <= 1024 and x.data_ptr() % 16 == 0:
                 # layout option "nhwc": the channels-last kernel, channels-last out
                 y = torch.empty_like(x)           # preserves the strides
                 N, Cc = x.shape[0], x.shape[1]
@@ -166,6 +166,8 @@ class GroupNorm(nn.Module):
                 _lib.check(rc, "f3dg_group_norm_silu_nhwc_pb")
                 return y
             xc = x.contiguous()
+            if xc.data_ptr() % 16:              # a dense view that starts inside an allocation: the kernels load 16-byte packets
+                xc = xc.clone()
             y = torch.empty_like(xc)
             N, Cc = xc.shape[0], xc.shape[1]
             fn = getattr(L, "f3dg_group_norm_silu_pb" + _KERNEL_SUFFIX[x.dtype])

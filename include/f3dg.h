@@ -419,8 +419,11 @@ int f3dg_group_norm_silu_bf16(void* stream, int N, int C, int HW, int groups, co
  * `moments` is scratch of f3dg_group_norm_nhwc_scratch_bytes(N, HW, groups) bytes: one (sum, sum of squares) pair per workgroup, sample
  * and group, added up in workgroup order by a second-stage kernel -- no atomics, the statistics are bit-reproducible from run to run
  * (round 5; until then the workgroups added into 8 atomic slots in arrival order). Same statistics, same formula.
- * `moments_bytes` = the size of the buffer behind `moments` (round 6: the scratch has grown with the kernel once -- a buffer smaller than
- * f3dg_group_norm_nhwc_scratch_bytes() is refused with F3DG_ERR_WORKSPACE instead of being written past its end). */
+ * `moments_bytes` = the size of the buffer behind `moments` (round 6: the scratch has grown with the kernel -- a pair per workgroup, then
+ * workgroups of 64 instead of 512 pixels for samples below 128 x 128 pixels; a buffer smaller than
+ * f3dg_group_norm_nhwc_scratch_bytes() is refused with F3DG_ERR_WORKSPACE instead of being written past its end).
+ * Both layouts sum (x - K) and (x - K)^2, K the first value of the (sample, group), so that the variance keeps torch's float32 accuracy
+ * when a group's mean is far from zero (measured up to |mean| / std = 100 and on constant groups: tests/test_backbone_kernels_gpu.py). */
 size_t f3dg_group_norm_nhwc_scratch_bytes(int N, int HW, int groups);
 int f3dg_group_norm_silu_nhwc(void* stream, int N, int C, int HW, int groups, const float* x, const float* weight,
                               const float* bias, float eps, int apply_silu, float* y, double* moments, size_t moments_bytes);
