@@ -11,6 +11,14 @@ OK, ERR_BAD_ARG, ERR_WORKSPACE, ERR_OVERFLOW, ERR_HIP, ERR_UNSUPPORTED, ERR_STAT
 FLAG_SAVE_AUX, FLAG_BG_PER_VIEW, FLAG_SKIP_NORMAL, FLAG_SKIP_DISTORTION = 1, 2, 4, 8
 FLAG_EXACT, FLAG_FAST, FLAG_NO_TILE_CULL, FLAG_NO_SMALL_PATH, FLAG_SCAN, FLAG_SETS_AUX = 16, 32, 64, 128, 256, 512
 PENDING = 1
+MAX_PANELS, PANEL_RGB, PANEL_SIGNED, PANEL_COLORMAP = 8, 0, 1, 2
+
+
+class Panel(C.Structure):
+    """f3dg_panel of include/f3dg.h (strides in floats)."""
+    _fields_ = [("src", C.c_void_p), ("image_stride", C.c_size_t), ("frame_stride", C.c_size_t), ("plane_stride", C.c_size_t),
+                ("kind", C.c_int), ("planes", C.c_int), ("range_index", C.c_int)]
+
 
 _ERR_TEXT = {
     ERR_BAD_ARG: "bad argument",
@@ -68,6 +76,9 @@ SIGNATURES = {
     "f3dg_cycle_inputs": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
     "f3dg_pack_frames": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "f3dg_pack_frames_host": (_i, [_p, _i, _i, _i, _i, _p, _p, _i]),
+    # stream | n_frames n_images H W nrow padding n_panels | panels (host, Panel[]) lut ranges invalid_val | dst dst_is_host max_workgroups
+    "f3dg_compose_frames": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _f, _p, _i, _i]),
+    "f3dg_compose_frames_size": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_sz)]),
     "f3dg_group_norm_silu": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _f, _i, _p]),
     "f3dg_group_norm_silu_bf16": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _f, _i, _p]),
     "f3dg_group_norm_silu_pb": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _f, _i, _p]),

@@ -399,6 +399,47 @@ int f3dg_pack_frames(void* stream, int n_frames, int H, int W, int src_channels,
 int f3dg_pack_frames_host(void* stream, int n_frames, int H, int W, int src_channels, const float* src, unsigned char* dst_host,
                           int max_workgroups);
 
+/* The frames of the reference's orbit video (visualize.py:403-416), composed in one kernel from the float32 planes where they lie:
+ * per frame, every image of the batch is a strip of n_panels panels of H x W pixels, left to right, and the strips are laid out as
+ * torchvision's make_grid(tensor[n_images,3,H,n_panels*W], nrow, padding, pad_value = 0) lays them out:
+ *   xmaps = min(nrow, n_images), ymaps = ceil(n_images / xmaps); a frame is [ymaps*(H+pad)+pad, xmaps*(n_panels*W+pad)+pad, 3] uint8
+ *   (HWC); image k has its top-left corner at (k / xmaps * (H+pad) + pad, k % xmaps * (n_panels*W+pad) + pad); padding and cells
+ *   without an image are 0. n_images == 1: the bare H x n_panels*W strip, no padding (what make_grid returns for one image).
+ * A panel is described by f3dg_panel: pixel (y, x) of plane c of image k in frame f is
+ *   src[k * image_stride + f * frame_stride + c * plane_stride + y * W + x]   (strides in floats; rows contiguous)
+ * so [B,V,C,H,W] tensors, a channel slice of a [B*V,9,H,W] raster, and a static [B,C,H,W] input (frame_stride = 0: the same on
+ * every frame) are all read in place. `kind` decides the bytes:
+ *   F3DG_PANEL_RGB      3 planes: byte = (unsigned)(255.0f * fminf(fmaxf(v, 0), 1)), the rule of f3dg_pack_frames (NaN -> 0);
+ *   F3DG_PANEL_SIGNED   3 planes, or 1 plane repeated: v' = (v + 1.0f) / 2.0f in float32, then the RGB rule (depth_normal, :412);
+ *   F3DG_PANEL_COLORMAP 1 plane d: the reference's colorize() (src/utils.py:94-150) with its defaults. vmin, vmax =
+ *       ranges[range_index][0..1]; t = (d - vmin) / (vmax - vmin) in float32 (IEEE divide), t = d * 0 when vmin == vmax;
+ *       d == invalid_val -> (128,128,128); NaN t -> (0,0,0); t < 0 -> lut[0]; t >= 1 -> lut[255]; else lut[(int)(t * 256)].
+ *       The bytes written are the table's own (the reference's / 255 ... 255 * round trip is the identity on them).
+ * lut [256][3] uint8 and ranges [.][2] float32 are DEVICE arrays, read only when a COLORMAP panel exists (NULL otherwise); the
+ * call carries no row count of `ranges`: the CALLER guarantees 0 <= range_index < its rows (a negative one is F3DG_ERR_BAD_ARG);
+ * `panels` is a HOST array of n_panels (1 .. F3DG_MAX_PANELS) descriptors, passed to the kernel by value.
+ * dst: n_frames frames, 16-byte aligned, every byte written. dst_is_host != 0: dst is PINNED host memory (anything else is
+ * F3DG_ERR_BAD_ARG), written by the kernel as f3dg_pack_frames_host does. A lane produces 16 consecutive bytes of the stream and
+ * stores them at once; the kernel is grid-stride with at most max_workgroups workgroups (0: 64 for host memory, 2048 otherwise).
+ * Offsets into src and dst are 64-bit; one frame must stay below 4 GB.
+ * F3DG_ERR_BAD_ARG before any launch: NULL dst / panels / panel src, n_panels outside 1..8, nrow < 1, non-positive sizes, negative
+ * padding, a COLORMAP panel with NULL lut or ranges, planes not matching kind, an unknown kind, a misaligned dst. */
+#define F3DG_MAX_PANELS 8
+#define F3DG_PANEL_RGB 0
+#define F3DG_PANEL_SIGNED 1
+#define F3DG_PANEL_COLORMAP 2
+typedef struct f3dg_panel {
+    const float* src;
+    size_t image_stride, frame_stride, plane_stride;
+    int kind, planes, range_index;
+} f3dg_panel;
+int f3dg_compose_frames(void* stream, int n_frames, int n_images, int H, int W, int nrow, int padding, int n_panels,
+                        const f3dg_panel* panels, const unsigned char* lut, const float* ranges, float invalid_val,
+                        unsigned char* dst, int dst_is_host, int max_workgroups);
+/* Height, width and total byte count (n_frames frames) of what f3dg_compose_frames writes; any output pointer may be NULL. */
+int f3dg_compose_frames_size(int n_frames, int n_images, int H, int W, int nrow, int padding, int n_panels,
+                             int* frame_h, int* frame_w, size_t* n_bytes);
+
 /* Hand-off of the cycle aggregation (reference visualize.py:311, 331-333): from the rendered rasters [B * V, 9, H, W] (frame
  * b * V + v) to the next predictor inputs, view-major: xin [V, B, 4, H, W] = cat(clamp(rgb, 0, 1), alpha) and
  * depth [V, B, 1, H, W] = the median depth. One kernel; H * W must be a multiple of 4 and the pointers 16-byte aligned. */
