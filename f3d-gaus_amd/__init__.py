@@ -20,7 +20,7 @@ from . import gaussian_renderer, gaussian_predictor, unet_gs, cycle, dist, ply, 
 from .gaussian_renderer import (render_predicted_more_v2_gof, render_predicted_more_v3_gof,  # noqa: E402,F401
                                 render_predicted_more_v2_gof_in, AlphaSweep,
                                 render_views, depth_to_normal, depths_to_points)
-from .gaussian_predictor import GaussianSplatPredictor_gtunet, splat_head  # noqa: E402,F401
+from .gaussian_predictor import GaussianSplatPredictor_gtunet, splat_head, splat_head_merge  # noqa: E402,F401
 from .unet_gs import Unet_GS_gtunet  # noqa: E402,F401
 from .mesh import marching_tetrahedra, tetra_points, bisect_level_set, extract_mesh  # noqa: E402,F401
 from .frames import compose_frames, compose_orbit_frames, depth_range, colormap_lut  # noqa: E402,F401

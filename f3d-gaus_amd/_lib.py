@@ -74,6 +74,7 @@ SIGNATURES = {
     "f3dg_render_epilogue_view": (_i, [_p, _i, _i, _i, _p, _p, _f, _f, _p, _p]),
     "f3dg_render_epilogue_backward": (_i, [_p, _i, _i, _i, _p, _p, _f, _f, _p, _p, _p]),
     "f3dg_cycle_inputs": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
+    "f3dg_cycle_inputs_backward": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "f3dg_pack_frames": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "f3dg_pack_frames_host": (_i, [_p, _i, _i, _i, _i, _p, _p, _i]),
     # stream | n_frames n_images H W nrow padding n_panels | panels (host, Panel[]) lut ranges invalid_val | dst dst_is_host max_workgroups

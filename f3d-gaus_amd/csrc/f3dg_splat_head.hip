@@ -635,3 +635,63 @@ extern "C" int f3dg_cycle_inputs(void* stream, int B, int V, int H, int W, const
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }
+
+// Adjoint of cycle_inputs_kernel (what torch.autograd derives from visualize.py:311, 331-333): the same launch shape, one thread per four
+// pixels of frame n = b * V + v, which takes its cotangents from slot v * B + b and writes all nine planes of d_raster. The clamp passes
+// the cotangent where 0 <= raster <= 1 (both ends and -0.0 included; NaN and +-Inf fail both comparisons); elsewhere +0.0 is SELECTED,
+// never g * 0, so a non-finite cotangent under the mask cannot leak. A NULL g_xin / g_depth counts as all-zero.
+namespace {
+__global__ void __launch_bounds__(F3DG_BLOCK)
+cycle_inputs_backward_kernel(size_t HW, int B, int V, const float* __restrict__ raster, const float* __restrict__ g_xin,
+                             const float* __restrict__ g_depth, float* __restrict__ d_raster)
+{
+    const size_t i = ((size_t)blockIdx.x * F3DG_BLOCK + threadIdx.x) * 4;
+    if (i >= HW) return;             // (HW is a multiple of 4: a thread's four pixels are all inside or all outside)
+    const unsigned n = blockIdx.y, b = n / (unsigned)V, v = n % (unsigned)V;
+    const float* src = raster + (size_t)n * F3DG_OUT_CHANNELS * HW + i;
+    float* dst = d_raster + (size_t)n * F3DG_OUT_CHANNELS * HW + i;
+    const size_t slot = (size_t)v * B + b;
+    auto gate = [](float r, float g) { return (r >= 0.0f && r <= 1.0f) ? g : 0.0f; };
+    auto put = [](float* p, float x, float y, float z, float w) { *reinterpret_cast<float4*>(p) = make_float4(x, y, z, w); };
+    if (g_xin) {
+        const float* gx = g_xin + slot * 4 * HW + i;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float4 r = *reinterpret_cast<const float4*>(src + c * HW);
+            const float4 g = *reinterpret_cast<const float4*>(gx + c * HW);
+            put(dst + c * HW, gate(r.x, g.x), gate(r.y, g.y), gate(r.z, g.z), gate(r.w, g.w));
+        }
+        const float4 a = *reinterpret_cast<const float4*>(gx + 3 * HW);
+        put(dst + 7 * HW, a.x, a.y, a.z, a.w);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; c++) put(dst + c * HW, 0.0f, 0.0f, 0.0f, 0.0f);
+        put(dst + 7 * HW, 0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    put(dst + 3 * HW, 0.0f, 0.0f, 0.0f, 0.0f);
+    put(dst + 4 * HW, 0.0f, 0.0f, 0.0f, 0.0f);
+    put(dst + 5 * HW, 0.0f, 0.0f, 0.0f, 0.0f);
+    if (g_depth) {
+        const float4 d = *reinterpret_cast<const float4*>(g_depth + slot * HW + i);
+        put(dst + 6 * HW, d.x, d.y, d.z, d.w);
+    } else {
+        put(dst + 6 * HW, 0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    put(dst + 8 * HW, 0.0f, 0.0f, 0.0f, 0.0f);
+}
+} // namespace
+
+extern "C" int f3dg_cycle_inputs_backward(void* stream, int B, int V, int H, int W, const float* raster,
+                                          const float* g_xin, const float* g_depth, float* d_raster)
+{
+    if (B < 0 || V <= 0 || H <= 0 || W <= 0 || !raster || !d_raster) return F3DG_ERR_BAD_ARG;
+    if (B == 0) return F3DG_OK;
+    const size_t HW = (size_t)H * W;
+    if ((HW & 3u) || ((uintptr_t)raster & 15u) || ((uintptr_t)d_raster & 15u) || ((uintptr_t)g_xin & 15u) || ((uintptr_t)g_depth & 15u))
+        return F3DG_ERR_BAD_ARG;
+    if ((long long)B * V > 65535) return F3DG_ERR_BAD_ARG;          // grid.y
+    F3DG_KLAUNCH(cycle_inputs_backward_kernel, dim3((unsigned)((HW / 4 + F3DG_BLOCK - 1) / F3DG_BLOCK), (unsigned)(B * V)),
+                 dim3(F3DG_BLOCK), 0, (hipStream_t)stream, HW, B, V, raster, g_xin, g_depth, d_raster);
+    F3DG_HIP_CHECK(hipGetLastError());
+    return F3DG_OK;
+}

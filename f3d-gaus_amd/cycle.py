@@ -14,20 +14,41 @@ MI355X shape of the same work here:
     the median depth, view-major so that the B inputs of a novel view are one contiguous predictor batch;
   * the 8 re-predictions are 8 predictor calls of B images each, as in the reference (visualize.py:326-340), and the splat
     head writes every pass directly into the preallocated merged buffers (no torch.cat chain, no O(n^2) re-copies);
-  * the order of the merged set is the reference's: canonical view first, then orbit views 0..7.
+  * the order of the merged set is the reference's: canonical view first, then orbit views 0..7;
+  * ``cycle_aggregate(differentiable=True)`` is the same loop under autograd, for training through the aggregation: the hand-off kernel
+    has an adjoint (f3dg_cycle_inputs_backward) and the merge is one node over the splat head's backward (``splat_head_merge``).
 """
 import torch
 
 from . import cameras
-from .gaussian_predictor import GAUSSIAN_KEYS, allocate_gaussians
+from .gaussian_predictor import GAUSSIAN_KEYS, allocate_gaussians, splat_head, splat_head_merge
 from .gaussian_renderer import cycle_inputs, render_views
 
 
-@torch.no_grad()
 def cycle_aggregate(model, images, depth, cfg, rig=None, num_views=8, yaw_diff=0.25, pitch_diff=0.15,
-                    return_renders=False):
+                    return_renders=False, differentiable=False, grad_through_renders=True):
     """images [B,3,H,W] in [0,1], depth [B,1,H,W] (z in camera space). Returns the merged Gaussian dict
-    (every value [B, (1+num_views)*H*W, ...]) -- what visualize.py calls ``gaussian_splat_batch_merge``."""
+    (every value [B, (1+num_views)*H*W, ...]) -- what visualize.py calls ``gaussian_splat_batch_merge``.
+
+    ``differentiable=True`` (with grad mode on; under ``torch.no_grad()`` it is the inference call): the merged set carries the autograd
+    graph back through all 1 + num_views predictor passes -- and, with ``grad_through_renders`` (default), through the hand-off and the
+    novel-view renders into pass 0 as well; ``grad_through_renders=False`` detaches the re-prediction inputs, so that the renders are
+    data and only the predictor passes are trained. The training shape:
+
+        merged = cycle_aggregate(model, images, depth, cfg, differentiable=True)
+        out = render_views(merged, None, world_views, full_projs, centers, bg, cfg, differentiable=True)
+        losses.photometric_loss(out["render"], target).backward()
+
+    The novel views are rendered on a workspace of their own, in all nine channels and the reference arithmetic (what the differentiable
+    render requires), so a later differentiable render of the merged set does not invalidate their backward."""
+    if differentiable and torch.is_grad_enabled():
+        return _cycle_aggregate_autograd(model, images, depth, cfg, rig, num_views, yaw_diff, pitch_diff, return_renders,
+                                         grad_through_renders)
+    with torch.no_grad():
+        return _cycle_aggregate_inference(model, images, depth, cfg, rig, num_views, yaw_diff, pitch_diff, return_renders)
+
+
+def _cycle_aggregate_inference(model, images, depth, cfg, rig, num_views, yaw_diff, pitch_diff, return_renders):
     device = images.device
     B, _, H, W = images.shape
     HW = H * W
@@ -64,6 +85,52 @@ def cycle_aggregate(model, images, depth, cfg, rig=None, num_views=8, yaw_diff=0
               out=merged, n_offset=(1 + v) * HW)
     if return_renders:
         xb = xin.transpose(0, 1)                           # [B,V,4,H,W]
+        return merged, dict(rgb=xb[:, :, :3], alpha=xb[:, :, 3:4], depth=zmed.transpose(0, 1))
+    return merged
+
+
+def _cycle_aggregate_autograd(model, images, depth, cfg, rig, num_views, yaw_diff, pitch_diff, return_renders, grad_through_renders):
+    """The same loop with every stage under autograd: the predictor passes stop before the head (``head=False``), the first set goes
+    through ``splat_head``, the batched differentiable render and the hand-off kernel with its adjoint, and ONE ``splat_head_merge``
+    node builds the merged set from the 1 + num_views passes (pass 0's head is recomputed into the merged buffer: 192 B per Gaussian,
+    and autograd sums the two contributions to its ``net_out``)."""
+    device = images.device
+    B = images.shape[0]
+    rig = rig or cameras.OrbitRig(cfg)
+    cano = rig.canonical
+    orbit = rig.orbit(num_views, yaw_diff, pitch_diff)
+    background = torch.zeros(3, dtype=torch.float32, device=device)
+    squre_clip = cfg['opt']['squre_clip']
+    ray_dirs = model.gaussian_predictor.ray_dirs
+
+    x0 = torch.cat([images, torch.ones_like(images[:, :1])], 1).unsqueeze(1)
+    v2w0 = cano.view_to_world_transforms.reshape(1, 1, 4, 4).expand(B, 1, 4, 4).to(device)
+    q0 = cano.source_cv2wT_quat.reshape(1, 1, 4).expand(B, 1, 4).to(device)
+    net0, depth0 = model(x0, background, v2w0, q0, return_3d_features=True, render=False, squre_clip=squre_clip, unet_depth=depth,
+                         head=False)
+    nets, depths, v2ws, quats = [net0], [depth0], [v2w0.reshape(B, 4, 4)], [q0.reshape(B, 4)]
+    first = splat_head(net0, depth0, ray_dirs, v2ws[0], quats[0], squre_clip)
+
+    wv, fp, cc = (orbit.world_view_transforms.to(device), orbit.full_proj_transforms.to(device),
+                  orbit.camera_centers.to(device))
+    # (workspace=None: a workspace of this call's own, which no later forward can make stale before backward() reads it)
+    r = render_views(first, None, wv, fp, cc, background, cfg, epilogue=False, differentiable=True)
+    xin, zmed = cycle_inputs(r["raster"], B, num_views)
+    if not grad_through_renders:
+        xin, zmed = xin.detach(), zmed.detach()
+
+    v2w = orbit.view_to_world_transforms.to(device)
+    quat = orbit.source_cv2wT_quat.to(device)
+    for v in range(num_views):
+        net_v, depth_v = model(xin[v].unsqueeze(1), background, v2w[v:v + 1].expand(B, 1, 4, 4), quat[v:v + 1].expand(B, 1, 4),
+                               return_3d_features=True, render=False, squre_clip=squre_clip, unet_depth=zmed[v], head=False)
+        nets.append(net_v)
+        depths.append(depth_v)
+        v2ws.append(v2w[v].reshape(1, 4, 4).expand(B, 4, 4))
+        quats.append(quat[v].reshape(1, 4).expand(B, 4))
+    merged = splat_head_merge(nets, depths, ray_dirs, v2ws, quats, squre_clip)
+    if return_renders:
+        xb = xin.transpose(0, 1)
         return merged, dict(rgb=xb[:, :, :3], alpha=xb[:, :, 3:4], depth=zmed.transpose(0, 1))
     return merged
 

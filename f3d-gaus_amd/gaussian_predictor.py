@@ -15,6 +15,7 @@ What is different by design (MI355X-first):
     composition, SH rotation, NCHW -> N x C flattening, multi-view union -- is libf3dg_hip's ``f3dg_splat_head``
     (one pass, 96 B read + 96 B written per Gaussian) instead of ~15 torch kernels and permute copies;
   * ``forward(..., out=, n_offset=)`` lets the cycle loop write each pass straight into the aggregated buffers;
+  * ``splat_head_merge`` is that merge under autograd: K passes, one node, the merged cotangents read in place;
   * under autograd the head is a ``torch.autograd.Function`` over ``f3dg_splat_head_backward``, so the rasterizer's gradients reach
     the network (``net_out``, ``unet_depth``); the cameras and ``ray_dirs`` get none, and ``out=`` stays an inference form;
   * the backbone's x2 up / down resampling uses nearest-upsample / 2x2 mean (identical maths to the reference's
@@ -437,6 +438,97 @@ def splat_head(net_out, depth, ray_dirs, view_to_world, cam_quat, squre_clip=100
     return _splat_head_call(net_out, depth, ray_dirs, v2w, quat, squre_clip, out, n_total, n_offset)
 
 
+class _SplatHeadMerge(torch.autograd.Function):
+    """K splat-head passes into ONE set of merged buffers [B, K*HW, ...] (pass k at rows k*HW .. (k+1)*HW) as one autograd node: the
+    forward is K ``f3dg_splat_head`` launches into one allocation, the backward K ``f3dg_splat_head_backward`` launches that read the
+    merged cotangents where they lie (``n_total = K*HW``, ``n_offset = k*HW``) -- no ``torch.cat`` and no per-pass slice copies either
+    way. Inputs after the constants: K net_outs, K depths, K view_to_worlds, K cam_quats (prepared: contiguous float32)."""
+
+    @staticmethod
+    def forward(ctx, ray_dirs, squre_clip, K, *tensors):
+        nets, depths, v2ws, quats = (tensors[i * K:(i + 1) * K] for i in range(4))
+        B, _, H, W = nets[0].shape
+        HW = H * W
+        ctx.set_materialize_grads(False)
+        out = allocate_gaussians(B, K * HW, nets[0].device)
+        for k in range(K):
+            _splat_head_call(nets[k], depths[k], ray_dirs, v2ws[k], quats[k], squre_clip, out, K * HW, k * HW)
+        ctx.save_for_backward(ray_dirs, *tensors)
+        ctx.K, ctx.squre_clip = K, float(squre_clip)
+        return tuple(out[k] for k in GAUSSIAN_KEYS)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        K = ctx.K
+        ray_dirs, tensors = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        nets, depths, v2ws, quats = (tensors[i * K:(i + 1) * K] for i in range(4))
+        B, _, H, W = nets[0].shape
+        HW = H * W
+        device = nets[0].device
+        # dense once, for all K launches; a None cotangent ("this output was not used") goes to the kernel as NULL
+        gs = [None if g is None else g.to(device=device, dtype=torch.float32).contiguous() for g in grads]
+        need = ctx.needs_input_grad[3:]
+        d_nets, d_depths = [None] * K, [None] * K
+        L = _lib.lib()
+        for k in range(K):
+            need_net, need_depth = need[k], need[K + k]
+            if not (need_net or need_depth):
+                continue                    # a pass of data only: no launch
+            d_net = torch.empty_like(nets[k])           # (the kernel always writes it)
+            d_depth = torch.empty_like(depths[k]) if need_depth else None
+            rc = L.f3dg_splat_head_backward(
+                _stream(), B, H, W, _lib.ptr(nets[k]), _lib.ptr(depths[k]), _lib.ptr(ray_dirs), _lib.ptr(v2ws[k]), _lib.ptr(quats[k]),
+                ctx.squre_clip, K * HW, k * HW, *[_lib.ptr(g) for g in gs], _lib.ptr(d_net), _lib.ptr(d_depth))
+            _lib.check(rc, "f3dg_splat_head_backward")
+            d_nets[k] = d_net if need_net else None
+            d_depths[k] = d_depth
+        return (None, None, None, *d_nets, *d_depths, *([None] * (2 * K)))
+
+
+def splat_head_merge(net_outs, depths, ray_dirs, view_to_worlds, cam_quats, squre_clip=10000.0):
+    """The splat head of K predictor passes merged into one Gaussian set: ``net_outs[k]`` [B,23,H,W], ``depths[k]`` [B,1,H,W],
+    ``view_to_worlds[k]`` [B,4,4], ``cam_quats[k]`` [B,4], one ``ray_dirs``. Returns the seven ``GAUSSIAN_KEYS`` as [B, K*H*W, ...] with
+    pass k at rows k*HW .. (k+1)*HW: the layout ``cycle_aggregate`` builds.
+
+    With grad mode on it is ONE autograd node, differentiable in every ``net_outs[k]`` / ``depths[k]`` that requires grad (the backward
+    launches nothing for a pass in which neither does); the cameras and ``ray_dirs`` are data, as for ``splat_head``. Without grad it is
+    the ``splat_head(out=, n_offset=)`` loop."""
+    K = len(net_outs)
+    if K == 0 or not (len(depths) == len(view_to_worlds) == len(cam_quats) == K):
+        raise RuntimeError("splat_head_merge needs the same non-zero number of net_outs, depths, view_to_worlds and cam_quats")
+    B, Cc, H, W = net_outs[0].shape
+    if Cc != 23:
+        raise RuntimeError("splat head expects the 23-channel with-offset / SH-degree-1 layout [3,1,3,4,3,9]")
+    device = net_outs[0].device
+    if device.type != "cuda":
+        raise RuntimeError("f3dgaus_amd splat head needs tensors on a HIP device (no CPU fallback)")
+    for k in range(K):
+        if tuple(net_outs[k].shape) != (B, 23, H, W) or depths[k].numel() != B * H * W:
+            raise RuntimeError(f"pass {k}: net_out must be [{B}, 23, {H}, {W}] and depth [{B}, 1, {H}, {W}] like pass 0's")
+    grad_on = torch.is_grad_enabled()
+    if grad_on:
+        named = [("ray_dirs", ray_dirs)] + [(f"view_to_worlds[{k}]", t) for k, t in enumerate(view_to_worlds)] + [
+            (f"cam_quats[{k}]", t) for k, t in enumerate(cam_quats)]
+        for name, t in named:
+            if t.requires_grad:
+                raise NotImplementedError(f"the splat head produces no gradient for `{name}` (cameras and ray directions are data in "
+                                          "every caller): detach it")
+    if not (grad_on and any(t.requires_grad for t in (*net_outs, *depths))):
+        with torch.no_grad():
+            out = allocate_gaussians(B, K * H * W, device)
+            for k in range(K):
+                splat_head(net_outs[k], depths[k], ray_dirs, view_to_worlds[k], cam_quats[k], squre_clip, out=out, n_offset=k * H * W)
+        return out
+    f = lambda t: t.to(device=device, dtype=torch.float32).contiguous()
+    nets = [f(t) for t in net_outs]
+    deps = [f(t).reshape(B, 1, H, W) for t in depths]
+    v2ws = [f(t).reshape(B, 16) for t in view_to_worlds]
+    quats = [f(t).reshape(B, 4) for t in cam_quats]
+    res = _SplatHeadMerge.apply(f(ray_dirs), float(squre_clip), K, *nets, *deps, *v2ws, *quats)
+    return dict(zip(GAUSSIAN_KEYS, res))
+
+
 class GaussianSplatPredictor_gtunet(nn.Module):
     def invalidate_filter_cache(self):
         """Forget every convolution's converted filter copy (see ``Conv2d.invalidate_filter_cache``: needed after writes through
@@ -517,10 +609,12 @@ class GaussianSplatPredictor_gtunet(nn.Module):
         return split, scale, bias
 
     def forward(self, x, source_cameras_view_to_world, source_cv2wT_quat=None, focals_pixels=None,
-                return_depth=False, squre_clip=10000.0, unet_depth=None, out=None, n_offset=0):
+                return_depth=False, squre_clip=10000.0, unet_depth=None, out=None, n_offset=0, head=True):
         """x [B,Nv,4,H,W]; view_to_world [B,Nv,4,4]; quat [B,Nv,4]; unet_depth [B*Nv,1,H,W] (bchw).
         ``out`` / ``n_offset`` (extension): write into preallocated aggregated buffers [B, n_total, ...];
-        requires Nv == 1 so that image b's Gaussians stay contiguous."""
+        requires Nv == 1 so that image b's Gaussians stay contiguous.
+        ``head=False`` (extension): stop before the splat head and return ``(net_out [B*Nv,23,H,W], depth [B*Nv,1,H,W])``, what
+        ``splat_head`` / ``splat_head_merge`` take -- the training form of the cycle aggregation merges several passes in one node."""
         assert focals_pixels is None, "Unexpected argument for srn dataset"
         assert source_cv2wT_quat is not None
         assert unet_depth is not None, "F3D-Gaus feeds the (monocular or rendered) depth map as unet_depth"
@@ -554,6 +648,8 @@ class GaussianSplatPredictor_gtunet(nn.Module):
         net_out = net_out.contiguous()                  # (the splat head reads planar channels)
         H, W = net_out.shape[-2:]
         depth = unet_depth.reshape(B * Nv, 1, H, W)
+        if not head:
+            return net_out, depth
         if out is not None:
             if Nv != 1:
                 raise RuntimeError("in-place aggregation (out=) needs one view per call")

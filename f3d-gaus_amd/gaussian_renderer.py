@@ -388,12 +388,8 @@ def render_views(pc: dict, bs, world_view_transforms, full_proj_transforms, came
             "radii": radii, "raster": raster, "workspace": ws}
 
 
-def cycle_inputs(raster, B, V):
-    """rasters [B * V, 9, H, W] (image-major) -> (xin [V, B, 4, H, W] = cat(clamp(rgb, 0, 1), alpha), depth [V, B, 1, H, W]):
-    the next predictor inputs of the cycle aggregation (visualize.py:311, 331-333), view-major, in one kernel."""
-    if raster.device.type != "cuda":
-        raise RuntimeError("f3dgaus_amd.cycle_inputs needs a HIP tensor (no CPU fallback)")
-    raster = raster.contiguous()
+def _cycle_inputs_call(raster, B, V):
+    """The raw hand-off kernel on a contiguous float32 raster."""
     H, W = raster.shape[-2:]
     xin = torch.empty((V, B, 4, H, W), dtype=torch.float32, device=raster.device)
     depth = torch.empty((V, B, 1, H, W), dtype=torch.float32, device=raster.device)
@@ -401,3 +397,40 @@ def cycle_inputs(raster, B, V):
                                       _lib.ptr(raster), _lib.ptr(xin), _lib.ptr(depth))
     _lib.check(rc, "f3dg_cycle_inputs")
     return xin, depth
+
+
+class _CycleInputs(torch.autograd.Function):
+    """``f3dg_cycle_inputs`` with ``f3dg_cycle_inputs_backward`` behind it: the raster is saved for the clamp mask, an unused output's
+    cotangent reaches the kernel as NULL."""
+
+    @staticmethod
+    def forward(ctx, raster, B, V):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(raster)
+        ctx.BV = (int(B), int(V))
+        return _cycle_inputs_call(raster, B, V)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_xin, g_depth):
+        raster, = ctx.saved_tensors
+        B, V = ctx.BV
+        H, W = raster.shape[-2:]
+        dense = lambda g: None if g is None else g.to(device=raster.device, dtype=torch.float32).contiguous()
+        g_xin, g_depth = dense(g_xin), dense(g_depth)
+        d_raster = torch.empty_like(raster)
+        rc = _lib.lib().f3dg_cycle_inputs_backward(_stream(), B, V, int(H), int(W), _lib.ptr(raster), _lib.ptr(g_xin), _lib.ptr(g_depth),
+                                                   _lib.ptr(d_raster))
+        _lib.check(rc, "f3dg_cycle_inputs_backward")
+        return d_raster, None, None
+
+
+def cycle_inputs(raster, B, V):
+    """rasters [B * V, 9, H, W] (image-major) -> (xin [V, B, 4, H, W] = cat(clamp(rgb, 0, 1), alpha), depth [V, B, 1, H, W]):
+    the next predictor inputs of the cycle aggregation (visualize.py:311, 331-333), view-major, in one kernel. With grad mode on and a
+    raster that requires grad, both outputs carry the graph back to it (f3dg_cycle_inputs_backward, one kernel as well)."""
+    if raster.device.type != "cuda":
+        raise RuntimeError("f3dgaus_amd.cycle_inputs needs a HIP tensor (no CPU fallback)")
+    if torch.is_grad_enabled() and raster.requires_grad:
+        return _CycleInputs.apply(raster.contiguous(), B, V)
+    return _cycle_inputs_call(raster.contiguous(), B, V)

@@ -3,7 +3,8 @@
 gaussians)`` -- or the frames alone when ``return_3d_features`` is False --; and, with ``render=True``, one ``self.renderer`` call per
 image of the batch with the argument pattern of src/unet_gs.py:82-87 (image index, that image's camera rows as [1, ...] slices, its
 background row, ``config``), so the reference's ``render_predicted_more_v2_gof`` or this package's plugs in unchanged. Extension:
-``out`` / ``n_offset`` hand preallocated merged buffers to the predictor (cycle aggregation in place)."""
+``out`` / ``n_offset`` hand preallocated merged buffers to the predictor (cycle aggregation in place); ``head=False`` returns the predictor's
+``(net_out, depth)`` before the splat head."""
 import torch
 from torch import nn
 
@@ -34,7 +35,10 @@ class Unet_GS_gtunet(nn.Module):
     def forward(self, x_input, background, view_to_world_transforms, source_cv2wT_quat, return_3d_features=True,
                 render=False, return_depth=False, squre_clip=10000.0, world_view_transforms=None,
                 full_proj_transforms=None, camera_centers=None, config=None, image_size=None, unet_depth=None,
-                out=None, n_offset=0):
+                out=None, n_offset=0, head=True):
+        if not head:        # (net_out, depth): the inputs of splat_head / splat_head_merge, nothing rendered
+            return self.gaussian_predictor(x_input, view_to_world_transforms, source_cv2wT_quat, focals_pixels=None,
+                                           return_depth=return_depth, squre_clip=squre_clip, unet_depth=unet_depth, head=False)
         in_place = {} if out is None else {"out": out, "n_offset": n_offset}
         predicted = self.gaussian_predictor(x_input, view_to_world_transforms, source_cv2wT_quat, focals_pixels=None,
                                             return_depth=return_depth, squre_clip=squre_clip, unet_depth=unet_depth, **in_place)

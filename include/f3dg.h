@@ -35,6 +35,8 @@
  *       the torch post-processing of render_predicted_more_v2_gof  src/gaussian_renderer/__init__.py:881-909, 1043-1053
  *   f3dg_render_epilogue_backward
  *       what torch.autograd derives from those same lines (they are plain torch ops on the raster in the reference)
+ *   f3dg_cycle_inputs_backward
+ *       what torch.autograd derives from the hand-off of the cycle aggregation   visualize.py:311, 331-333
  *   f3dg_marching_tets_count / f3dg_marching_tets_emit
  *       the integer topology of _unbatched_marching_tetrahedra     src/utils_tetmesh.py:47-138 (torch.unique + mask indexing there)
  *   f3dg_ssim_forward / f3dg_ssim_backward
@@ -444,6 +446,21 @@ int f3dg_compose_frames_size(int n_frames, int n_images, int H, int W, int nrow,
  * b * V + v) to the next predictor inputs, view-major: xin [V, B, 4, H, W] = cat(clamp(rgb, 0, 1), alpha) and
  * depth [V, B, 1, H, W] = the median depth. One kernel; H * W must be a multiple of 4 and the pointers 16-byte aligned. */
 int f3dg_cycle_inputs(void* stream, int B, int V, int H, int W, const float* raster, float* xin, float* depth);
+
+/* Adjoint of f3dg_cycle_inputs: the vector-Jacobian product that torch.autograd derives from the hand-off's torch lines
+ * (clamp, two slices, cat). The same launch shape as the forward: one thread per four pixels, 16-byte loads and stores, grid.y = B * V.
+ *   raster   [B * V, 9, H, W]: the forward's input, read for the clamp mask only (channels 0..2).
+ *   g_xin    [V, B, 4, H, W], g_depth [V, B, 1, H, W]: the cotangents, view-major as the forward wrote its outputs. Either may be
+ *            NULL = "this output was not used": all of its entries count as zero.
+ *   d_raster [B * V, 9, H, W], image-major: frame n = b * V + v takes its cotangents from slot v * B + b. Every element is written
+ *            (no accumulation, the caller need not zero it):
+ *     channels 0..2   g_xin[slot, c] where 0 <= raster <= 1 (0, 1 and -0.0 pass; NaN and +-Inf do not), else +0.0. The masked value is
+ *                     SELECTED, never g * 0: a masked position is +0.0 even under a NaN or Inf cotangent;
+ *     channel  7      g_xin[slot, 3];      channel 6      g_depth[slot];      channels 3, 4, 5, 8      0.
+ * F3DG_ERR_BAD_ARG before any HIP call: NULL raster or d_raster, non-positive V, H or W, B < 0, H * W not a multiple of 4, a pointer
+ * that is not 16-byte aligned, B * V > 65,535. B == 0: F3DG_OK at once. */
+int f3dg_cycle_inputs_backward(void* stream, int B, int V, int H, int W, const float* raster,
+                               const float* g_xin, const float* g_depth, float* d_raster);
 
 /* Fused GroupNorm (+ SiLU when apply_silu != 0) of the predictor's SongUNet backbone (src/gaussian_predictor.py:250-262 and the
  * `silu(norm(x))` of its residual blocks, :318-323): x, y [N,C,HW] float32 contiguous (NCHW), weight / bias [C],
