@@ -6,10 +6,15 @@
 //     ray and the Gaussian's record only;
 //   * the RECURRENCE -- test_T = T (1 - alpha), the saturation stop, the distortion sums, the colour / normal / alpha accumulators, the
 //     median-depth switch (forward.cu:543-583): a function of the pixel's running state and six numbers of the stateless part.
-// f3dg_pair_eval is the first, f3dg_pair_apply the second; applying the one to the other's result reproduces blend_entry /
-// blend_entry_fast of f3dg_render.hip operation for operation (the values handed over are float32 in the reference too). The split lets
+// f3dg_pair_eval is the first, f3dg_pair_apply the second (the values handed over are float32 in the reference too). The split lets
 // the packed schedule of f3dg_render4.hip evaluate the stateless part for (pixel, Gaussian) pairs of DIFFERENT pixels in one wave trip,
 // one pair per lane, and leave only the recurrence to the lane that owns the pixel.
+//
+// This header is the ONE copy of the blend arithmetic of every quadrant kernel (render3s, render4, render3p, render3q, render5,
+// render5p), in both modes, together with what is not schedule-specific around it: the pixel's state (F3dgPixel), the fused trip of a
+// pixel on one staged slot (f3dg_fused_trip) and the pixel's write-out (f3dg_pixel_store). The plain transcription
+// (render_fwd_kernel, f3dg_render.hip) does NOT include it: it keeps its own state, its own blend_entry and its own write-out, written
+// straight from the reference, so that the bit-identity tests compare this header against an independent transcription.
 //
 // FAST = false: the reference's float32 / float64 operation order (the file is built with -ffp-contract=off).
 // FAST = true:  the inference arithmetic of f3dg_common.h (f3dg_fast_t_G: error-free float32 pairs for the float64 island, hardware
@@ -36,6 +41,8 @@ __device__ __forceinline__ void f3dg_pixel_init(F3dgPixel& st)
 // a blended pair always has alpha >= 1/255.
 struct F3dgPair {
     float alpha, t, m, nn0, nn1, nn2;     // m: the NDC image of t (mapped_max_t); nn: the unit normal, already negated
+    bool live;                            // alpha != 0, straight from the evaluation's own tests: what f3dg_fused_trip branches on (a compare of
+                                          // the selected alpha costs the fast trip three instructions). The hand-overs through LDS carry alpha only
 };
 
 // q0 = (v0 v1 v2 v3), q1 = (v4 v5 v6 v7), q2 = (v8 v9 opacity K): the first three 16-byte chunks of the Gaussian's record
@@ -44,6 +51,7 @@ __device__ __forceinline__ F3dgPair f3dg_pair_eval(float ray_x, float ray_y, con
 {
     F3dgPair pr;
     pr.alpha = 0.0f; pr.t = 0.0f; pr.m = 0.0f; pr.nn0 = pr.nn1 = pr.nn2 = 0.0f;
+    pr.live = false;
     // the reference's own float32 a and b / 2, in its operation order (forward.cu:499-509)
     const float n0 = q0.x * ray_x + q0.y * ray_y + q0.z;
     const float n1 = q0.y * ray_x + q0.w * ray_y + q1.x;
@@ -57,7 +65,8 @@ __device__ __forceinline__ F3dgPair f3dg_pair_eval(float ray_x, float ray_y, con
         // (double)t <= 0.2  <=>  t < 0.2f: 0.2f is the float just above 0.2 (false for NaN, as the reference's test)
         const bool behind = t < 0.2f;
         const float alpha = fminf(0.99f, opac * G);
-        pr.alpha = (behind || alpha < 1.0f / 255.0f) ? 0.0f : alpha;
+        pr.live = !(behind || alpha < 1.0f / 255.0f);
+        pr.alpha = pr.live ? alpha : 0.0f;
         // a rejected pair gets a harmless depth: t = -b / a may be infinite or NaN there, and the branch-free recurrence
         // (f3dg_pair_apply_flat) multiplies every handed-over number by a zero weight instead of skipping it
         pr.t = SANITIZE ? (pr.alpha != 0.0f ? t : 1.0f) : t;
@@ -92,6 +101,7 @@ __device__ __forceinline__ F3dgPair f3dg_pair_eval(float ray_x, float ray_y, con
                 }
             }
         }
+        pr.live = pr.alpha != 0.0f;
     }
     return pr;
 }
@@ -199,4 +209,57 @@ __device__ __forceinline__ bool f3dg_pair_apply_flat(F3dgPixel& st, unsigned con
     st.Tr = go ? test_T : Tr;
     st.last_contributor = go ? contributor : st.last_contributor;
     return sat;
+}
+
+// One FUSED trip of phase 2: the pixel of this lane takes staged slot j of the window sR ([16-byte chunk][slot]) through the stateless
+// part and the recurrence. Returns true when the pixel saturates (`done`). The loop around it, its counters and what a caller does with
+// `done` are the caller's: that is where the schedules differ.
+template <bool FAST, bool NORMAL, bool DIST>
+__device__ __forceinline__ bool f3dg_fused_trip(F3dgPixel& st, const float4 (*sR)[64], unsigned j, unsigned contributor, float ray_x, float ray_y)
+{
+    const float4 q0 = sR[0][j], q1 = sR[1][j], q2 = sR[2][j], q3 = sR[3][j];
+    const F3dgPair pr = f3dg_pair_eval<FAST, NORMAL, DIST, false>(ray_x, ray_y, q0, q1, q2);
+    // of chunks 2 and 3 a trip uses three words (K and the ellipse's c are phase 1's), and hipcc narrows those loads to ds_read_b96 --
+    // which takes 8 LDS cycles per wave where ds_read_b128 takes 4 (MI355X_MICROARCH.md, LDS table). An empty asm that "uses" the fourth
+    // words keeps the loads 16 bytes wide; it sits behind the evaluation so that the arithmetic on the first chunks starts while the
+    // last ones are still on their way
+    asm volatile("" :: "v"(q2.w), "v"(q3.w), "v"(pr.t));
+    if (pr.live)
+        return f3dg_pair_apply<FAST, NORMAL, DIST>(st, contributor, pr, q3.x, q3.y, q3.z);
+    return false;
+}
+
+// The pixel's write-out (forward.cu:584-611): colour over the background, the distortion normalised in float64, the other channels as
+// accumulated; with SAVE_AUX the planes the backward reads (final_T [V][4][HW]: T, dist1, dist2, the distortion before normalisation;
+// n_contrib [V][2][HW]: last and median contributor). NORMAL / DIST = false: channels 3..5 / 8 are not written. For a pixel inside the
+// image only.
+template <bool SAVE_AUX, bool NORMAL, bool DIST>
+__device__ __forceinline__ void f3dg_pixel_store(const F3dgPixel& st, unsigned view, size_t pix_id, size_t HW, const float* background, int bg_per_view,
+                                                 float* out_color, float* final_T, unsigned* n_contrib)
+{
+    const float* bg = background + (bg_per_view ? 3 * view : 0);
+    const float Tr = st.Tr;
+    const float distortion = (float)(st.distortion / ((1 - Tr) * (1 - Tr) + 1e-7));
+    if (SAVE_AUX) {
+        float* fT = final_T + (size_t)view * 4 * HW;
+        fT[pix_id] = Tr;
+        fT[pix_id + HW] = st.dist1;
+        fT[pix_id + 2 * HW] = st.dist2;
+        fT[pix_id + 3 * HW] = st.distortion;
+        unsigned* nc = n_contrib + (size_t)view * 2 * HW;
+        nc[pix_id] = st.last_contributor;
+        nc[pix_id + HW] = st.max_contributor;
+    }
+    float* out = out_color + (size_t)view * F3DG_OUT_CHANNELS * HW;
+    out[0 * HW + pix_id] = st.C0 + Tr * bg[0];
+    out[1 * HW + pix_id] = st.C1 + Tr * bg[1];
+    out[2 * HW + pix_id] = st.C2 + Tr * bg[2];
+    if (NORMAL) {
+        out[3 * HW + pix_id] = st.C3;
+        out[4 * HW + pix_id] = st.C4;
+        out[5 * HW + pix_id] = st.C5;
+    }
+    out[6 * HW + pix_id] = st.C6;
+    out[7 * HW + pix_id] = st.C7;
+    if (DIST) out[8 * HW + pix_id] = distortion;
 }

@@ -72,7 +72,7 @@ struct F3dgHeader {
 // The first three float4 are everything the conservative pre-test needs; the 4th is only read by contributors.
 struct __attribute__((aligned(16))) F3dgRec { float f[F3DG_REC_FLOATS]; };
 
-// The "fast" arithmetic of a (pixel, Gaussian) pair up to G = exp(power) (option render_fast; f3dg_render.hip: blend_entry_fast). ONE
+// The "fast" arithmetic of a (pixel, Gaussian) pair up to G = exp(power) (option render_fast; f3dg_blend.h: f3dg_pair_eval). ONE
 // definition, because the compositing backward must repeat the forward's alpha to the bit when the forward took this mode
 // (F3dgHeader::alpha_fast). aaf, bhalf are the reference's own float32 a and b / 2 (forward.cu:499-509, in its operation order: their
 // rounding errors are amplified 1e5..1e6 x by the cancellation below and must be reproduced, not improved on), CC is the quadric's
@@ -214,9 +214,6 @@ extern int g_f3dg_bwd_occ;             // waves per SIMD render3_bwd_kernel is c
 extern int g_f3dg_render_unroll;       // small launches (render_lowocc): entries per phase-2 trip of render3p (1 or 2); -1 = by launch size and arithmetic
 extern int g_f3dg_reference_kernels;   // diagnostic: 1 = the compositing forward and integrate pass 1 take the plain transcriptions (render_fwd_kernel,
                                        // integrate_pass1_kernel) in the reference's arithmetic: the baseline of the bit-identity tests
-int f3dg_launch_render_small(hipStream_t s, int V, int P, int W, int H, float focal_x, float focal_y, const F3dgHeader* hdr, const uint2* ranges,
-                         const unsigned* point_list, const F3dgRec* rec, const float4* cull, const float* background, int bg_per_view,
-                         float* out_color, int fast, int save_aux, float* final_T, unsigned* n_contrib, int unroll, int split, int count);
 extern int g_f3dg_render_split;        // small launches: 1 = two waves per quadrant (render3p_fwd_kernel: a producer wave scans, gathers and runs phase 1 for the window after the one the consumer wave composites)
 extern int g_f3dg_render_lowocc;       // n >= 1 (default 1): launches of at most max(2, n) x 1024 quadrant waves take the multi-wave kernels of f3dg_render4.hip; 0: never
 extern int g_f3dg_render_count;        // 1: the one-wave kernel's counting variant (diagnostic; f3dg_debug_render_counts)
@@ -232,26 +229,50 @@ int f3dg_launch_render(hipStream_t s, int V, int P, int W, int H, float focal_x,
                        float* final_T, unsigned* n_contrib, int save_aux, unsigned skip_channels = 0u, int fast = -1 /* -1: the process default */,
                        int scan = 0 /* the call carries F3DG_FLAG_SCAN */);
 
+// What every compositing forward launch is handed: f3dg_launch_render fills it once and picks the kernel family; the launchers of
+// f3dg_render4.hip / f3dg_render5.hip take it and only their own knobs. The kernels get its fields by value.
+struct F3dgRenderLaunch {
+    hipStream_t s;
+    int V, P, W, H, tiles_x, T;
+    float focal_x, focal_y;
+    const F3dgHeader* hdr;
+    const uint2* ranges;
+    const unsigned* point_list;
+    const F3dgRec* rec;
+    const float4* cull;
+    const float* background;
+    int bg_per_view;
+    float* out_color;
+    float* final_T;
+    unsigned* n_contrib;
+    int fast, save_aux;               // the call's arithmetic (resolved), F3DG_FLAG_SAVE_AUX
+    unsigned skip_channels;           // F3DG_FLAG_SKIP_NORMAL | F3DG_FLAG_SKIP_DISTORTION of the call
+    int count;                        // option render_count
+    // the batched loops of the build that consume RGB, depth and alpha only (cycle aggregation, orbit frames) skip the normal and
+    // distortion accumulators: the channels they do write are bit-identical
+    bool lean() const { return !save_aux && (skip_channels & (F3DG_FLAG_SKIP_NORMAL | F3DG_FLAG_SKIP_DISTORTION)) == (F3DG_FLAG_SKIP_NORMAL | F3DG_FLAG_SKIP_DISTORTION); }
+    dim3 quadrants() const { return dim3((unsigned)V * (unsigned)T * 4u); }      // the grid of a quadrant kernel
+};
+// records the name of the compositing forward kernel just launched (f3dg_debug_last_render_kernel; per host thread)
+void f3dg_note_render_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+// debug read-outs of a kernel family's work counters: h_out[16] = the first `rows` of the [64][16] device symbol summed; reset clears all 64
+int f3dg_read_render_counts(const void* symbol, int rows, unsigned long long* h_out, int reset);
+// small launches (f3dg_render4.hip): render3p (split 1; unroll = entries per trip) or render3q (split 2 / 3 = evaluator waves)
+int f3dg_launch_render_small(const F3dgRenderLaunch& a, int unroll, int split);
+
 // the rank-packed compositing forward (f3dg_render4.hip; option render_pack)
 extern int g_f3dg_render_pack;         // -1 (default): inference launches in the reference's arithmetic take render4; 1: all inference launches; 0: none
 extern int g_f3dg_render_pack_th;      // trips of a slide with at most this many participating pixels are packed (default 32; 0: never)
-int f3dg_launch_render4(hipStream_t s, int V, int P, int W, int H, float focal_x, float focal_y, const F3dgHeader* hdr, const uint2* ranges,
-                        const unsigned* point_list, const F3dgRec* rec, const float4* cull, const float* background, int bg_per_view,
-                        float* out_color, int fast, unsigned skip_channels, int count, int save_aux = 0, float* final_T = nullptr,
-                        unsigned* n_contrib = nullptr);
+int f3dg_launch_render4(const F3dgRenderLaunch& a);
 
 // the split-pixel compositing forward (f3dg_render5.hip; F3DG_FLAG_SCAN / option render_scan: fast inference launches of the general path)
 extern int g_f3dg_render_scan;         // -1 (default): calls with F3DG_FLAG_SCAN; 1: every eligible launch; 0: never
 extern int g_f3dg_render_scan_min;     // stragglers holding fewer older-half entries than this finish the slide in fused trips (default 4; 0: always compact)
 extern int g_f3dg_render_scan_th;      // fused trips while more than this many pixels take part (default 12)
-int f3dg_launch_render5(hipStream_t s, int V, int P, int W, int H, float focal_x, float focal_y, const F3dgHeader* hdr, const uint2* ranges,
-                        const unsigned* point_list, const F3dgRec* rec, const float4* cull, const float* background, int bg_per_view,
-                        float* out_color, unsigned skip_channels, int count);
+int f3dg_launch_render5(const F3dgRenderLaunch& a);
+int f3dg_launch_render5_small(const F3dgRenderLaunch& a);         // one- and two-view launches: four lanes per pixel (render5p_fwd_kernel)
 
 // the dense compositing backward (f3dg_backward5.hip; option bwd_dense)
-int f3dg_launch_render5_small(hipStream_t s, int V, int P, int W, int H, float focal_x, float focal_y, const F3dgHeader* hdr, const uint2* ranges,
-                              const unsigned* point_list, const F3dgRec* rec, const float4* cull, const float* background, int bg_per_view,
-                              float* out_color);
 extern int g_f3dg_bwd_dense;           // 1: render5_bwd_kernel (entry-major batches of (pixel, entry) pairs, segmented scans); 0: render3_bwd_kernel (lock-step walk)
 int f3dg_launch_render5_bwd(hipStream_t s, int V, int P, int W, int H, int tiles_x, int T, float focal_x, float focal_y, F3dgHeader* hdr,
                             const uint2* ranges, const unsigned* point_list, const unsigned* small_list, const F3dgRec* rec, const float4* cull,

@@ -1,8 +1,8 @@
 // f3dg_quad.h -- the front end of the quadrant kernels: a workgroup's 8x8 pixel quadrant and its lane's pixel, the tile's list range,
 // and F3dgHalfWindow, the sliding half-window of the one-wave compositing forwards (render3s_fwd_kernel, render4_fwd_kernel,
-// render5_fwd_kernel) up to and including phase 1. Every kernel keeps its own phase 2. Everything here is
-// force-inlined. The plain reference kernels (render_fwd_kernel, integrate_pass1_kernel) do not use this
-// header: the bit-identity tests compare every other path against them.
+// render5_fwd_kernel) up to and including phase 1. Phase 2 is the kernel's own loop around f3dg_fused_trip
+// (f3dg_blend.h). Everything here is force-inlined. The plain reference kernels (render_fwd_kernel, integrate_pass1_kernel) do not use
+// this header: the bit-identity tests compare every other path against them.
 #pragma once
 #include "f3dg_common.h"
 #include "f3dg_ellipse.h"

@@ -5,32 +5,37 @@
 // of the quadric along the ray into an alpha, and blend RGB, view-space normal, median depth, alpha and the 2DGS-style distortion
 // term front to back. All views of a call are ONE launch; an XCD-aware id -> (view, tile) map keeps a view's records in one L2.
 //
-// The blend is a strict per-pixel recurrence whose float32 / float64 operation order is the reference's (blend_entry; the file is
-// built with -ffp-contract=off): the exponent -(1/2)(C - B^2/4A) cancels 1e5..1e6 x and any re-association moves isolated pixels by
-// 1e-2. blend_entry_fast is the inference-mode variant: the same float32 a, b in the reference's order, the float64
-// island replaced by error-free float32 pairs. There is no inter-pixel arithmetic, hence no MFMA.
+// The blend is a strict per-pixel recurrence whose float32 / float64 operation order is the reference's (the file is built with
+// -ffp-contract=off): the exponent -(1/2)(C - B^2/4A) cancels 1e5..1e6 x and any re-association moves isolated pixels by 1e-2
+// (SURVEY 0.9). There is no inter-pixel arithmetic, hence no MFMA.
 //
-// The kernels here only ever REMOVE (pixel, Gaussian) pairs that are a bare `continue` in the reference (alpha < 1/255 proven by a
-// conservative test), so their images are bit-identical within an arithmetic mode:
+// Two kernels, and two copies of that arithmetic ON PURPOSE:
 //   render3s_fwd_kernel (the default of the general path): one wave64 per 8x8 pixel quadrant, no workgroup barriers, sliding
-//       half-windows of staged records. See the comment above the kernel. The multi-wave kernels of f3dg_render4.hip / f3dg_render5.hip
-//       share its blend arithmetic.
+//       half-windows of staged records. See the comment above the kernel. Its blend arithmetic, in the reference's order and in the
+//       fast inference mode, its fused trip and its write-out are those of f3dg_blend.h, shared with the multi-wave kernels of
+//       f3dg_render4.hip / f3dg_render5.hip. These kernels only ever REMOVE (pixel, Gaussian) pairs that are a bare `continue` in the
+//       reference (alpha < 1/255 proven by a conservative test), so their images are bit-identical within an arithmetic mode.
 //   render_fwd_kernel (option reference_kernels): the plain transcription -- every pixel visits every entry of its tile's list in the
 //       reference's arithmetic. It is the baseline every other compositing kernel is compared with bit for bit
-//       (tests/test_raster_forward_gpu.py::test_pretest_is_conservative_bit_identical_outputs).
+//       (tests/test_raster_forward_gpu.py::test_pretest_is_conservative_bit_identical_outputs), so it shares NOTHING with them: its
+//       pixel state, its blend_entry and its write-out stand next to it, written straight from the reference, and it uses neither
+//       f3dg_blend.h nor f3dg_quad.h. A slip in the shared arithmetic therefore shows as a difference between two independent texts.
 // t = -BB/(2*AA) is a double quotient of float-valued operands rounded to float: identical to ONE IEEE float32 divide (double
 // rounding is innocuous for p = 24, q = 53 >= 2p + 2), so the float64 divide is not needed.
+#include "f3dg_blend.h"
 #include "f3dg_common.h"
 #include "f3dg_ellipse.h"
 #include "f3dg_quad.h"
 
+#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 
-extern thread_local const char* g_f3dg_last_render_kernel;
-
 namespace {
 
+// ---- the plain transcription (option reference_kernels): one workgroup per tile, one pixel per lane, every pixel visits every entry of
+// the tile's list in the reference's arithmetic (blend_entry). Nothing is filtered: the baseline of the bit-identity tests. PixelState,
+// blend_entry and the write-out at the kernel's end are its own (see the file header).
 struct PixelState {
     float Tr;
     unsigned last_contributor, max_contributor;
@@ -40,9 +45,6 @@ struct PixelState {
 
 // The reference's per-(pixel, Gaussian) arithmetic after the geometric terms (forward.cu:511-579), in its operation
 // order. Returns true when the pixel saturates (`done = true`); `contributor` is the 1-based position in the tile list.
-// NORMAL / DIST = false (f3dg_forward_sets with F3DG_FLAG_SKIP_NORMAL / F3DG_FLAG_SKIP_DISTORTION; the one-wave kernel only): the normal
-// channels 3..5 / the distortion channel 8 are neither accumulated nor written; every other channel is bit-identical.
-template <bool NORMAL = true, bool DIST = true>
 __device__ __forceinline__ bool blend_entry(PixelState& st, unsigned contributor, float n0, float n1, float n2, float aaf,
                                             float bhalf, float CC, float opac, float cr, float cg, float cb)
 {
@@ -70,7 +72,7 @@ __device__ __forceinline__ bool blend_entry(PixelState& st, unsigned contributor
     if (test_T < 0.0001f)
         return true;
 
-    if (DIST) {
+    {
         const float mapped_max_t = (float)((F3DG_FAR_PLANE * t - F3DG_FAR_PLANE * F3DG_NEAR_PLANE) / ((F3DG_FAR_PLANE - F3DG_NEAR_PLANE) * t));
         const float A = 1 - Tr;
         const float error = mapped_max_t * mapped_max_t * A + st.dist2 - 2 * mapped_max_t * st.dist1;
@@ -82,7 +84,7 @@ __device__ __forceinline__ bool blend_entry(PixelState& st, unsigned contributor
     st.C0 += cr * alpha * Tr;
     st.C1 += cg * alpha * Tr;
     st.C2 += cb * alpha * Tr;
-    if (NORMAL) {
+    {
         const float length = (float)sqrt(n0 * n0 + n1 * n1 + n2 * n2 + 1e-7);
         const float nn0 = -n0 / length, nn1 = -n1 / length, nn2 = -n2 / length;
         st.C3 += nn0 * alpha * Tr;
@@ -100,73 +102,6 @@ __device__ __forceinline__ bool blend_entry(PixelState& st, unsigned contributor
     return false;
 }
 
-
-// Fast-mode counterpart of blend_entry (option "render_fast", the default): the same decisions and the same float32
-// accumulations, but the reference's float64 island (forward.cu:511-522,545,548) is evaluated with error-free float32
-// pairs instead of float64 divides / square roots:
-//   * aaf, bhalf (and n0..n2) are the reference's own float32 values, computed in its operation order by the caller:
-//     their rounding errors are amplified 1e5..1e6 x by the cancellation and must be reproduced, not improved on;
-//   * b^2/a is formed as a double-single quotient (q1 + q2, relative error ~2^-45): b*b = p + e exactly (FMA), q1 = p*r,
-//     q2 = ((p - q1*a) + e)*r with r ~ 1/a; C - q1 is exact (Sterbenz) wherever the exponent matters, so
-//     min_value = (C - q1) - q2 carries one float32 rounding of a number of magnitude <~ 20: |d power| <~ 1e-6;
-//   * t = -b/a from the same reciprocal with one Newton step (<= 1 ulp), exp() as v_exp_f32(power * log2 e),
-//     the NDC depth as c0 - c1/t with a hardware reciprocal, the normal with v_rsq_f32.
-// Every output stays within ~1e-6 relative of blend_entry's; the parity tests gate this mode at the same 1e-4 / 99.9 % /
-// 80 dB bar as the exact one (tests/test_raster_forward_gpu.py) and report both against the oracle.
-template <bool NORMAL = true, bool DIST = true>
-__device__ __forceinline__ bool blend_entry_fast(PixelState& st, unsigned contributor, float n0, float n1, float n2, float aaf,
-                                                 float bhalf, float CC, float opac, float cr, float cg, float cb)
-{
-    float t, G;
-    f3dg_fast_t_G(aaf, bhalf, CC, t, G);
-    // (double)t <= 0.2  <=>  t < 0.2f: 0.2f is the float just above 0.2 (false for NaN, as the reference's test). Tested together
-    // with alpha below: a wave nearly always holds a lane that passes, so an early branch here only costs scalar instructions
-    const bool behind = t < 0.2f;
-    const float alpha = fminf(0.99f, opac * G);
-    if (behind || alpha < 1.0f / 255.0f)
-        return false;
-    const float Tr = st.Tr;
-    const float test_T = Tr * (1 - alpha);
-    if (test_T < 0.0001f)
-        return true;
-
-    // (the accumulations below are contracted into FMAs: fewer roundings than the reference's separate products and sums, ~1e-8
-    // absolute on the distortion channel, whose values are 1e-7..1e-2)
-    const float w = alpha * Tr;
-    if (DIST) {
-        // (FAR*t - FAR*NEAR) / ((FAR - NEAR)*t) = FAR/(FAR-NEAR) - (FAR*NEAR/(FAR-NEAR)) / t
-        const float mapped_max_t = fmaf(-0.20040080160320642f, __builtin_amdgcn_rcpf(t), 1.0020040080160322f);
-        const float A = 1 - Tr;
-        const float m2 = mapped_max_t * mapped_max_t;
-        const float error = fmaf(-2.0f * mapped_max_t, st.dist1, fmaf(m2, A, st.dist2));
-        st.distortion = fmaf(error, w, st.distortion);
-        st.dist1 = fmaf(mapped_max_t, w, st.dist1);
-        st.dist2 = fmaf(m2, w, st.dist2);
-    }
-    st.C0 = fmaf(cr, w, st.C0);
-    st.C1 = fmaf(cg, w, st.C1);
-    st.C2 = fmaf(cb, w, st.C2);
-    if (NORMAL) {
-        // (the unit normal is formed first and then weighted -- the order of f3dg_blend.h, where the packed schedule of
-        // f3dg_render4.hip hands it from the lane that evaluated the pair to the lane that owns the pixel)
-        const float ninv = -__builtin_amdgcn_rsqf(fmaf(n2, n2, fmaf(n1, n1, n0 * n0)) + 1e-7f);
-        st.C3 = fmaf(n0 * ninv, w, st.C3);
-        st.C4 = fmaf(n1 * ninv, w, st.C4);
-        st.C5 = fmaf(n2 * ninv, w, st.C5);
-    }
-    if (Tr > 0.5f) {
-        st.C6 = t;
-        st.max_contributor = contributor;
-    }
-    st.C7 += w;
-
-    st.Tr = test_T;
-    st.last_contributor = contributor;
-    return false;
-}
-
-// ---- the plain transcription (option reference_kernels): one workgroup per tile, one pixel per lane, every pixel visits every entry of
-// the tile's list in the reference's arithmetic (blend_entry). Nothing is filtered: the baseline of the bit-identity tests.
 #define F3DG_ROUND (F3DG_BLOCK - 1)     // list entries staged per round; LDS slot F3DG_ROUND holds the vote counters
 
 template <bool SAVE_AUX>
@@ -251,7 +186,7 @@ render_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x,
             const float n2 = q0.z * ray_x + q1.x * ray_y + q1.y;
             const float aaf = ray_x * n0 + ray_y * n1 + n2;
             const float bhalf = q1.z * ray_x + q1.w * ray_y + q2.x;
-            done = blend_entry<>(st, round_base + (unsigned)j + 1u, n0, n1, n2, aaf, bhalf, q2.y, q2.z, q3.x, q3.y, q3.z);
+            done = blend_entry(st, round_base + (unsigned)j + 1u, n0, n1, n2, aaf, bhalf, q2.y, q2.z, q3.x, q3.y, q3.z);
         }
     }
 
@@ -307,14 +242,9 @@ __device__ unsigned long long g_f3dg_counts[64][16];
 //            ballot and lands, by two v_writelane, in the lane that owns the pixel (quad_ballots): 5 instructions per 64 tests, no
 //            per-block lists, no ds_bpermute.
 //   phase 2  pixels across the lanes: every pixel walks its own 64-bit pass mask in list order through the reference's recurrence
-//            (blend_entry / blend_entry_fast, unchanged); the bit index IS the LDS slot, so no per-block index list is read.
+//            (f3dg_fused_trip of f3dg_blend.h); the bit index IS the LDS slot, so no per-block index list is read.
 // The conservative filters only drop pairs that are a bare `continue` in the reference, so the images are bit-identical to the
 // plain transcription within an arithmetic mode (tests/test_raster_forward_gpu.py). LDS: 4 KB of records + 1 KB of queue per wave.
-
-// phase 2 reads the four 16-byte chunks of a record; of chunks 2 and 3 it uses three words (K and the ellipse's c are phase 1's), and
-// hipcc narrows those loads to ds_read_b96 -- which takes 8 LDS cycles per wave where ds_read_b128 takes 4 (MI355X_MICROARCH.md, LDS
-// table). An empty asm that "uses" the fourth word keeps the loads 16 bytes wide.
-#define F3DG_FULL16(a, b) asm volatile("" :: "v"((a).w), "v"((b).w))
 
 // ---- render3 with a SLIDING window (the default) ----------------------------------------------------------------------------------
 // With fixed 64-entry windows every lane waits at the end of a window for the lane with the most passing entries: the CPU model
@@ -345,11 +275,8 @@ render3s_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
     __shared__ unsigned sP[SAVE_AUX ? 64 : 1];                // list position of every staged slot (the reference's `contributor`)
 
     bool done = !inside;
-    PixelState st;
-    st.Tr = 1.0f;
-    st.last_contributor = 0; st.max_contributor = (unsigned)-1;
-    st.C0 = st.C1 = st.C2 = st.C3 = st.C4 = st.C5 = st.C6 = st.C7 = 0;
-    st.dist1 = st.dist2 = st.distortion = 0;
+    F3dgPixel st;
+    f3dg_pixel_init(st);
 
     unsigned n_useful = 0;
     unsigned n_half_sep = 0, n_half_pair = 0;
@@ -380,14 +307,7 @@ render3s_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
             const unsigned j = (unsigned)__builtin_ctzll(pass) ^ xr;
             pass &= pass - 1;
             if (COUNT) n_trips++;
-            const float4 q0 = sR[0][j], q1 = sR[1][j], q2 = sR[2][j], q3 = sR[3][j];
-            F3DG_FULL16(q2, q3);
-            const float n0 = q0.x * ray_x + q0.y * ray_y + q0.z;
-            const float n1 = q0.y * ray_x + q0.w * ray_y + q1.x;
-            const float n2 = q0.z * ray_x + q1.x * ray_y + q1.y;
-            const float aaf = ray_x * n0 + ray_y * n1 + n2;
-            const float bhalf = q1.z * ray_x + q1.w * ray_y + q2.x;
-            done = (FAST ? blend_entry_fast<NORMAL, DIST> : blend_entry<NORMAL, DIST>)(st, F3DG_SLOT_FLAG | j, n0, n1, n2, aaf, bhalf, q2.y, q2.z, q3.x, q3.y, q3.z);
+            done = f3dg_fused_trip<FAST, NORMAL, DIST>(st, sR, j, F3DG_SLOT_FLAG | j, ray_x, ray_y);
             if (done) pass = 0ull;
         }
         if (COUNT) {                // the loop ran as often as its busiest lane needed (lanes leave it, none re-enters)
@@ -437,76 +357,62 @@ render3s_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
         if (lane == 0) atomicAdd(&g_f3dg_counts[blockIdx.x & 63u][4], (unsigned long long)t);
     }
 
-    if (inside) {
-        const float* bg = background + (bg_per_view ? 3 * view : 0);
-        const float Tr = st.Tr;
-        const float distortion_before_normalized = st.distortion;
-        const float distortion = (float)(st.distortion / ((1 - Tr) * (1 - Tr) + 1e-7));
-
-        if (SAVE_AUX) {
-            float* fT = final_T + (size_t)view * 4 * HW;
-            fT[pix_id] = Tr;
-            fT[pix_id + HW] = st.dist1;
-            fT[pix_id + 2 * HW] = st.dist2;
-            fT[pix_id + 3 * HW] = distortion_before_normalized;
-            unsigned* nc = n_contrib + (size_t)view * 2 * HW;
-            nc[pix_id] = st.last_contributor;
-            nc[pix_id + HW] = st.max_contributor;
-        }
-        float* out = out_color + (size_t)view * F3DG_OUT_CHANNELS * HW;
-        out[0 * HW + pix_id] = st.C0 + Tr * bg[0];
-        out[1 * HW + pix_id] = st.C1 + Tr * bg[1];
-        out[2 * HW + pix_id] = st.C2 + Tr * bg[2];
-        if (NORMAL) {
-            out[3 * HW + pix_id] = st.C3;
-            out[4 * HW + pix_id] = st.C4;
-            out[5 * HW + pix_id] = st.C5;
-        }
-        out[6 * HW + pix_id] = st.C6;
-        out[7 * HW + pix_id] = st.C7;
-        if (DIST) out[8 * HW + pix_id] = distortion;
-    }
+    if (inside)
+        f3dg_pixel_store<SAVE_AUX, NORMAL, DIST>(st, view, pix_id, HW, background, bg_per_view, out_color, final_T, n_contrib);
 }
 
-} // namespace
-
-namespace {
-thread_local char g_kernel_name[160] = "";       // (per host thread: the library is called from several)
-void note_kernel(const char* base, int save_aux, int fast, const char* extra)
-{
-    snprintf(g_kernel_name, sizeof g_kernel_name, "%s<SAVE_AUX=%s, FAST=%s%s>", base, save_aux ? "true" : "false", fast ? "true" : "false", extra);
-    g_f3dg_last_render_kernel = g_kernel_name;
-}
 } // namespace
 
 int f3dg_render_uses_fast(int save_aux) { return g_f3dg_render_fast == 2 || (g_f3dg_render_fast == 1 && !save_aux); }
 
+// the compositing forward kernel the last f3dg_launch_render of this host thread launched (what `roofline.kernel` of bench.py prints)
+thread_local const char* g_f3dg_last_render_kernel = "";
+extern "C" const char* f3dg_debug_last_render_kernel(void) { return g_f3dg_last_render_kernel; }
+
+void f3dg_note_render_kernel(const char* fmt, ...)
+{
+    thread_local char name[160] = "";       // (per host thread: the library is called from several)
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(name, sizeof name, fmt, ap);
+    va_end(ap);
+    g_f3dg_last_render_kernel = name;
+}
+
+int f3dg_read_render_counts(const void* symbol, int rows, unsigned long long* h_out, int reset)
+{
+    unsigned long long buf[64][16];
+    F3DG_HIP_CHECK(hipMemcpyFromSymbol(buf, symbol, sizeof buf));
+    if (h_out)
+        for (int k = 0; k < 16; k++) {
+            h_out[k] = 0;
+            for (int r = 0; r < rows; r++) h_out[k] += buf[r][k];
+        }
+    if (reset) {
+        memset(buf, 0, sizeof buf);
+        F3DG_HIP_CHECK(hipMemcpyToSymbol(symbol, buf, sizeof buf));
+    }
+    return F3DG_OK;
+}
+
 namespace {
 
-// what every compositing launch is handed
-struct RenderArgs {
-    hipStream_t s;
-    int V, P, W, H, tiles_x, T;
-    float focal_x, focal_y;
-    const F3dgHeader* hdr;
-    const uint2* ranges;
-    const unsigned* point_list;
-    const F3dgRec* rec;
-    const float4* cull;
-    const float* background;
-    int bg_per_view;
-    float* out_color;
-    float* final_T;
-    unsigned* n_contrib;
-};
-
 template <bool AUX, bool FAST, bool NORMAL, bool DIST, bool COUNT>
-void launch3s(const RenderArgs& a)
+void launch3s(const F3dgRenderLaunch& a)
 {
-    F3DG_KLAUNCH((render3s_fwd_kernel<AUX, FAST, NORMAL, DIST, COUNT>), dim3((unsigned)a.V * (unsigned)a.T * 4u), dim3(64), 0, a.s,
+    F3DG_KLAUNCH((render3s_fwd_kernel<AUX, FAST, NORMAL, DIST, COUNT>), a.quadrants(), dim3(64), 0, a.s,
                  a.V, a.P, a.W, a.H, a.tiles_x, a.T, a.focal_x, a.focal_y, a.hdr, a.ranges, a.point_list, a.rec, a.cull, a.background, a.bg_per_view,
                  a.out_color, a.final_T, a.n_contrib);
 }
+
+template <bool AUX>
+void launch_plain(const F3dgRenderLaunch& a)
+{
+    F3DG_KLAUNCH((render_fwd_kernel<AUX>), dim3((unsigned)a.V * (unsigned)a.T), dim3(F3DG_BLOCK), 0, a.s, a.V, a.P, a.W, a.H, a.tiles_x, a.T, a.focal_x, a.focal_y,
+                 a.hdr, a.ranges, a.point_list, a.rec, a.background, a.bg_per_view, a.out_color, a.final_T, a.n_contrib);
+}
+
+const char* tf(int b) { return b ? "true" : "false"; }
 
 } // namespace
 
@@ -523,17 +429,14 @@ int f3dg_launch_render(hipStream_t s, int V, int P, int W, int H, float focal_x,
     const int tiles_x = (W + F3DG_TILE - 1) / F3DG_TILE, tiles_y = (H + F3DG_TILE - 1) / F3DG_TILE;
     const int T = tiles_x * tiles_y;
     const int fast = fast_arg < 0 ? f3dg_render_uses_fast(save_aux) : fast_arg;
+    const F3dgRenderLaunch a = { s, V, P, W, H, tiles_x, T, focal_x, focal_y, hdr, ranges, point_list, rec, cull, background, bg_per_view,
+                                 out_color, final_T, n_contrib, fast, save_aux, skip_channels, g_f3dg_render_count };
     const long long waves = (long long)V * T * 4;           // one wave per 8 x 8 pixel quadrant
     if (g_f3dg_reference_kernels) {
         // the plain transcription (the reference's arithmetic only: f3dg_forward_sets runs such a call with fast = 0)
         if (fast) return F3DG_ERR_BAD_ARG;
-        if (save_aux)
-            F3DG_KLAUNCH((render_fwd_kernel<true>), dim3((unsigned)V * (unsigned)T), dim3(F3DG_BLOCK), 0, s, V, P, W, H, tiles_x, T, focal_x, focal_y,
-                         hdr, ranges, point_list, rec, background, bg_per_view, out_color, final_T, n_contrib);
-        else
-            F3DG_KLAUNCH((render_fwd_kernel<false>), dim3((unsigned)V * (unsigned)T), dim3(F3DG_BLOCK), 0, s, V, P, W, H, tiles_x, T, focal_x, focal_y,
-                         hdr, ranges, point_list, rec, background, bg_per_view, out_color, final_T, n_contrib);
-        note_kernel("render_fwd_kernel", save_aux, 0, "");
+        if (save_aux) launch_plain<true>(a); else launch_plain<false>(a);
+        f3dg_note_render_kernel("render_fwd_kernel<SAVE_AUX=%s, FAST=false>", tf(save_aux));
         F3DG_HIP_CHECK(hipGetLastError());
         return F3DG_OK;
     }
@@ -541,12 +444,9 @@ int f3dg_launch_render(hipStream_t s, int V, int P, int W, int H, float focal_x,
     const bool small_launch = g_f3dg_render_lowocc && waves <= (g_f3dg_render_lowocc > 1 ? 1024ll * g_f3dg_render_lowocc : 2048ll);
     // (2) the split-pixel schedule of f3dg_render5.hip: fast inference launches that ask for it (F3DG_FLAG_SCAN, whatever their size) or,
     // with option render_scan 1, every such launch that is not small
-    if (fast && !save_aux && g_f3dg_render_scan != 0 && (scan || g_f3dg_render_scan == 1)) {
-        if (small_launch)       // one or two views: four lanes per pixel instead of helper-lane batches (render5p_fwd_kernel)
-            return f3dg_launch_render5_small(s, V, P, W, H, focal_x, focal_y, hdr, ranges, point_list, rec, cull, background, bg_per_view, out_color);
-        return f3dg_launch_render5(s, V, P, W, H, focal_x, focal_y, hdr, ranges, point_list, rec, cull, background, bg_per_view, out_color,
-                                   skip_channels, g_f3dg_render_count);
-    }
+    if (fast && !save_aux && g_f3dg_render_scan != 0 && (scan || g_f3dg_render_scan == 1))
+        // small: one or two views, four lanes per pixel instead of helper-lane batches (render5p_fwd_kernel)
+        return small_launch ? f3dg_launch_render5_small(a) : f3dg_launch_render5(a);
     if (small_launch) {
         // the multi-wave kernels of f3dg_render4.hip. Defaults by measurement at 65,536 pixel-ordered Gaussians (profiles/r05_final/
         // one_view.md): fast arithmetic -- producer + consumer waves, two entries per trip (render3p, 76.6 -> 57.9 us; two views 79.7 ->
@@ -555,60 +455,37 @@ int f3dg_launch_render(hipStream_t s, int V, int P, int W, int H, float focal_x,
         const bool one_view = waves <= 1024ll;
         const int split = g_f3dg_render_split >= 1 ? g_f3dg_render_split : fast ? 1 : one_view ? 3 : 1;
         const int unroll = g_f3dg_render_unroll >= 1 ? g_f3dg_render_unroll : fast ? 2 : 1;
-        return f3dg_launch_render_small(s, V, P, W, H, focal_x, focal_y, hdr, ranges, point_list, rec, cull, background, bg_per_view, out_color,
-                                        fast, save_aux, final_T, n_contrib, unroll, split, g_f3dg_render_count);
+        return f3dg_launch_render_small(a, unroll, split);
     }
     // (3) the rank-packed kernel of f3dg_render4.hip (option render_pack: 1 = every launch, -1 = the default: launches in the reference's
     // arithmetic, whose stateless part is 2.5 x as long -- measured -38 % on the real merged set, -6 % at C2; in fast arithmetic the packed
     // trips' hand-over costs what they save: 8.4-8.7 against 8.6 ms). A SAVE_AUX forward in the reference's
     // arithmetic takes it too (its auxiliary planes are bit-identical to render3s's).
     if (g_f3dg_render_pack == 1 || (g_f3dg_render_pack < 0 && !fast))
-        return f3dg_launch_render4(s, V, P, W, H, focal_x, focal_y, hdr, ranges, point_list, rec, cull, background, bg_per_view, out_color,
-                                   fast, skip_channels, g_f3dg_render_count, save_aux, final_T, n_contrib);
+        return f3dg_launch_render4(a);
     // (4) render3s_fwd_kernel: one wave per quadrant, sliding half-windows
-    const RenderArgs a = { s, V, P, W, H, tiles_x, T, focal_x, focal_y, hdr, ranges, point_list, rec, cull, background, bg_per_view, out_color, final_T, n_contrib };
-    // the batched loops of the build that consume RGB, depth and alpha only (cycle aggregation, orbit frames) skip the normal and
-    // distortion accumulators: the channels they do write are bit-identical
-    const bool lean = !save_aux && (skip_channels & (F3DG_FLAG_SKIP_NORMAL | F3DG_FLAG_SKIP_DISTORTION)) == (F3DG_FLAG_SKIP_NORMAL | F3DG_FLAG_SKIP_DISTORTION);
-    const bool count = g_f3dg_render_count && !save_aux;        // (diagnostic: the same kernel with its work counters on)
-    const char* extra = ", OCC=8, WPB=1";
+    const bool lean = a.lean();
+    const bool count = a.count && !save_aux;        // (diagnostic: the same kernel with its work counters on)
+    const char* extra = "";
     if (count) {
         if (fast) launch3s<false, true, true, true, true>(a); else launch3s<false, false, true, true, true>(a);
-        extra = ", OCC=8, WPB=1, COUNT=true";
+        extra = ", COUNT=true";
     } else if (lean) {
         if (fast) launch3s<false, true, false, false, false>(a); else launch3s<false, false, false, false, false>(a);
-        extra = ", OCC=8, WPB=1, NORMAL=false, DIST=false";
+        extra = ", NORMAL=false, DIST=false";
     } else if (save_aux) {
         if (fast) launch3s<true, true, true, true, false>(a); else launch3s<true, false, true, true, false>(a);
     } else {
         if (fast) launch3s<false, true, true, true, false>(a); else launch3s<false, false, true, true, false>(a);
     }
-    note_kernel("render3s_fwd_kernel", lean || count ? 0 : save_aux, fast, extra);
+    f3dg_note_render_kernel("render3s_fwd_kernel<SAVE_AUX=%s, FAST=%s, OCC=8, WPB=1%s>", tf(lean || count ? 0 : save_aux), tf(fast), extra);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }
 
 // debug: the work counters of the counting variant of the one-wave kernel (option render_count = 1), summed over all launches since
 // the last reset: h_out8[16] = { staged, scanned, wave trips, slides, lane-trips, waves, trips with <= 8 / <= 24 live pixels, slides with <= 8 / <= 24, 0... }
-extern "C" int f3dg_debug_render_counts(unsigned long long* h_out8, int reset)
-{
-    unsigned long long rows[64][16];
-    F3DG_HIP_CHECK(hipMemcpyFromSymbol(rows, HIP_SYMBOL(g_f3dg_counts), sizeof rows));
-    if (h_out8)
-        for (int k = 0; k < 16; k++) {
-            h_out8[k] = 0;
-            for (int r = 0; r < 64; r++) h_out8[k] += rows[r][k];
-        }
-    if (reset) {
-        memset(rows, 0, sizeof rows);
-        F3DG_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_f3dg_counts), rows, sizeof rows));
-    }
-    return F3DG_OK;
-}
-
-// the compositing forward kernel the last f3dg_launch_render of this process launched (what `roofline.kernel` of bench.py prints)
-thread_local const char* g_f3dg_last_render_kernel = "";
-extern "C" const char* f3dg_debug_last_render_kernel(void) { return g_f3dg_last_render_kernel; }
+extern "C" int f3dg_debug_render_counts(unsigned long long* h_out8, int reset) { return f3dg_read_render_counts(&g_f3dg_counts, 64, h_out8, reset); }
 
 // debug: the phase-timing counters of earlier builds; no kernel is instrumented any more, so they are zeros
 extern "C" int f3dg_debug_timing(unsigned long long* h_out8, int reset)

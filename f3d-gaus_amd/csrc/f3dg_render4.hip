@@ -32,7 +32,6 @@
 #include <stdio.h>
 #include <string.h>
 
-extern thread_local const char* g_f3dg_last_render_kernel;
 int g_f3dg_render_pack_th = 32;       // option render_pack_th: trips with at most this many participating pixels are packed (0: never)
 
 // work counters (option render_count = 1; f3dg_debug_render_counts rows 16..): [0] staged entries, [1] scanned, [2] fused trips,
@@ -99,13 +98,7 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
             const unsigned j = (unsigned)__builtin_ctzll(pass) ^ xr;
             pass &= pass - 1;
             if (COUNT) n_lane_fused++;
-            const float4 q0 = sR[0][j], q1 = sR[1][j], q2 = sR[2][j], q3 = sR[3][j];
-            const F3dgPair pr = f3dg_pair_eval<FAST, NORMAL, DIST, false>(ray_x, ray_y, q0, q1, q2);
-            // keeps the loads 16 bytes wide (ds_read_b96 takes twice the LDS cycles); placed behind the evaluation so that the
-            // arithmetic on the first chunks starts while the last ones are still on their way
-            asm volatile("" :: "v"(q2.w), "v"(q3.w), "v"(pr.alpha));
-            if (pr.alpha != 0.0f)
-                done = f3dg_pair_apply<FAST, NORMAL, DIST>(st, F3DG_SLOT_FLAG | j, pr, q3.x, q3.y, q3.z);
+            done = f3dg_fused_trip<FAST, NORMAL, DIST>(st, sR, j, F3DG_SLOT_FLAG | j, ray_x, ray_y);
             if (done) pass = 0ull;
             if (COUNT && __builtin_ctzll(__ballot(true)) == (int)lane) n_fused++;
         }
@@ -230,37 +223,9 @@ render4_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
     const unsigned out_x = qx0 + (lane_e & 7u), out_y = qy0 + (lane_e >> 3);
     if (out_x < (unsigned)W && out_y < (unsigned)H) {
         const size_t HW = (size_t)H * W;
-        const size_t pix_id = (size_t)W * out_y + out_x;
-        const float* bg = background + (bg_per_view ? 3 * view : 0);
-        const float Tr = st.Tr;
-        const float distortion = (float)(st.distortion / ((1 - Tr) * (1 - Tr) + 1e-7));
-        if (SAVE_AUX) {
-            float* fT = final_T + (size_t)view * 4 * HW;
-            fT[pix_id] = Tr;
-            fT[pix_id + HW] = st.dist1;
-            fT[pix_id + 2 * HW] = st.dist2;
-            fT[pix_id + 3 * HW] = st.distortion;
-            unsigned* nc = n_contrib + (size_t)view * 2 * HW;
-            nc[pix_id] = st.last_contributor;
-            nc[pix_id + HW] = st.max_contributor;
-        }
-        float* out = out_color + (size_t)view * F3DG_OUT_CHANNELS * HW;
-        out[0 * HW + pix_id] = st.C0 + Tr * bg[0];
-        out[1 * HW + pix_id] = st.C1 + Tr * bg[1];
-        out[2 * HW + pix_id] = st.C2 + Tr * bg[2];
-        if (NORMAL) {
-            out[3 * HW + pix_id] = st.C3;
-            out[4 * HW + pix_id] = st.C4;
-            out[5 * HW + pix_id] = st.C5;
-        }
-        out[6 * HW + pix_id] = st.C6;
-        out[7 * HW + pix_id] = st.C7;
-        if (DIST) out[8 * HW + pix_id] = distortion;
+        f3dg_pixel_store<SAVE_AUX, NORMAL, DIST>(st, view, (size_t)W * out_y + out_x, HW, background, bg_per_view, out_color, final_T, n_contrib);
     }
 }
-
-thread_local char g_kernel_name4[160] = "";
-
 
 #define F3DG_R3U_RING 256
 // ---- SMALL launches, two waves per quadrant: a PRODUCER wave prepares window k + 1 while the CONSUMER wave composites window k ------
@@ -357,33 +322,8 @@ render3p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
         }
     }
 
-    if (inside) {
-        const float* bg = background + (bg_per_view ? 3 * view : 0);
-        const float Tr = st.Tr;
-        const float distortion_before_normalized = st.distortion;
-        const float distortion = (float)(st.distortion / ((1 - Tr) * (1 - Tr) + 1e-7));
-
-        if (SAVE_AUX) {
-            float* fT = final_T + (size_t)view * 4 * HW;
-            fT[pix_id] = Tr;
-            fT[pix_id + HW] = st.dist1;
-            fT[pix_id + 2 * HW] = st.dist2;
-            fT[pix_id + 3 * HW] = distortion_before_normalized;
-            unsigned* nc = n_contrib + (size_t)view * 2 * HW;
-            nc[pix_id] = st.last_contributor;
-            nc[pix_id + HW] = st.max_contributor;
-        }
-        float* out = out_color + (size_t)view * F3DG_OUT_CHANNELS * HW;
-        out[0 * HW + pix_id] = st.C0 + Tr * bg[0];
-        out[1 * HW + pix_id] = st.C1 + Tr * bg[1];
-        out[2 * HW + pix_id] = st.C2 + Tr * bg[2];
-        out[3 * HW + pix_id] = st.C3;
-        out[4 * HW + pix_id] = st.C4;
-        out[5 * HW + pix_id] = st.C5;
-        out[6 * HW + pix_id] = st.C6;
-        out[7 * HW + pix_id] = st.C7;
-        out[8 * HW + pix_id] = distortion;
-    }
+    if (inside)
+        f3dg_pixel_store<SAVE_AUX, true, true>(st, view, pix_id, HW, background, bg_per_view, out_color, final_T, n_contrib);
 }
 
 // ---- SMALL launches, a PIPELINE of waves per quadrant (option render_split = 2 / 3) -------------------------------------------------
@@ -643,96 +583,68 @@ render3q_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
 #undef R3Q_TIMED
 #undef R3Q_REPORT
 
-    if (inside) {
-        const float* bg = background + (bg_per_view ? 3 * view : 0);
-        const float Tr = st.Tr;
-        const float distortion_before_normalized = st.distortion;
-        const float distortion = (float)(st.distortion / ((1 - Tr) * (1 - Tr) + 1e-7));
-
-        if (SAVE_AUX) {
-            float* fT = final_T + (size_t)view * 4 * HW;
-            fT[pix_id] = Tr;
-            fT[pix_id + HW] = st.dist1;
-            fT[pix_id + 2 * HW] = st.dist2;
-            fT[pix_id + 3 * HW] = distortion_before_normalized;
-            unsigned* nc = n_contrib + (size_t)view * 2 * HW;
-            nc[pix_id] = st.last_contributor;
-            nc[pix_id + HW] = st.max_contributor;
-        }
-        float* out = out_color + (size_t)view * F3DG_OUT_CHANNELS * HW;
-        out[0 * HW + pix_id] = st.C0 + Tr * bg[0];
-        out[1 * HW + pix_id] = st.C1 + Tr * bg[1];
-        out[2 * HW + pix_id] = st.C2 + Tr * bg[2];
-        out[3 * HW + pix_id] = st.C3;
-        out[4 * HW + pix_id] = st.C4;
-        out[5 * HW + pix_id] = st.C5;
-        out[6 * HW + pix_id] = st.C6;
-        out[7 * HW + pix_id] = st.C7;
-        out[8 * HW + pix_id] = distortion;
-    }
+    if (inside)
+        f3dg_pixel_store<SAVE_AUX, true, true>(st, view, pix_id, HW, background, bg_per_view, out_color, final_T, n_contrib);
 }
+
+template <bool AUX, bool FAST, int E>
+void launch3q(const F3dgRenderLaunch& a)
+{
+    F3DG_KLAUNCH((render3q_fwd_kernel<AUX, FAST, E>), a.quadrants(), dim3(64 * (E + 2)), 0, a.s, a.V, a.P, a.W, a.H, a.tiles_x, a.T, a.focal_x, a.focal_y,
+                 a.hdr, a.ranges, a.point_list, a.rec, a.cull, a.background, a.bg_per_view, a.out_color, a.final_T, a.n_contrib, a.count);
+}
+
+template <bool AUX, bool FAST, int U>
+void launch3p(const F3dgRenderLaunch& a)
+{
+    F3DG_KLAUNCH((render3p_fwd_kernel<AUX, FAST, U>), a.quadrants(), dim3(128), 0, a.s, a.V, a.P, a.W, a.H, a.tiles_x, a.T, a.focal_x, a.focal_y,
+                 a.hdr, a.ranges, a.point_list, a.rec, a.cull, a.background, a.bg_per_view, a.out_color, a.final_T, a.n_contrib);
+}
+
+template <bool FAST, bool NORMAL, bool DIST, bool COUNT, bool AUX>
+void launch4(const F3dgRenderLaunch& a, int th)
+{
+    F3DG_KLAUNCH((render4_fwd_kernel<FAST, NORMAL, DIST, COUNT, AUX>), a.quadrants(), dim3(64), 0, a.s, a.V, a.P, a.W, a.H, a.tiles_x, a.T, a.focal_x, a.focal_y,
+                 a.hdr, a.ranges, a.point_list, a.rec, a.cull, a.background, a.bg_per_view, a.out_color, th, a.final_T, a.n_contrib);
+}
+
+// the two-valued knob of a small launch (E of render3q, U of render3p) as a template argument
+template <bool AUX, bool FAST>
+void launch_small(const F3dgRenderLaunch& a, bool pipeline, int n)
+{
+    if (pipeline) { if (n == 3) launch3q<AUX, FAST, 3>(a); else launch3q<AUX, FAST, 2>(a); }
+    else { if (n == 2) launch3p<AUX, FAST, 2>(a); else launch3p<AUX, FAST, 1>(a); }
+}
+
+const char* tf(int b) { return b ? "true" : "false"; }
 
 } // namespace
 
-int f3dg_launch_render_small(hipStream_t s, int V, int P, int W, int H, float focal_x, float focal_y, const F3dgHeader* hdr, const uint2* ranges,
-                         const unsigned* point_list, const F3dgRec* rec, const float4* cull, const float* background, int bg_per_view,
-                         float* out_color, int fast, int save_aux, float* final_T, unsigned* n_contrib, int unroll, int split, int count)
+int f3dg_launch_render_small(const F3dgRenderLaunch& a, int unroll, int split)
 {
-    const int tiles_x = (W + F3DG_TILE - 1) / F3DG_TILE, tiles_y = (H + F3DG_TILE - 1) / F3DG_TILE;
-    const int T = tiles_x * tiles_y;
-    const dim3 grid((unsigned)V * (unsigned)T * 4u);
-    if (split >= 2) {       // the pipeline of waves: consumer + E evaluators + producer
-        const int E = split >= 3 ? 3 : 2;
-#define F3DG_LAUNCH3Q(AUX, FST, EE) F3DG_KLAUNCH((render3q_fwd_kernel<AUX, FST, EE>), grid, dim3(64 * (EE + 2)), 0, s, V, P, W, H, tiles_x, T, focal_x, focal_y, hdr, ranges, \
-                                                 point_list, rec, cull, background, bg_per_view, out_color, final_T, n_contrib, count)
-#define F3DG_LAUNCH3Q_E(AUX, FST) do { if (E == 3) F3DG_LAUNCH3Q(AUX, FST, 3); else F3DG_LAUNCH3Q(AUX, FST, 2); } while (0)
-        if (save_aux) { if (fast) F3DG_LAUNCH3Q_E(true, true); else F3DG_LAUNCH3Q_E(true, false); }
-        else { if (fast) F3DG_LAUNCH3Q_E(false, true); else F3DG_LAUNCH3Q_E(false, false); }
-#undef F3DG_LAUNCH3Q_E
-#undef F3DG_LAUNCH3Q
-        snprintf(g_kernel_name4, sizeof g_kernel_name4, "render3q_fwd_kernel<SAVE_AUX=%s, FAST=%s, E=%d>", save_aux ? "true" : "false", fast ? "true" : "false", E);
-        g_f3dg_last_render_kernel = g_kernel_name4;
-        F3DG_HIP_CHECK(hipGetLastError());
-        return F3DG_OK;
-    }
-    if (split) {
-        const int U = unroll >= 2 ? 2 : 1;
-#define F3DG_LAUNCH3P(AUX, FST, UU) F3DG_KLAUNCH((render3p_fwd_kernel<AUX, FST, UU>), grid, dim3(128), 0, s, V, P, W, H, tiles_x, T, focal_x, focal_y, hdr, ranges, \
-                                                 point_list, rec, cull, background, bg_per_view, out_color, final_T, n_contrib)
-#define F3DG_LAUNCH3P_U(AUX, FST) do { if (U == 2) F3DG_LAUNCH3P(AUX, FST, 2); else F3DG_LAUNCH3P(AUX, FST, 1); } while (0)
-        if (save_aux) { if (fast) F3DG_LAUNCH3P_U(true, true); else F3DG_LAUNCH3P_U(true, false); }
-        else { if (fast) F3DG_LAUNCH3P_U(false, true); else F3DG_LAUNCH3P_U(false, false); }
-#undef F3DG_LAUNCH3P_U
-#undef F3DG_LAUNCH3P
-        snprintf(g_kernel_name4, sizeof g_kernel_name4, "render3p_fwd_kernel<SAVE_AUX=%s, FAST=%s, U=%d>", save_aux ? "true" : "false", fast ? "true" : "false", U);
-        g_f3dg_last_render_kernel = g_kernel_name4;
-        F3DG_HIP_CHECK(hipGetLastError());
-        return F3DG_OK;
-    }
-    (void)unroll;
-    return F3DG_ERR_BAD_ARG;      // (split == 0 is render3l_fwd_kernel's: f3dg_launch_render does not come here)
+    if (split < 1)
+        return F3DG_ERR_BAD_ARG;      // (f3dg_launch_render does not come here with split 0)
+    // split >= 2: the pipeline of waves, consumer + E evaluators + producer (render3q); split 1: producer + consumer, U entries per trip (render3p)
+    const bool pipeline = split >= 2;
+    const int n = pipeline ? (split >= 3 ? 3 : 2) : (unroll >= 2 ? 2 : 1);
+    if (a.save_aux) { if (a.fast) launch_small<true, true>(a, pipeline, n); else launch_small<true, false>(a, pipeline, n); }
+    else { if (a.fast) launch_small<false, true>(a, pipeline, n); else launch_small<false, false>(a, pipeline, n); }
+    f3dg_note_render_kernel(pipeline ? "render3q_fwd_kernel<SAVE_AUX=%s, FAST=%s, E=%d>" : "render3p_fwd_kernel<SAVE_AUX=%s, FAST=%s, U=%d>", tf(a.save_aux), tf(a.fast), n);
+    F3DG_HIP_CHECK(hipGetLastError());
+    return F3DG_OK;
 }
 
-int f3dg_launch_render4(hipStream_t s, int V, int P, int W, int H, float focal_x, float focal_y, const F3dgHeader* hdr, const uint2* ranges,
-                        const unsigned* point_list, const F3dgRec* rec, const float4* cull, const float* background, int bg_per_view,
-                        float* out_color, int fast, unsigned skip_channels, int count, int save_aux, float* final_T, unsigned* n_contrib)
+int f3dg_launch_render4(const F3dgRenderLaunch& a)
 {
-    const int tiles_x = (W + F3DG_TILE - 1) / F3DG_TILE, tiles_y = (H + F3DG_TILE - 1) / F3DG_TILE;
-    const int T = tiles_x * tiles_y;
-    const dim3 grid((unsigned)V * (unsigned)T * 4u);
-    const bool lean = !save_aux && (skip_channels & (F3DG_FLAG_SKIP_NORMAL | F3DG_FLAG_SKIP_DISTORTION)) == (F3DG_FLAG_SKIP_NORMAL | F3DG_FLAG_SKIP_DISTORTION);
+    const bool lean = a.lean(), fast = a.fast != 0;
+    const bool count = a.count && !lean && !a.save_aux;
     const int th = g_f3dg_render_pack_th;
-#define F3DG_R4_ARGS s, V, P, W, H, tiles_x, T, focal_x, focal_y, hdr, ranges, point_list, rec, cull, background, bg_per_view, out_color, th, final_T, n_contrib
-#define F3DG_LAUNCH4(FST, NRM, DST, CNT, AUX) F3DG_KLAUNCH((render4_fwd_kernel<FST, NRM, DST, CNT, AUX>), grid, dim3(64), 0, F3DG_R4_ARGS)
-    if (save_aux) { if (fast) F3DG_LAUNCH4(true, true, true, false, true); else F3DG_LAUNCH4(false, true, true, false, true); }
-    else if (count && !lean) { if (fast) F3DG_LAUNCH4(true, true, true, true, false); else F3DG_LAUNCH4(false, true, true, true, false); }
-    else if (lean) { if (fast) F3DG_LAUNCH4(true, false, false, false, false); else F3DG_LAUNCH4(false, false, false, false, false); }
-    else { if (fast) F3DG_LAUNCH4(true, true, true, false, false); else F3DG_LAUNCH4(false, true, true, false, false); }
-#undef F3DG_LAUNCH4
-#undef F3DG_R4_ARGS
-    snprintf(g_kernel_name4, sizeof g_kernel_name4, "render4_fwd_kernel<FAST=%s, NORMAL=%s, DIST=%s%s%s, pack_th=%d>", fast ? "true" : "false",
-             lean ? "false" : "true", lean ? "false" : "true", count && !lean && !save_aux ? ", COUNT=true" : "", save_aux ? ", SAVE_AUX=true" : "", th);
-    g_f3dg_last_render_kernel = g_kernel_name4;
+    if (a.save_aux) { if (fast) launch4<true, true, true, false, true>(a, th); else launch4<false, true, true, false, true>(a, th); }
+    else if (count) { if (fast) launch4<true, true, true, true, false>(a, th); else launch4<false, true, true, true, false>(a, th); }
+    else if (lean) { if (fast) launch4<true, false, false, false, false>(a, th); else launch4<false, false, false, false, false>(a, th); }
+    else { if (fast) launch4<true, true, true, false, false>(a, th); else launch4<false, true, true, false, false>(a, th); }
+    f3dg_note_render_kernel("render4_fwd_kernel<FAST=%s, NORMAL=%s, DIST=%s%s%s, pack_th=%d>", tf(fast), tf(!lean), tf(!lean),
+                            count ? ", COUNT=true" : "", a.save_aux ? ", SAVE_AUX=true" : "", th);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }
@@ -740,21 +652,7 @@ int f3dg_launch_render4(hipStream_t s, int V, int P, int W, int H, float focal_x
 // debug: the work counters of render4's counting variant (option render_count = 1), summed over all launches since the last reset:
 // h_out[16] = { staged, scanned, fused trips, slides, lane-trips of fused trips, waves, packed batches, blend trips, pairs evaluated in
 // dense trips, pairs that reached a blend trip, 0... }
-extern "C" int f3dg_debug_render4_counts(unsigned long long* h_out, int reset)
-{
-    static unsigned long long rows[64][16];
-    F3DG_HIP_CHECK(hipMemcpyFromSymbol(rows, HIP_SYMBOL(g_f3dg_counts4), sizeof rows));
-    if (h_out)
-        for (int k = 0; k < 16; k++) {
-            h_out[k] = 0;
-            for (int r = 0; r < 32; r++) h_out[k] += rows[r][k];      // (rows 32..: render3q's role clocks)
-        }
-    if (reset) {
-        memset(rows, 0, sizeof rows);
-        F3DG_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_f3dg_counts4), rows, sizeof rows));
-    }
-    return F3DG_OK;
-}
+extern "C" int f3dg_debug_render4_counts(unsigned long long* h_out, int reset) { return f3dg_read_render_counts(&g_f3dg_counts4, 32, h_out, reset); }    // (rows 32..: render3q's role clocks)
 
 // debug: the role clocks of render3q_fwd_kernel (option render_count = 1), summed over the launches since the last reset of
 // f3dg_debug_render4_counts: h_out[4][16] = rows { consumer, evaluators, producer } x { shader clocks in total, at the window barrier,

@@ -39,7 +39,6 @@
 #include <stdio.h>
 #include <string.h>
 
-extern thread_local const char* g_f3dg_last_render_kernel;
 int g_f3dg_render_scan = -1;          // option render_scan: -1 (default) = calls that ask for it (F3DG_FLAG_SCAN); 1 = every fast inference launch of the general path; 0 = never
 int g_f3dg_render_scan_min = 4;       // option render_scan_min: stragglers that hold fewer than this many older-half entries each finish the slide in fused trips (0: always compact)
 int g_f3dg_render_scan_th = 12;       // option render_scan_th: fused trips while more than this many pixels take part (64: every trip is compacted)
@@ -90,11 +89,7 @@ render5_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
             const unsigned j = (unsigned)__builtin_ctzll(pass) ^ xr;
             pass &= pass - 1;
             if (COUNT) n_lane_fused++;
-            const float4 q0 = sR[0][j], q1 = sR[1][j], q2 = sR[2][j], q3 = sR[3][j];
-            const F3dgPair pr = f3dg_pair_eval<true, NORMAL, DIST, false>(ray_x, ray_y, q0, q1, q2);
-            asm volatile("" :: "v"(q2.w), "v"(q3.w), "v"(pr.alpha));
-            if (pr.alpha != 0.0f)
-                done = f3dg_pair_apply<true, NORMAL, DIST>(st, 0u, pr, q3.x, q3.y, q3.z);
+            done = f3dg_fused_trip<true, NORMAL, DIST>(st, sR, j, 0u, ray_x, ray_y);
             if (done) pass = 0ull;
             if (COUNT && __builtin_ctzll(__ballot(true)) == (int)lane) n_fused++;
         }
@@ -114,11 +109,7 @@ render5_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                     const unsigned j = (unsigned)__builtin_ctzll(pass) ^ xr;
                     pass &= pass - 1;
                     if (COUNT) n_lane_fused++;
-                    const float4 q0 = sR[0][j], q1 = sR[1][j], q2 = sR[2][j], q3 = sR[3][j];
-                    const F3dgPair pr = f3dg_pair_eval<true, NORMAL, DIST, false>(ray_x, ray_y, q0, q1, q2);
-                    asm volatile("" :: "v"(q2.w), "v"(q3.w), "v"(pr.alpha));
-                    if (pr.alpha != 0.0f)
-                        done = f3dg_pair_apply<true, NORMAL, DIST>(st, 0u, pr, q3.x, q3.y, q3.z);
+                    done = f3dg_fused_trip<true, NORMAL, DIST>(st, sR, j, 0u, ray_x, ray_y);
                     if (done) pass = 0ull;
                     if (COUNT && __builtin_ctzll(__ballot(true)) == (int)lane) n_fused++;
                 }
@@ -285,22 +276,7 @@ render5_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
     const unsigned out_x = qx0 + (lane_e & 7u), out_y = qy0 + (lane_e >> 3);
     if (out_x < (unsigned)W && out_y < (unsigned)H) {
         const size_t HW = (size_t)H * W;
-        const size_t pix_id = (size_t)W * out_y + out_x;
-        const float* bg = background + (bg_per_view ? 3 * view : 0);
-        const float Tr = st.Tr;
-        const float distortion = (float)(st.distortion / ((1 - Tr) * (1 - Tr) + 1e-7));
-        float* out = out_color + (size_t)view * F3DG_OUT_CHANNELS * HW;
-        out[0 * HW + pix_id] = st.C0 + Tr * bg[0];
-        out[1 * HW + pix_id] = st.C1 + Tr * bg[1];
-        out[2 * HW + pix_id] = st.C2 + Tr * bg[2];
-        if (NORMAL) {
-            out[3 * HW + pix_id] = st.C3;
-            out[4 * HW + pix_id] = st.C4;
-            out[5 * HW + pix_id] = st.C5;
-        }
-        out[6 * HW + pix_id] = st.C6;
-        out[7 * HW + pix_id] = st.C7;
-        if (DIST) out[8 * HW + pix_id] = distortion;
+        f3dg_pixel_store<false, NORMAL, DIST>(st, view, (size_t)W * out_y + out_x, HW, background, bg_per_view, out_color, nullptr, nullptr);
     }
 }
 
@@ -435,58 +411,41 @@ render5p_fwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_
         if (r > med_rank) { med_rank = r; med_t = tt; }
     }
     if (inside && sub == 0u) {
-        const size_t HW = (size_t)H * W;
-        const size_t pix_id = (size_t)W * pix_y + pix_x;
-        const float* bg = background + (bg_per_view ? 3 * view : 0);
-        const float distortion = (float)(Cd / ((1 - Tf) * (1 - Tf) + 1e-7));
-        float* out = out_color + (size_t)view * F3DG_OUT_CHANNELS * HW;
-        out[0 * HW + pix_id] = C0 + Tf * bg[0];
-        out[1 * HW + pix_id] = C1 + Tf * bg[1];
-        out[2 * HW + pix_id] = C2 + Tf * bg[2];
-        out[3 * HW + pix_id] = C3;
-        out[4 * HW + pix_id] = C4;
-        out[5 * HW + pix_id] = C5;
-        out[6 * HW + pix_id] = med_t;
-        out[7 * HW + pix_id] = C7;
-        out[8 * HW + pix_id] = distortion;
+        F3dgPixel st;               // the pixel's reduced sums in the shape the shared write-out takes
+        f3dg_pixel_init(st);
+        st.Tr = Tf;
+        st.C0 = C0; st.C1 = C1; st.C2 = C2; st.C3 = C3; st.C4 = C4; st.C5 = C5; st.C6 = med_t; st.C7 = C7;
+        st.distortion = Cd;
+        f3dg_pixel_store<false, true, true>(st, view, pix_id, (size_t)H * W, background, bg_per_view, out_color, nullptr, nullptr);
     }
 }
 
-thread_local char g_kernel_name5[160] = "";
+template <bool NORMAL, bool DIST, bool COUNT>
+void launch5(const F3dgRenderLaunch& a, int th)
+{
+    F3DG_KLAUNCH((render5_fwd_kernel<NORMAL, DIST, COUNT>), a.quadrants(), dim3(64), 0, a.s, a.V, a.P, a.W, a.H, a.tiles_x, a.T, a.focal_x, a.focal_y,
+                 a.hdr, a.ranges, a.point_list, a.rec, a.cull, a.background, a.bg_per_view, a.out_color, th, g_f3dg_render_scan_min);
+}
 
 } // namespace
 
-int f3dg_launch_render5(hipStream_t s, int V, int P, int W, int H, float focal_x, float focal_y, const F3dgHeader* hdr, const uint2* ranges,
-                        const unsigned* point_list, const F3dgRec* rec, const float4* cull, const float* background, int bg_per_view,
-                        float* out_color, unsigned skip_channels, int count)
+int f3dg_launch_render5(const F3dgRenderLaunch& a)
 {
-    const int tiles_x = (W + F3DG_TILE - 1) / F3DG_TILE, tiles_y = (H + F3DG_TILE - 1) / F3DG_TILE;
-    const int T = tiles_x * tiles_y;
-    const dim3 grid((unsigned)V * (unsigned)T * 4u);
-    const bool lean = (skip_channels & (F3DG_FLAG_SKIP_NORMAL | F3DG_FLAG_SKIP_DISTORTION)) == (F3DG_FLAG_SKIP_NORMAL | F3DG_FLAG_SKIP_DISTORTION);
+    const bool lean = a.lean();
     const int th = g_f3dg_render_scan_th;
-#define F3DG_LAUNCH5(NRM, DST, CNT) F3DG_KLAUNCH((render5_fwd_kernel<NRM, DST, CNT>), grid, dim3(64), 0, s, V, P, W, H, tiles_x, T, focal_x, focal_y, hdr, ranges, \
-                                                 point_list, rec, cull, background, bg_per_view, out_color, th, g_f3dg_render_scan_min)
-    if (lean) { if (count) F3DG_LAUNCH5(false, false, true); else F3DG_LAUNCH5(false, false, false); }
-    else { if (count) F3DG_LAUNCH5(true, true, true); else F3DG_LAUNCH5(true, true, false); }
-#undef F3DG_LAUNCH5
-    snprintf(g_kernel_name5, sizeof g_kernel_name5, "render5_fwd_kernel<NORMAL=%s, DIST=%s%s, scan_th=%d>", lean ? "false" : "true", lean ? "false" : "true",
-             count ? ", COUNT=true" : "", th);
-    g_f3dg_last_render_kernel = g_kernel_name5;
+    if (lean) { if (a.count) launch5<false, false, true>(a, th); else launch5<false, false, false>(a, th); }
+    else { if (a.count) launch5<true, true, true>(a, th); else launch5<true, true, false>(a, th); }
+    f3dg_note_render_kernel("render5_fwd_kernel<NORMAL=%s, DIST=%s%s, scan_th=%d>", lean ? "false" : "true", lean ? "false" : "true",
+                            a.count ? ", COUNT=true" : "", th);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }
 
-// one- and two-view launches with F3DG_FLAG_SCAN: four lanes per pixel (render5p_fwd_kernel)
-int f3dg_launch_render5_small(hipStream_t s, int V, int P, int W, int H, float focal_x, float focal_y, const F3dgHeader* hdr, const uint2* ranges,
-                              const unsigned* point_list, const F3dgRec* rec, const float4* cull, const float* background, int bg_per_view,
-                              float* out_color)
+int f3dg_launch_render5_small(const F3dgRenderLaunch& a)
 {
-    const int tiles_x = (W + F3DG_TILE - 1) / F3DG_TILE, tiles_y = (H + F3DG_TILE - 1) / F3DG_TILE;
-    const int T = tiles_x * tiles_y;
-    F3DG_KLAUNCH(render5p_fwd_kernel, dim3((unsigned)V * (unsigned)T * 4u), dim3(320), 0, s, V, P, W, H, tiles_x, T, focal_x, focal_y, hdr, ranges,
-                 point_list, rec, cull, background, bg_per_view, out_color);
-    g_f3dg_last_render_kernel = "render5p_fwd_kernel<4 lanes per pixel>";
+    F3DG_KLAUNCH(render5p_fwd_kernel, a.quadrants(), dim3(320), 0, a.s, a.V, a.P, a.W, a.H, a.tiles_x, a.T, a.focal_x, a.focal_y, a.hdr, a.ranges,
+                 a.point_list, a.rec, a.cull, a.background, a.bg_per_view, a.out_color);
+    f3dg_note_render_kernel("render5p_fwd_kernel<4 lanes per pixel>");
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }
@@ -494,18 +453,4 @@ int f3dg_launch_render5_small(hipStream_t s, int V, int P, int W, int H, float f
 // debug: the work counters of render5's counting variant (option render_count = 1), summed over all launches since the last reset:
 // h_out[16] = { staged, scanned, fused trips, slides, lane-trips of fused trips, waves, dense batches, pairs in dense batches, pixels
 // compacted, slides with a compaction, 0... }
-extern "C" int f3dg_debug_render5_counts(unsigned long long* h_out, int reset)
-{
-    static unsigned long long rows[64][16];
-    F3DG_HIP_CHECK(hipMemcpyFromSymbol(rows, HIP_SYMBOL(g_f3dg_counts5), sizeof rows));
-    if (h_out)
-        for (int k = 0; k < 16; k++) {
-            h_out[k] = 0;
-            for (int r = 0; r < 64; r++) h_out[k] += rows[r][k];
-        }
-    if (reset) {
-        memset(rows, 0, sizeof rows);
-        F3DG_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_f3dg_counts5), rows, sizeof rows));
-    }
-    return F3DG_OK;
-}
+extern "C" int f3dg_debug_render5_counts(unsigned long long* h_out, int reset) { return f3dg_read_render_counts(&g_f3dg_counts5, 64, h_out, reset); }
