@@ -8,78 +8,28 @@
 // The reference's computeCov2DCUDA / computeCov3D backward are commented out there (:992-1007, :627-630), so
 // dL_dconic and dL_dcov3D are identically zero; they are left untouched here as well.
 //
-// MI355X shape. The reference issues 17 float atomicAdds per contributing (pixel, Gaussian) pair. Here all 64
-// lanes of a wave walk the tile list in lock-step, so the 17 partial derivatives of one Gaussian are first
-// summed across the wave with cross-lane butterflies and only lane 0 touches memory: <= 17 atomics per
-// (wave, Gaussian) instead of per (pixel, Gaussian), and nothing at all for the (wave, Gaussian) pairs no lane of
-// the strip contributes to (a ballot). The 10 dL/dview2gaussian entries are accumulated in float64
-// (global_atomic_add_f64): the per-Gaussian stage below amplifies a 5e-7 ordering perturbation of them into tens
-// of percent on dL/dscale (SURVEY 0.9 -- the reference's own run-to-run spread), so float64 sums make the result
-// reproducible to rounding where the reference is not.
+// MI355X shape of render3_bwd_kernel (option bwd_dense 0; the default is render5_bwd_kernel). The reference issues 17 float atomicAdds per
+// contributing (pixel, Gaussian) pair. Here all 64 lanes of a wave walk the tile list in lock-step, so the 17 partial derivatives of one
+// Gaussian (f3dg_bwd_pair.h) are first summed across the wave in float32: permlane swaps pair the values two by two (pair32, pair16) until
+// every 16-lane row holds the partial sums of different values, four DPP steps finish a row (row_total), and the four row-end lanes add
+// neighbouring elements to memory -- five atomic instructions per (wave, Gaussian) instead of 17 per (pixel, Gaussian), and nothing at
+// all for the (wave, Gaussian) pairs no lane contributes to (a ballot). Only the accumulation of the 10 dL/dview2gaussian entries is
+// float64 (global_atomic_add_f64): the per-Gaussian stage below amplifies a 5e-7 ordering perturbation of them into tens of percent on
+// dL/dscale (SURVEY 0.9 -- the reference's own run-to-run spread), so float64 sums keep the order of the waves out of the result.
 #include "f3dg_common.h"
 #include "f3dg_ellipse.h"
 #include "f3dg_quad.h"
+#include "f3dg_bwd_pair.h"
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-// float64 butterfly: the 64 per-pixel float terms are summed exactly (to double rounding), so the only float32
-// rounding left in dL/dview2gaussian is the final narrowing -- see the header comment on why that matters
-__device__ __forceinline__ double wave_sum_f64(float v)
-{
-    double d = (double)v;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) d += __shfl_xor(d, m, 64);
-    return d;
-}
-
-
-// Wave64 sums on the VALU with DPP (no LDS traffic): inclusive row scans (row_shr 1, 2, 4, 8 with zero fill), then the
-// row totals are folded across the four rows (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3). The total
-// ends up in lane 63. The backward kernel is LDS-pipe-bound with ds_bpermute butterflies or LDS atomics (measured:
-// SQ_ACTIVE_INST_LDS ~ the kernel time), while its VALU is mostly idle.
+// Row-local sums on the VALU with DPP (no LDS traffic): inclusive row scans (row_shr 1, 2, 4, 8 with zero fill)
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_f32(float v)
 {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xF, true));
 }
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xFFFFFFFFll), CTRL, ROW_MASK, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xF, true);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
 #define F3DG_DPP_ROW_SHR(n) (0x110 + (n))
-#define F3DG_DPP_ROW_BCAST15 0x142
-#define F3DG_DPP_ROW_BCAST31 0x143
-__device__ __forceinline__ float wave_total_lane63(float v)
-{
-    v += dpp_f32<F3DG_DPP_ROW_SHR(1), 0xF>(v);
-    v += dpp_f32<F3DG_DPP_ROW_SHR(2), 0xF>(v);
-    v += dpp_f32<F3DG_DPP_ROW_SHR(4), 0xF>(v);
-    v += dpp_f32<F3DG_DPP_ROW_SHR(8), 0xF>(v);
-    v += dpp_f32<F3DG_DPP_ROW_BCAST15, 0xA>(v);
-    v += dpp_f32<F3DG_DPP_ROW_BCAST31, 0xC>(v);
-    return v;
-}
-__device__ __forceinline__ double wave_total_lane63_f64(float f)
-{
-    double v = (double)f;
-    v += dpp_f64<F3DG_DPP_ROW_SHR(1), 0xF>(v);
-    v += dpp_f64<F3DG_DPP_ROW_SHR(2), 0xF>(v);
-    v += dpp_f64<F3DG_DPP_ROW_SHR(4), 0xF>(v);
-    v += dpp_f64<F3DG_DPP_ROW_SHR(8), 0xF>(v);
-    v += dpp_f64<F3DG_DPP_ROW_BCAST15, 0xA>(v);
-    v += dpp_f64<F3DG_DPP_ROW_BCAST31, 0xC>(v);
-    return v;
-}
 
 // ---- transposed wave reduction of several values at once -------------------------------------------------------------
 // v_permlane32_swap / v_permlane16_swap (gfx950) exchange half-waves / 16-lane rows between two registers, so ONE add
@@ -98,22 +48,6 @@ __device__ __forceinline__ float pair16(float x, float y)
     const f3dg_u2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
     return __uint_as_float(r.x) + __uint_as_float(r.y);
 }
-__device__ __forceinline__ double pair32(double x, double y)
-{
-    const unsigned long long a = (unsigned long long)__double_as_longlong(x), b = (unsigned long long)__double_as_longlong(y);
-    const f3dg_u2 lo = __builtin_amdgcn_permlane32_swap((unsigned)a, (unsigned)b, false, false);
-    const f3dg_u2 hi = __builtin_amdgcn_permlane32_swap((unsigned)(a >> 32), (unsigned)(b >> 32), false, false);
-    return __longlong_as_double((long long)(((unsigned long long)hi.x << 32) | lo.x)) +
-           __longlong_as_double((long long)(((unsigned long long)hi.y << 32) | lo.y));
-}
-__device__ __forceinline__ double pair16(double x, double y)
-{
-    const unsigned long long a = (unsigned long long)__double_as_longlong(x), b = (unsigned long long)__double_as_longlong(y);
-    const f3dg_u2 lo = __builtin_amdgcn_permlane16_swap((unsigned)a, (unsigned)b, false, false);
-    const f3dg_u2 hi = __builtin_amdgcn_permlane16_swap((unsigned)(a >> 32), (unsigned)(b >> 32), false, false);
-    return __longlong_as_double((long long)(((unsigned long long)hi.x << 32) | lo.x)) +
-           __longlong_as_double((long long)(((unsigned long long)hi.y << 32) | lo.y));
-}
 // total of each 16-lane row in its lane 15
 __device__ __forceinline__ float row_total(float v)
 {
@@ -123,16 +57,8 @@ __device__ __forceinline__ float row_total(float v)
     v += dpp_f32<F3DG_DPP_ROW_SHR(8), 0xF>(v);
     return v;
 }
-__device__ __forceinline__ double row_total(double v)
-{
-    v += dpp_f64<F3DG_DPP_ROW_SHR(1), 0xF>(v);
-    v += dpp_f64<F3DG_DPP_ROW_SHR(2), 0xF>(v);
-    v += dpp_f64<F3DG_DPP_ROW_SHR(4), 0xF>(v);
-    v += dpp_f64<F3DG_DPP_ROW_SHR(8), 0xF>(v);
-    return v;
-}
 
-// ---- render3's counterpart: ONE wave64 per 8x8 quadrant, no workgroup barriers (the default) ------------------------------------
+// ---- render3's counterpart: ONE wave64 per 8x8 quadrant, no workgroup barriers ------------------------------------------------------
 // The reference's arithmetic per contributing (pixel, Gaussian) pair, followed by a transposed wave reduction. Around it, as in the
 // forward (f3dg_render.hip, render3s_fwd_kernel):
 //   * a workgroup is one wave that owns a quadrant from its deepest last contributor back to the first list entry; nothing is
@@ -143,32 +69,25 @@ __device__ __forceinline__ double row_total(double v)
 //     render5_bwd_kernel);
 //   * the surviving entries are walked in lock-step, back to front, because the 17 partials of a Gaussian are reduced across the
 //     wave before they touch memory.
+// Of a pair's arithmetic the kernel keeps what makes it the independent cross-check of render5_bwd_kernel: backward.cu's six per-pixel
+// recurrences in registers, T rebuilt by the reference's division, its rounding of the background term. The rest is f3dg_bwd_pair.h.
 template <int OCC>
 __global__ void __launch_bounds__(64, OCC)
-render3_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x, float focal_y,
-                   F3dgHeader* __restrict__ hdr, const uint2* __restrict__ ranges,
-                   const unsigned* __restrict__ point_list_general, const unsigned* __restrict__ small_list, const F3dgRec* __restrict__ rec,
-                   const float4* __restrict__ cull,
-                   const float2* __restrict__ means2D, const float4* __restrict__ conic,
-                   const float* __restrict__ background, int bg_per_view,
-                   const float* __restrict__ final_T, const unsigned* __restrict__ n_contrib,
-                   const float* __restrict__ dL_dpixels,
-                   float* __restrict__ dL_dmean2D, float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolors,
-                   double* __restrict__ dL_dv2g_acc)
+render3_bwd_kernel(const F3dgBwdLaunch::Args a, float* __restrict__ dL_dmean2D, float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolors)
 {
-    const F3dgQuad qd = f3dg_quad(V, T, tiles_x);
+    const F3dgQuad qd = f3dg_quad(a.V, a.T, a.tiles_x);
     const unsigned lane = threadIdx.x;
-    const auto [pix_x, pix_y, inside, pix_id, ray_x, ray_y] = f3dg_quad_pixel(qd, lane, W, H, focal_x, focal_y);
+    const auto [pix_x, pix_y, inside, pix_id, ray_x, ray_y] = f3dg_quad_pixel(qd, lane, a.W, a.H, a.focal_x, a.focal_y);
 
     __shared__ float4 sR[4][64];          // records of the window, [16-byte chunk][entry] (global_load_lds image)
     __shared__ float4 sC[64];             // 2D conic + opacity * coef
     __shared__ float2 sX[64];             // projected centre
     __shared__ uint2 sQ[F3DG_QUAD_RING];  // (list position, Gaussian id) of the kept entries, ring
 
-    F3dgBwdWindow<false> w(sR, sC, sX, nullptr, sQ, qd, inside, pix_id, lane, P, T, W, H, hdr, ranges, point_list_general, small_list, rec, cull,
-                           means2D, conic, background, bg_per_view, final_T, n_contrib, dL_dpixels);
+    F3dgBwdWindow<false> w(a, sR, sC, sX, nullptr, sQ, qd, inside, pix_id, lane);
     const size_t vP = w.vP;
-    const float pixf_x = (float)pix_x + 0.5f, pixf_y = (float)pix_y + 0.5f;
+    const F3dgBwdPixel px = { ray_x, ray_y, (float)pix_x, (float)pix_y, { w.dpx0, w.dpx1, w.dpx2 }, { w.dn0, w.dn1, w.dn2 },
+                              w.dL_dmax_depth, w.dL_dreg, w.final_A, w.final_D, w.max_contributor };
     float Tr = w.T_final;
     float accum_rec0 = 0, accum_rec1 = 0, accum_rec2 = 0;
     float last_alpha = 0;
@@ -183,7 +102,7 @@ render3_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
     char* const add0 = row < 3 ? reinterpret_cast<char*>(dL_dcolors + vP * 3 + row) : reinterpret_cast<char*>(dL_dmean2D + vP * 3);   // stride 12
     char* const add1 = row < 2 ? reinterpret_cast<char*>(dL_dmean2D + vP * 3 + 1 + row) : reinterpret_cast<char*>(dL_dopacity);
     const unsigned stride1 = row < 2 ? 12u : 4u;
-    char* const addD = reinterpret_cast<char*>(dL_dv2g_acc + vP * 10 + row);                                                           // stride 80
+    char* const addD = reinterpret_cast<char*>(a.dL_dv2g_acc + vP * 10 + row);                                                         // stride 80
 
     while (w.next()) {
         // ---- lock-step walk over the entries that reach at least one pixel, back to front (window slot order)
@@ -193,62 +112,28 @@ render3_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
             todo &= todo - 1ull;
             const uint2 pe = w.entry((unsigned)j);
             const int contributor = (int)pe.x;                             // 0-based position from the front
-            bool active = inside && ((w.pass >> j) & 1ull) != 0ull && contributor < w.last_contributor;
-            if (__ballot(active) == 0)
+            const bool reached = inside && ((w.pass >> j) & 1ull) != 0ull && contributor < w.last_contributor;
+            if (__ballot(reached) == 0)
                 continue;
 
-            const float4 q0 = sR[0][j], q1 = sR[1][j], q2 = sR[2][j];
-            const float n0 = q0.x * ray_x + q0.y * ray_y + q0.z;
-            const float n1 = q0.y * ray_x + q0.w * ray_y + q1.x;
-            const float n2 = q0.z * ray_x + q1.x * ray_y + q1.y;
-            const float aaf = ray_x * n0 + ray_y * n1 + n2;
-            const float bhalf = q1.z * ray_x + q1.w * ray_y + q2.x;
-
-            const float CC = q2.y;
-            float t = 0, G = 0, alpha = 0;
-            if (active) {
-                if (w.alpha_fast) {
-                    // the forward of this workspace took the fast arithmetic: the same function, to the bit
-                    f3dg_fast_t_G(aaf, bhalf, CC, t, G);
-                    if (t < 0.2f) active = false;
-                    alpha = fminf(0.99f, q2.z * G);
-                } else {
-                    const double AA = aaf;
-                    const double BB = 2 * bhalf;
-                    const double q = BB / AA;                          // one division: -BB / (2 * AA) == -0.5 * (BB / AA) exactly
-                    t = (float)(-0.5 * q);
-                    if (t <= F3DG_NEAR_PLANE) active = false;
-                    const double min_value = -q * (BB / 4.) + CC;
-                    float power = (float)(-0.5f * min_value);
-                    if (power > 0.0f) power = 0.0f;
-                    G = expf(power);
-                    alpha = fminf(0.99f, q2.z * G);
-                }
-                if (alpha < 1.0f / 255.0f) active = false;
-            }
+            const F3dgBwdPair pr = f3dg_bwd_pair_eval(sR[0][j], sR[1][j], sR[2][j], ray_x, ray_y, w.alpha_fast, reached);
             {
-                const unsigned long long act = __ballot(active);
+                const unsigned long long act = __ballot(pr.live);
                 if (act == 0)
                     continue;
                 n_pairs += (unsigned)__popcll(act);
             }
 
-            float g_col0 = 0, g_col1 = 0, g_col2 = 0, g_mx = 0, g_my = 0, g_mz = 0, g_op = 0;
-            float g_v0 = 0, g_v1 = 0, g_v2 = 0, g_v3 = 0, g_v4 = 0, g_v5 = 0, g_v6 = 0, g_v7 = 0, g_v8 = 0, g_v9 = 0;
-            if (active) {
+            float g[17];
+#pragma unroll
+            for (int c = 0; c < 17; c++) g[c] = 0.0f;
+            if (pr.live) {
                 // gradient terms only from here: float32 with one reciprocal each, FMA contraction allowed
 #pragma clang fp contract(fast)
                 const float4 q3 = sR[3][j];
-                const float4 con = sC[j];
-                const float2 xy = sX[j];
-                const float d_x = (float)(xy.x - (pixf_x - 0.5)), d_y = (float)(xy.y - (pixf_y - 0.5));
-
-                // (hardware reciprocals / reciprocal square root, <= 1 ulp: these feed float32 gradient sums only)
-                const float inv_t = __builtin_amdgcn_rcpf(t);
-                const float mapped_max_t = fmaf(-0.20040080160320642f, inv_t, 1.0020040080160322f);
-                const float dmax_t_dd = 0.20040080160320642f * inv_t * inv_t;
-                const float inv_len = __builtin_amdgcn_rsqf(n0 * n0 + n1 * n1 + n2 * n2 + 1e-7f);
-                const float nn0 = -n0 * inv_len, nn1 = -n1 * inv_len, nn2 = -n2 * inv_len;
+                const float alpha = pr.alpha;
+                float nn0, nn1, nn2;
+                f3dg_bwd_pair_normal(pr, nn0, nn1, nn2);
 
                 // T is rebuilt by the reference's own IEEE division (backward.cu:803): a reciprocal + Newton step (<= 1 ulp per layer)
                 // keeps the compositing-stage gradients within 1e-5, but the per-Gaussian stage amplifies even that on ill-conditioned
@@ -256,90 +141,37 @@ render3_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                 const float oma = 1.f - alpha;
                 Tr = Tr / oma;
                 const float inv_oma = __builtin_amdgcn_rcpf(oma);      // background term only
-                const float dchannel_dcolor = alpha * Tr;
 
+                // backward.cu's recurrences: the colour / normal blended behind the entry, channel by channel
                 float dL_dalpha = 0.0f;
                 const float c0 = q3.x, c1 = q3.y, c2 = q3.z;
                 accum_rec0 = last_alpha * last_c0 + (1.f - last_alpha) * accum_rec0; last_c0 = c0;
-                dL_dalpha += (c0 - accum_rec0) * w.dpx0;
-                g_col0 = dchannel_dcolor * w.dpx0;
+                dL_dalpha += (c0 - accum_rec0) * px.dpx[0];
                 accum_rec1 = last_alpha * last_c1 + (1.f - last_alpha) * accum_rec1; last_c1 = c1;
-                dL_dalpha += (c1 - accum_rec1) * w.dpx1;
-                g_col1 = dchannel_dcolor * w.dpx1;
+                dL_dalpha += (c1 - accum_rec1) * px.dpx[1];
                 accum_rec2 = last_alpha * last_c2 + (1.f - last_alpha) * accum_rec2; last_c2 = c2;
-                dL_dalpha += (c2 - accum_rec2) * w.dpx2;
-                g_col2 = dchannel_dcolor * w.dpx2;
-
-                float dL_dmax_t = 0.0f;
-                dL_dmax_t += 2.0f * (Tr * alpha) * (mapped_max_t * w.final_A - w.final_D) * w.dL_dreg * dmax_t_dd;
-                dL_dalpha += 0.f - 0.f;
-
+                dL_dalpha += (c2 - accum_rec2) * px.dpx[2];
                 acc_n0 = last_alpha * last_n0 + (1.f - last_alpha) * acc_n0; last_n0 = nn0;
-                dL_dalpha += (nn0 - acc_n0) * w.dn0;
-                const float dnn0 = alpha * Tr * w.dn0;
+                dL_dalpha += (nn0 - acc_n0) * px.dn[0];
                 acc_n1 = last_alpha * last_n1 + (1.f - last_alpha) * acc_n1; last_n1 = nn1;
-                dL_dalpha += (nn1 - acc_n1) * w.dn1;
-                const float dnn1 = alpha * Tr * w.dn1;
+                dL_dalpha += (nn1 - acc_n1) * px.dn[1];
                 acc_n2 = last_alpha * last_n2 + (1.f - last_alpha) * acc_n2; last_n2 = nn2;
-                dL_dalpha += (nn2 - acc_n2) * w.dn2;
-                const float dnn2 = alpha * Tr * w.dn2;
-
-                float dL_dlength = (dnn0 * n0 + dnn1 * n1 + dnn2 * n2);
-                dL_dlength *= inv_len * inv_len;
-                float dLn0 = (-dnn0 + dL_dlength * n0) * inv_len;
-                float dLn1 = (-dnn1 + dL_dlength * n1) * inv_len;
-                float dLn2 = (-dnn2 + dL_dlength * n2) * inv_len;
-
-                float dL_dt = dL_dmax_t;
-                if (contributor == w.max_contributor - 1)
-                    dL_dt += w.dL_dmax_depth;
-
+                dL_dalpha += (nn2 - acc_n2) * px.dn[2];
                 dL_dalpha *= Tr;
                 last_alpha = alpha;
                 dL_dalpha += (-w.T_final * inv_oma) * w.bg_dot_dpixel;
 
-                const float dL_dG = con.w * dL_dalpha;
-                const float gdx = G * d_x;
-                const float gdy = G * d_y;
-                const float dG_ddelx = -gdx * con.x - gdy * con.y;
-                const float dG_ddely = -gdy * con.z - gdx * con.y;
-                g_mx = dL_dG * dG_ddelx * w.ddelx_dx;
-                g_my = dL_dG * dG_ddely * w.ddely_dy;
-                g_mz = fabsf(dL_dG * dG_ddelx * w.ddelx_dx) + fabsf(dL_dG * dG_ddely * w.ddely_dy);
-                g_op = G * dL_dalpha;
-
-                const float dL_dpower = dL_dG * G;
-                const float dL_dmin_value = dL_dpower * -0.5f;
-                const float qf = -2.0f * t, inv_a = __builtin_amdgcn_rcpf(aaf);
-                float dL_dA = dL_dmin_value * qf * qf * 0.25f;
-                float dL_dB = dL_dmin_value * (-0.5f * qf);
-                const float dL_dC = dL_dmin_value;
-                dL_dA += dL_dt * (0.5f * qf * inv_a);
-                dL_dB += dL_dt * (-0.5f * inv_a);
-                dLn0 += dL_dA * ray_x;
-                dLn1 += dL_dA * ray_y;
-                dLn2 += dL_dA;
-
-                g_v0 = dLn0 * ray_x;
-                g_v1 = dLn0 * ray_y + dLn1 * ray_x;
-                g_v2 = dLn0 + dLn2 * ray_x;
-                g_v3 = dLn1 * ray_y;
-                g_v4 = dLn1 + dLn2 * ray_y;
-                g_v5 = dLn2;
-                g_v6 = dL_dB * 2 * ray_x;
-                g_v7 = dL_dB * 2 * ray_y;
-                g_v8 = dL_dB * 2;
-                g_v9 = dL_dC;
+                f3dg_bwd_pair_partials<true>(g, px, pr, sC[j], sX[j], w.ddelx_dx, w.ddely_dy, contributor, Tr, dL_dalpha);
             }
 
             // the 17 partials summed over the wave's 64 pixels (pair32 / pair16, then row-local DPP); the values are paired so that
             // lane 15 of row r holds element r of each target array:
             //                     row 0          row 1          row 2          row 3
-            const float f0 = row_total(pair16(pair32(g_col0, g_col2), pair32(g_col1, g_mx)));     // col0   col1   col2   mean2D.x
-            const float f1 = row_total(pair16(pair32(g_my, g_op), pair32(g_mz, 0.0f)));           // m2D.y  m2D.z  opacity  -
-            const float d0 = row_total(pair16(pair32(g_v0, g_v2), pair32(g_v1, g_v3)));           // v0 v1 v2 v3
-            const float d1 = row_total(pair16(pair32(g_v4, g_v6), pair32(g_v5, g_v7)));           // v4 v5 v6 v7
-            const float d2 = row_total(pair16(pair32(g_v8, 0.0f), pair32(g_v9, 0.0f)));           // v8 v9 -  -
+            const float f0 = row_total(pair16(pair32(g[0], g[2]), pair32(g[1], g[3])));           // col0   col1   col2   mean2D.x
+            const float f1 = row_total(pair16(pair32(g[4], g[6]), pair32(g[5], 0.0f)));           // m2D.y  m2D.z  opacity  -
+            const float d0 = row_total(pair16(pair32(g[7], g[9]), pair32(g[8], g[10])));          // v0 v1 v2 v3
+            const float d1 = row_total(pair16(pair32(g[11], g[13]), pair32(g[12], g[14])));       // v4 v5 v6 v7
+            const float d2 = row_total(pair16(pair32(g[15], 0.0f), pair32(g[16], 0.0f)));         // v8 v9 -  -
             if ((lane & 15u) == 15u) {
                 const size_t id = pe.y;
                 unsafeAtomicAdd(reinterpret_cast<float*>(add0 + id * 12u), f0);
@@ -353,7 +185,7 @@ render3_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
         w.retire();
     }
     if (lane == 0 && n_pairs)
-        atomicAdd(&hdr->bwd_pairs, (unsigned long long)n_pairs);
+        atomicAdd(&a.hdr->bwd_pairs, (unsigned long long)n_pairs);
 }
 
 struct M3 { float m[3][3]; };
@@ -675,9 +507,12 @@ preprocess_bwd_kernel(int P, int D, int M, const float* __restrict__ means3D, co
     }
 }
 
-} // namespace
-
-namespace {
+// the lock-step walk compiled for OCC waves per SIMD (option bwd_occ)
+template <int OCC>
+void launch_render3_bwd(const F3dgBwdLaunch& a)
+{
+    F3DG_KLAUNCH((render3_bwd_kernel<OCC>), a.quadrants(), dim3(64), 0, a.s, a.k, a.dL_dmean2D, a.dL_dopacity, a.dL_dcolors);
+}
 
 int backward_sets(void* stream, void* workspace, size_t workspace_bytes, long long max_rendered,
                   int n_sets, int views_per_set, int P, int D, int M, const float* background, int W, int H,
@@ -726,25 +561,24 @@ int backward_sets(void* stream, void* workspace, size_t workspace_bytes, long lo
     }
     const int prof = f3dg_prof_bwd_begin(s);
 
+    const F3dgBwdLaunch launch = { s, { n_views, P, W, H, tiles_x, T, focal_x, focal_y, hdr, reinterpret_cast<const uint2*>(ws + L.ranges),
+                                        reinterpret_cast<const unsigned*>(ws + L.vals[0]), reinterpret_cast<const unsigned*>(ws + L.small_list),
+                                        reinterpret_cast<const F3dgRec*>(ws + L.rec), reinterpret_cast<const float4*>(ws + L.cull),
+                                        reinterpret_cast<const float2*>(ws + L.means2D), reinterpret_cast<const float4*>(ws + L.conic), background,
+                                        (flags & F3DG_FLAG_BG_PER_VIEW) ? 1 : 0, reinterpret_cast<const float*>(ws + L.final_T),
+                                        reinterpret_cast<const unsigned*>(ws + L.n_contrib), dL_dpix, acc },
+                                   dL_dmean2D, dL_dopacity, dL_dcolor };
     if (dense) {
-        const int rc5 = f3dg_launch_render5_bwd(s, n_views, P, W, H, tiles_x, T, focal_x, focal_y, hdr, reinterpret_cast<const uint2*>(ws + L.ranges),
-                                                reinterpret_cast<const unsigned*>(ws + L.vals[0]), reinterpret_cast<const unsigned*>(ws + L.small_list),
-                                                reinterpret_cast<const F3dgRec*>(ws + L.rec), reinterpret_cast<const float4*>(ws + L.cull),
-                                                reinterpret_cast<const float2*>(ws + L.means2D), reinterpret_cast<const float4*>(ws + L.conic), background,
-                                                (flags & F3DG_FLAG_BG_PER_VIEW) ? 1 : 0, reinterpret_cast<const float*>(ws + L.final_T),
-                                                reinterpret_cast<const unsigned*>(ws + L.n_contrib), dL_dpix, dL_dmean2D, dL_dopacity, dL_dcolor, acc);
+        const int rc5 = f3dg_launch_render5_bwd(launch);
         if (rc5 != F3DG_OK) return rc5;
     } else {
-#define F3DG_LAUNCH_BWD3(OCC) F3DG_KLAUNCH((render3_bwd_kernel<OCC>), dim3((unsigned)n_views * (unsigned)T * 4u), dim3(64), 0, s, n_views, P, W, H,  \
-                           tiles_x, T, focal_x, focal_y, hdr, reinterpret_cast<const uint2*>(ws + L.ranges),                                        \
-                           reinterpret_cast<const unsigned*>(ws + L.vals[0]), reinterpret_cast<const unsigned*>(ws + L.small_list), reinterpret_cast<const F3dgRec*>(ws + L.rec),                        \
-                           reinterpret_cast<const float4*>(ws + L.cull),                                                                            \
-                           reinterpret_cast<const float2*>(ws + L.means2D), reinterpret_cast<const float4*>(ws + L.conic),                         \
-                           background, (flags & F3DG_FLAG_BG_PER_VIEW) ? 1 : 0, reinterpret_cast<const float*>(ws + L.final_T),                    \
-                           reinterpret_cast<const unsigned*>(ws + L.n_contrib), dL_dpix, dL_dmean2D, dL_dopacity, dL_dcolor, acc)
-        if (g_f3dg_bwd_occ == 4) F3DG_LAUNCH_BWD3(4); else if (g_f3dg_bwd_occ == 6) F3DG_LAUNCH_BWD3(6); else if (g_f3dg_bwd_occ == 3) F3DG_LAUNCH_BWD3(3);
-        else if (g_f3dg_bwd_occ == 2) F3DG_LAUNCH_BWD3(2); else F3DG_LAUNCH_BWD3(5);
-#undef F3DG_LAUNCH_BWD3
+        switch (g_f3dg_bwd_occ) {
+        case 2: launch_render3_bwd<2>(launch); break;
+        case 3: launch_render3_bwd<3>(launch); break;
+        case 4: launch_render3_bwd<4>(launch); break;
+        case 6: launch_render3_bwd<6>(launch); break;
+        default: launch_render3_bwd<5>(launch); break;
+        }
     }
     f3dg_prof_bwd_mark(prof, 0, s);
     F3DG_KLAUNCH(preprocess_bwd_kernel, dim3((P + F3DG_BLOCK - 1) / F3DG_BLOCK, (unsigned)n_sets), dim3(F3DG_BLOCK), 0, s, P,

@@ -7,7 +7,7 @@
 // ENTRY-major (a scalar loop over the entries: the ballot of the pixels an entry reaches, every such pixel lane writes its pair at ring
 // position tail + mbcnt) and processed 64 to a batch, one pair per lane:
 //   * the pair's pixel constants (ray, dL/dpixel, the pixel's totals) come by ds_bpermute from the lane that owns the pixel, its record from
-//     the staged window; alpha is recomputed exactly as the forward did (f3dg_fast_t_G or the reference's float32 / float64 order);
+//     the staged window; alpha is recomputed exactly as the forward did (f3dg_bwd_pair_eval);
 //   * the per-pixel recurrence -- T rebuilt back to front (a correctly rounded reciprocal per pair, a multiply per layer), the colour /
 //     normal blended behind the entry -- lives in LDS
 //     (one float4 per pixel) and is advanced entry after entry: the lanes of one entry's run update the slots of their pixels together,
@@ -15,13 +15,15 @@
 //     they only ever meet dL/dpixel as a dot product and dL/dpixel is constant per pixel;
 //   * the 17 partials are summed over the pixels of an entry by segmented scans along its run (f3dg_segscan.h) and added to memory by the
 //     run's last lane.
-// Same arithmetic per pair as render3_bwd_kernel except for the folded recurrence and the order of the per-entry sums (a tree over the
-// run instead of a transposed butterfly over the wave): compositing-stage gradients within 1e-5 of the oracle as before
+// The arithmetic of a pair is f3dg_bwd_pair.h, shared with render3_bwd_kernel; this kernel's own are the folded recurrence, the
+// reciprocal-and-multiply rebuild of T, its rounding of the background term and the order of the per-entry sums (a tree over the run
+// instead of a transposed butterfly over the wave): compositing-stage gradients within 1e-5 of the oracle as before
 // (tests/test_raster_backward_gpu.py runs with either kernel).
 #include "f3dg_common.h"
 #include "f3dg_ellipse.h"
 #include "f3dg_quad.h"
 #include "f3dg_segscan.h"
+#include "f3dg_bwd_pair.h"
 
 int g_f3dg_bwd_dense = 1;             // option bwd_dense: 1 (default) = render5_bwd_kernel, 0 = render3_bwd_kernel (the lock-step walk)
 
@@ -32,20 +34,11 @@ namespace {
 
 template <int OCC>
 __global__ void __launch_bounds__(64, OCC)
-render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x, float focal_y,
-                   F3dgHeader* __restrict__ hdr, const uint2* __restrict__ ranges,
-                   const unsigned* __restrict__ point_list_general, const unsigned* __restrict__ small_list, const F3dgRec* __restrict__ rec,
-                   const float4* __restrict__ cull,
-                   const float2* __restrict__ means2D, const float4* __restrict__ conic,
-                   const float* __restrict__ background, int bg_per_view,
-                   const float* __restrict__ final_T, const unsigned* __restrict__ n_contrib,
-                   const float* __restrict__ dL_dpixels,
-                   float* __restrict__ dL_dmean2D, float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolors,
-                   double* __restrict__ dL_dv2g_acc)
+render5_bwd_kernel(const F3dgBwdLaunch::Args a)
 {
-    const F3dgQuad qd = f3dg_quad(V, T, tiles_x);
+    const F3dgQuad qd = f3dg_quad(a.V, a.T, a.tiles_x);
     const unsigned lane = threadIdx.x;
-    const auto [pix_x, pix_y, inside, pix_id, ray_x, ray_y] = f3dg_quad_pixel(qd, lane, W, H, focal_x, focal_y);
+    const auto [pix_x, pix_y, inside, pix_id, ray_x, ray_y] = f3dg_quad_pixel(qd, lane, a.W, a.H, a.focal_x, a.focal_y);
 
     __shared__ float4 sR[4][64];          // records of the window, [16-byte chunk][entry] (global_load_lds image)
     __shared__ float4 sC[64];             // 2D conic (x, y, z) and, over the opacity * coef the record carries as well, the projected centre's x
@@ -55,8 +48,7 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
     __shared__ __attribute__((aligned(16))) float sOut[F3DG_B5_STAGE][20];     // the 17 totals + Gaussian id of up to twelve runs on their way to one-element-per-lane
     __shared__ float4 sS[64];             // per pixel: (T in front of its last blended entry, blended dot behind it, that entry's alpha, its dot)
 
-    F3dgBwdWindow<true> w(sR, sC, nullptr, sY, sQ, qd, inside, pix_id, lane, P, T, W, H, hdr, ranges, point_list_general, small_list, rec, cull,
-                          means2D, conic, background, bg_per_view, final_T, n_contrib, dL_dpixels);
+    F3dgBwdWindow<true> w(a, sR, sC, nullptr, sY, sQ, qd, inside, pix_id, lane);
     const unsigned qx0 = qd.qx0, qy0 = qd.qy0;
     unsigned n_pairs = 0;                 // contributing (pixel, Gaussian) pairs of this wave
 
@@ -69,7 +61,7 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
     // one 128-byte record per (view, Gaussian) takes all 17 sums of an entry: ten float64 (view2gaussian) at byte 0, seven float32 (colour,
     // mean2D, opacity) at byte 80 -- an atomic event touches ONE line (three 64-byte requests at most) instead of four arrays;
     // preprocess_bwd_kernel hands the float32 ones to the caller's arrays
-    double* const gacc = dL_dv2g_acc + w.vP * 16;
+    double* const gacc = a.dL_dv2g_acc + w.vP * 16;
     while (w.next()) {
         // ---- the window's contributing (pixel, entry) pairs, ENTRY-major (back to front: window slot order), 64 to a batch
         unsigned long long todo = w.any;
@@ -106,47 +98,23 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
             const unsigned long long upto = heads_all & (~0ull >> (63u - lane));
             const unsigned rr = valid ? lane - (63u - (unsigned)__builtin_clzll(upto | 1ull)) : 0u;
             const int oaddr = (int)(own << 2);
-#define F3DG_B5_PULL(v) __int_as_float(__builtin_amdgcn_ds_bpermute(oaddr, __float_as_int(v)))
-            const float p_ray_x = F3DG_B5_PULL(ray_x), p_ray_y = F3DG_B5_PULL(ray_y);
-            const float p_dpx0 = F3DG_B5_PULL(w.dpx0), p_dpx1 = F3DG_B5_PULL(w.dpx1), p_dpx2 = F3DG_B5_PULL(w.dpx2);
-            const float p_dn0 = F3DG_B5_PULL(w.dn0), p_dn1 = F3DG_B5_PULL(w.dn1), p_dn2 = F3DG_B5_PULL(w.dn2);
-            const float p_dmaxd = F3DG_B5_PULL(w.dL_dmax_depth), p_dreg = F3DG_B5_PULL(w.dL_dreg);
-            const float p_final_A = F3DG_B5_PULL(w.final_A), p_final_D = F3DG_B5_PULL(w.final_D), p_TfBg = F3DG_B5_PULL(TfBg);
-            const int p_maxc = __builtin_amdgcn_ds_bpermute(oaddr, w.max_contributor);
-            const float p_pixx = (float)(qx0 + (own & 7u)), p_pixy = (float)(qy0 + (own >> 3));      // the owner's pixel
-#undef F3DG_B5_PULL
+            // the pair's pixel constants, from the lane that owns the pixel
+            F3dgBwdPixel px;
+            px.ray_x = f3dg_pull(oaddr, ray_x); px.ray_y = f3dg_pull(oaddr, ray_y);
+            px.dpx[0] = f3dg_pull(oaddr, w.dpx0); px.dpx[1] = f3dg_pull(oaddr, w.dpx1); px.dpx[2] = f3dg_pull(oaddr, w.dpx2);
+            px.dn[0] = f3dg_pull(oaddr, w.dn0); px.dn[1] = f3dg_pull(oaddr, w.dn1); px.dn[2] = f3dg_pull(oaddr, w.dn2);
+            px.dL_dmax_depth = f3dg_pull(oaddr, w.dL_dmax_depth); px.dL_dreg = f3dg_pull(oaddr, w.dL_dreg);
+            px.final_A = f3dg_pull(oaddr, w.final_A); px.final_D = f3dg_pull(oaddr, w.final_D);
+            const float p_TfBg = f3dg_pull(oaddr, TfBg);
+            px.max_contributor = __builtin_amdgcn_ds_bpermute(oaddr, w.max_contributor);
+            px.pix_x = (float)(qx0 + (own & 7u)); px.pix_y = (float)(qy0 + (own >> 3));
             const uint2 pe = w.entry((unsigned)j);
             const int contributor = (int)pe.x;
 
-            const float4 q0 = sR[0][j], q1 = sR[1][j], q2 = sR[2][j];
-            const float n0 = q0.x * p_ray_x + q0.y * p_ray_y + q0.z;
-            const float n1 = q0.y * p_ray_x + q0.w * p_ray_y + q1.x;
-            const float n2 = q0.z * p_ray_x + q1.x * p_ray_y + q1.y;
-            const float aaf = p_ray_x * n0 + p_ray_y * n1 + n2;
-            const float bhalf = q1.z * p_ray_x + q1.w * p_ray_y + q2.x;
-            const float CC = q2.y;
-            float t = 1.0f, G = 0, alpha = 0;
-            bool active = valid;
-            if (active) {
-                if (w.alpha_fast) {
-                    // the forward of this workspace took the fast arithmetic: the same function, to the bit
-                    f3dg_fast_t_G(aaf, bhalf, CC, t, G);
-                    if (t < 0.2f) active = false;
-                    alpha = fminf(0.99f, q2.z * G);
-                } else {
-                    const double AA = aaf;
-                    const double BB = 2 * bhalf;
-                    const double q = BB / AA;                          // one division: -BB / (2 * AA) == -0.5 * (BB / AA) exactly
-                    t = (float)(-0.5 * q);
-                    if (t <= F3DG_NEAR_PLANE) active = false;
-                    const double min_value = -q * (BB / 4.) + CC;
-                    float power = (float)(-0.5f * min_value);
-                    if (power > 0.0f) power = 0.0f;
-                    G = expf(power);
-                    alpha = fminf(0.99f, q2.z * G);
-                }
-                if (alpha < 1.0f / 255.0f) active = false;
-            }
+            const float4 q2 = sR[2][j];
+            const F3dgBwdPair pr = f3dg_bwd_pair_eval(sR[0][j], sR[1][j], q2, px.ray_x, px.ray_y, w.alpha_fast, valid);
+            const bool active = pr.live;
+            const float alpha = pr.alpha;
             n_pairs += (unsigned)__popcll(__ballot(active));
 
             // ---- gradient terms only from here: float32 with one reciprocal each, FMA contraction allowed (as render3_bwd_kernel)
@@ -159,10 +127,10 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                 float4 con = sC[j];
                 const float2 xy = make_float2(con.w, sY[j]);
                 con.w = q2.z;
-                const float inv_len = __builtin_amdgcn_rsqf(n0 * n0 + n1 * n1 + n2 * n2 + 1e-7f);
-                const float nn0 = -n0 * inv_len, nn1 = -n1 * inv_len, nn2 = -n2 * inv_len;
+                float nn0, nn1, nn2;
+                f3dg_bwd_pair_normal(pr, nn0, nn1, nn2);
                 const float c0 = q3.x, c1 = q3.y, c2 = q3.z;
-                const float u = c0 * p_dpx0 + c1 * p_dpx1 + c2 * p_dpx2 + nn0 * p_dn0 + nn1 * p_dn1 + nn2 * p_dn2;
+                const float u = c0 * px.dpx[0] + c1 * px.dpx[1] + c2 * px.dpx[2] + nn0 * px.dn[0] + nn1 * px.dn[1] + nn2 * px.dn[2];
                 const float oma = 1.f - alpha;
 
                 // ---- the recurrence, entry after entry (a pixel has at most one pair per entry, so the lanes of a run never share a
@@ -187,60 +155,10 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
                 }
 
                 if (active) {
-                    const float d_x = xy.x - p_pixx, d_y = xy.y - p_pixy;
-                    const float inv_t = __builtin_amdgcn_rcpf(t);
-                    const float mapped_max_t = fmaf(-0.20040080160320642f, inv_t, 1.0020040080160322f);
-                    const float dmax_t_dd = 0.20040080160320642f * inv_t * inv_t;
                     const float inv_oma = __builtin_amdgcn_rcpf(oma);      // background term only
-                    const float dchannel_dcolor = alpha * Tr;
-                    g[0] = dchannel_dcolor * p_dpx0;
-                    g[1] = dchannel_dcolor * p_dpx1;
-                    g[2] = dchannel_dcolor * p_dpx2;
-                    const float dL_dmax_t = 2.0f * (Tr * alpha) * (mapped_max_t * p_final_A - p_final_D) * p_dreg * dmax_t_dd;
-                    const float dnn0 = alpha * Tr * p_dn0, dnn1 = alpha * Tr * p_dn1, dnn2 = alpha * Tr * p_dn2;
-                    float dL_dlength = (dnn0 * n0 + dnn1 * n1 + dnn2 * n2);
-                    dL_dlength *= inv_len * inv_len;
-                    float dLn0 = (-dnn0 + dL_dlength * n0) * inv_len;
-                    float dLn1 = (-dnn1 + dL_dlength * n1) * inv_len;
-                    float dLn2 = (-dnn2 + dL_dlength * n2) * inv_len;
-                    float dL_dt = dL_dmax_t;
-                    if (contributor == p_maxc - 1)
-                        dL_dt += p_dmaxd;
                     float dL_dalpha = (u - A) * Tr;
                     dL_dalpha += (-inv_oma) * p_TfBg;
-
-                    const float dL_dG = con.w * dL_dalpha;
-                    const float gdx = G * d_x;
-                    const float gdy = G * d_y;
-                    const float dG_ddelx = -gdx * con.x - gdy * con.y;
-                    const float dG_ddely = -gdy * con.z - gdx * con.y;
-                    g[3] = dL_dG * dG_ddelx * w.ddelx_dx;
-                    g[4] = dL_dG * dG_ddely * w.ddely_dy;
-                    g[5] = fabsf(dL_dG * dG_ddelx * w.ddelx_dx) + fabsf(dL_dG * dG_ddely * w.ddely_dy);
-                    g[6] = G * dL_dalpha;
-
-                    const float dL_dpower = dL_dG * G;
-                    const float dL_dmin_value = dL_dpower * -0.5f;
-                    const float qf = -2.0f * t, inv_a = __builtin_amdgcn_rcpf(aaf);
-                    float dL_dA = dL_dmin_value * qf * qf * 0.25f;
-                    float dL_dB = dL_dmin_value * (-0.5f * qf);
-                    const float dL_dC = dL_dmin_value;
-                    dL_dA += dL_dt * (0.5f * qf * inv_a);
-                    dL_dB += dL_dt * (-0.5f * inv_a);
-                    dLn0 += dL_dA * p_ray_x;
-                    dLn1 += dL_dA * p_ray_y;
-                    dLn2 += dL_dA;
-
-                    g[7] = dLn0 * p_ray_x;
-                    g[8] = dLn0 * p_ray_y + dLn1 * p_ray_x;
-                    g[9] = dLn0 + dLn2 * p_ray_x;
-                    g[10] = dLn1 * p_ray_y;
-                    g[11] = dLn1 + dLn2 * p_ray_y;
-                    g[12] = dLn2;
-                    g[13] = dL_dB * 2 * p_ray_x;
-                    g[14] = dL_dB * 2 * p_ray_y;
-                    g[15] = dL_dB * 2;
-                    g[16] = dL_dC;
+                    f3dg_bwd_pair_partials<false>(g, px, pr, con, xy, w.ddelx_dx, w.ddely_dy, contributor, Tr, dL_dalpha);
                 }
 
                 // ---- the 17 partials of an entry summed over its pixels: segmented scans along the entry's run, totals in its last lane
@@ -303,21 +221,15 @@ render5_bwd_kernel(int V, int P, int W, int H, int tiles_x, int T, float focal_x
         w.retire();
     }
     if (lane == 0 && n_pairs)
-        atomicAdd(&hdr->bwd_pairs, (unsigned long long)n_pairs);
+        atomicAdd(&a.hdr->bwd_pairs, (unsigned long long)n_pairs);
 }
 
 
 } // namespace
 
-int f3dg_launch_render5_bwd(hipStream_t s, int V, int P, int W, int H, int tiles_x, int T, float focal_x, float focal_y, F3dgHeader* hdr,
-                            const uint2* ranges, const unsigned* point_list, const unsigned* small_list, const F3dgRec* rec, const float4* cull,
-                            const float2* means2D, const float4* conic, const float* background, int bg_per_view, const float* final_T,
-                            const unsigned* n_contrib, const float* dL_dpixels, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolors,
-                            double* dL_dv2g_acc)
+int f3dg_launch_render5_bwd(const F3dgBwdLaunch& a)
 {
-    F3DG_KLAUNCH((render5_bwd_kernel<F3DG_B5_OCC>), dim3((unsigned)V * (unsigned)T * 4u), dim3(64), 0, s, V, P, W, H, tiles_x, T, focal_x, focal_y, hdr, ranges,
-                 point_list, small_list, rec, cull, means2D, conic, background, bg_per_view, final_T, n_contrib, dL_dpixels, dL_dmean2D,
-                 dL_dopacity, dL_dcolors, dL_dv2g_acc);
+    F3DG_KLAUNCH((render5_bwd_kernel<F3DG_B5_OCC>), a.quadrants(), dim3(64), 0, a.s, a.k);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }

@@ -274,11 +274,35 @@ int f3dg_launch_render5_small(const F3dgRenderLaunch& a);         // one- and tw
 
 // the dense compositing backward (f3dg_backward5.hip; option bwd_dense)
 extern int g_f3dg_bwd_dense;           // 1: render5_bwd_kernel (entry-major batches of (pixel, entry) pairs, segmented scans); 0: render3_bwd_kernel (lock-step walk)
-int f3dg_launch_render5_bwd(hipStream_t s, int V, int P, int W, int H, int tiles_x, int T, float focal_x, float focal_y, F3dgHeader* hdr,
-                            const uint2* ranges, const unsigned* point_list, const unsigned* small_list, const F3dgRec* rec, const float4* cull,
-                            const float2* means2D, const float4* conic, const float* background, int bg_per_view, const float* final_T,
-                            const unsigned* n_contrib, const float* dL_dpixels, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolors,
-                            double* dL_dv2g_acc);
+// What a compositing backward launch is handed: backward_sets (f3dg_backward.hip) fills it once and picks the kernel. `k` is the part
+// the device sees -- both kernels take it by value, F3dgBwdWindow (f3dg_quad.h) by reference.
+struct F3dgBwdLaunch {
+    hipStream_t s;
+    struct Args {
+        int V, P, W, H, tiles_x, T;
+        float focal_x, focal_y;
+        F3dgHeader* hdr;
+        const uint2* ranges;
+        const unsigned* point_list_general;
+        const unsigned* small_list;       // the per-tile lists of a forward that took the small-call path
+        const F3dgRec* rec;
+        const float4* cull;
+        const float2* means2D;
+        const float4* conic;
+        const float* background;
+        int bg_per_view;
+        const float* final_T;
+        const unsigned* n_contrib;
+        const float* dL_dpixels;
+        double* dL_dv2g_acc;              // [V*P][10] float64 (lock-step) or the [V*P] 128-byte records (dense)
+    } k;
+    // render3_bwd_kernel only: it adds into the caller's arrays; the dense kernel's sums reach them through preprocess_bwd_kernel
+    float* dL_dmean2D;
+    float* dL_dopacity;
+    float* dL_dcolors;
+    dim3 quadrants() const { return dim3((unsigned)k.V * (unsigned)k.T * 4u); }      // the grid of a quadrant kernel
+};
+int f3dg_launch_render5_bwd(const F3dgBwdLaunch& a);
 
 int f3dg_launch_integrate_fill(hipStream_t s, int W, int H, int PN, float* out_color, float* out_alpha_integrated,
                                float* out_color_integrated);

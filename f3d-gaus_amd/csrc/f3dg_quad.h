@@ -204,7 +204,9 @@ struct F3dgHalfWindow {
 // the per-tile slots) and the pixel's inputs (the forward's auxiliary planes, dL/dpixels); the scan from the deepest last contributor
 // of the quadrant's pixels back to the list's first entry into a ring of (list position, id); a window's staging -- record by
 // global_load_lds, 2D conic, projected centre -- and phase 1: lane e tests entry e against the 64 pixels (quad_ballots_any), every
-// pixel gets its pass mask and the wave the mask of entries that can reach ANY of its pixels.
+// pixel gets its pass mask and the wave the mask of entries that can reach ANY of its pixels. Shared by render3_bwd_kernel and
+// render5_bwd_kernel; what they do with a window's pairs is in f3dg_bwd_pair.h and in the kernels. The constructor takes the launch
+// record's device part (F3dgBwdLaunch::Args, f3dg_common.h), the kernel's LDS, its quadrant and the lane's pixel.
 // LDS the kernel declares: float4 sR[4][64] records, float4 sC[64] 2D conic + opacity * coef, uint2 sQ[F3DG_QUAD_RING]; the projected
 // centre goes to float2 sX[64] or, with CENTRE_IN_CONIC, its x over sC[j].w (the record carries opacity * coef as well: word 10,
 // sR[2][j].z) and its y to float sY[64].
@@ -234,18 +236,17 @@ struct F3dgBwdWindow {
     unsigned m;                       // entries of the window
     unsigned long long pass, any;     // phase 1: the pixel's pass mask; the entries that reach any pixel of the quadrant
 
-    __device__ __forceinline__ F3dgBwdWindow(float4 (*sR_)[64], float4* sC_, float2* sX_, float* sY_, uint2* sQ_, const F3dgQuad& q, bool inside,
-                                             size_t pix_id, unsigned lane_, int P, int T, int W, int H, F3dgHeader* hdr, const uint2* ranges,
-                                             const unsigned* point_list_general, const unsigned* small_list, const F3dgRec* rec,
-                                             const float4* cull, const float2* means2D_, const float4* conic_, const float* background,
-                                             int bg_per_view, const float* final_T, const unsigned* n_contrib, const float* dL_dpixels)
-        : sR(sR_), sC(sC_), sX(sX_), sY(sY_), sQ(sQ_), means2D(means2D_), conic(conic_), qx0(q.qx0), qy0(q.qy0), lane(lane_), qhead(0),
+    __device__ __forceinline__ F3dgBwdWindow(const F3dgBwdLaunch::Args& a, float4 (*sR_)[64], float4* sC_, float2* sX_, float* sY_, uint2* sQ_,
+                                             const F3dgQuad& q, bool inside, size_t pix_id, unsigned lane_)
+        : sR(sR_), sC(sC_), sX(sX_), sY(sY_), sQ(sQ_), means2D(a.means2D), conic(a.conic), qx0(q.qx0), qy0(q.qy0), lane(lane_), qhead(0),
           qcount(0), m(0), pass(0ull), any(0ull)
     {
-        uint2 range = ranges[(size_t)q.view * T + q.tile];
+        F3dgHeader* const hdr = a.hdr;
+        const int W = a.W, H = a.H;
+        uint2 range = a.ranges[(size_t)q.view * a.T + q.tile];
         // no lists to walk after an overflow -- and none that belong to this call when the workspace's last forward kept no auxiliary
         // planes (an inference call): all gradients stay zero, the header says why
-        point_list = hdr->small_path != 0u ? small_list : point_list_general;
+        point_list = hdr->small_path != 0u ? a.small_list : a.point_list_general;
         if (hdr->overflow || hdr->save_aux == 0u) {
             range = make_uint2(0, 0);
             if (!hdr->overflow && blockIdx.x == 0 && threadIdx.x == 0) hdr->bwd_stale = 1u;
@@ -253,14 +254,14 @@ struct F3dgBwdWindow {
         start = range.x;
         alpha_fast = hdr->alpha_fast != 0;
 
-        vP = (size_t)q.view * P;
-        vrec = rec + vP;
-        vcull = cull + vP;
+        vP = (size_t)q.view * a.P;
+        vrec = a.rec + vP;
+        vcull = a.cull + vP;
         const size_t HW = (size_t)H * W;
-        const float* fT = final_T + (size_t)q.view * 4 * HW;
-        const unsigned* nc = n_contrib + (size_t)q.view * 2 * HW;
-        const float* dpix = dL_dpixels + (size_t)q.view * F3DG_OUT_CHANNELS * HW;
-        const float* bg = background + (bg_per_view ? 3 * q.view : 0);
+        const float* fT = a.final_T + (size_t)q.view * 4 * HW;
+        const unsigned* nc = a.n_contrib + (size_t)q.view * 2 * HW;
+        const float* dpix = a.dL_dpixels + (size_t)q.view * F3DG_OUT_CHANNELS * HW;
+        const float* bg = a.background + (a.bg_per_view ? 3 * q.view : 0);
         T_final = inside ? fT[pix_id] : 0;
         final_D = inside ? fT[pix_id + HW] : 0;
         final_A = 1 - T_final;
