@@ -92,6 +92,12 @@ SIGNATURES = {
     "f3dg_residual_join_f16": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _f, _p]),
     "f3dg_residual_join": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _f, _p]),
     "f3dg_residual_join_bf16": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _f, _p]),
+    # training through the backbone: the stats-keeping float32 forward and the adjoints (stream N C HW groups nhwc | ...)
+    "f3dg_group_norm_silu_stats": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _f, _i, _p, _p, _p, _sz]),
+    "f3dg_group_norm_silu_backward_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "f3dg_group_norm_silu_backward": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _sz]),
+    "f3dg_residual_join_backward_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "f3dg_residual_join_backward": (_i, [_p, _i, _i, _i, _i, _p, _f, _p, _p, _p, _sz]),
     "f3dg_group_norm_silu_nhwc": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _f, _i, _p, _p, _sz]),
     "f3dg_group_norm_silu_nhwc_bf16": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _f, _i, _p, _p, _sz]),
     # n_planes W H  /  stream | n_planes W H | img1 img2 | map dm_dmu1 dm_dsigma1_sq dm_dsigma12 | partials partials_bytes plane_sums

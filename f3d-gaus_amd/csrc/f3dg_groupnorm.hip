@@ -10,85 +10,9 @@
 // float64, and re-reads the slab (<= 1 MiB: L2-resident) to write silu(weight * (x - mean) * rstd + bias). Two HBM
 // passes (one read, one write) instead of five. The channels-last pair of kernels is described where it is defined.
 #include "f3dg_common.h"
+#include "f3dg_groupnorm.h"
 
 namespace {
-
-constexpr int GN_THREADS = 1024;
-
-// bf16 <-> f32 (round to nearest even; NaN kept quiet)
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ unsigned short f32_to_bf16(float f)
-{
-    const unsigned u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (unsigned short)((u >> 16) | 0x40u);
-    return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-
-// 16-byte packets: 4 floats or 8 bf16
-template <typename T> struct Packet;
-template <> struct Packet<float> {
-    static constexpr int N = 4;
-    float v[4];
-    __device__ __forceinline__ void load(const float* p) { const float4 q = *reinterpret_cast<const float4*>(p); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
-    __device__ __forceinline__ void store(float* p) const { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <> struct Packet<unsigned short> {
-    static constexpr int N = 8;
-    float v[8];
-    __device__ __forceinline__ void load(const unsigned short* p)
-    {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        const unsigned w[4] = { q.x, q.y, q.z, q.w };
-#pragma unroll
-        for (int i = 0; i < 4; i++) { v[2 * i] = __uint_as_float(w[i] << 16); v[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u); }
-    }
-    __device__ __forceinline__ void store(unsigned short* p) const
-    {
-        unsigned w[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) w[i] = (unsigned)f32_to_bf16(v[2 * i]) | ((unsigned)f32_to_bf16(v[2 * i + 1]) << 16);
-        *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-};
-// 8 float16 (the fp16 option of the backbone: 10 mantissa bits at the bf16 MFMA rate; T = _Float16)
-template <> struct Packet<_Float16> {
-    static constexpr int N = 8;
-    float v[8];
-    __device__ __forceinline__ void load(const _Float16* p)
-    {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        const unsigned w[4] = { q.x, q.y, q.z, q.w };
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            v[2 * i] = (float)__builtin_bit_cast(_Float16, (unsigned short)(w[i] & 0xFFFFu));
-            v[2 * i + 1] = (float)__builtin_bit_cast(_Float16, (unsigned short)(w[i] >> 16));
-        }
-    }
-    __device__ __forceinline__ void store(_Float16* p) const
-    {
-        unsigned w[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-            w[i] = (unsigned)__builtin_bit_cast(unsigned short, (_Float16)v[2 * i]) | ((unsigned)__builtin_bit_cast(unsigned short, (_Float16)v[2 * i + 1]) << 16);
-        *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-};
-// SiLU. float32 activations: expf and an IEEE division (the backbone's float32 parity bar is 2e-5 of the reference fixture).
-// bfloat16 activations: the result is rounded to 8 bits, so hardware exp2 / reciprocal (~1 ulp of float32 each) are invisible and the
-// ~30 instructions per element of the accurate form -- which made the kernel VALU-bound -- become 5.
-template <typename T> __device__ __forceinline__ float silu_of(float v)
-{
-    if constexpr (sizeof(T) == 2)
-        return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
-    else
-        return v / (1.0f + expf(-v));
-}
-__device__ __forceinline__ float to_f32(float x) { return x; }
-__device__ __forceinline__ float to_f32(unsigned short x) { return bf16_to_f32(x); }
-__device__ __forceinline__ void from_f32(float& d, float x) { d = x; }
-__device__ __forceinline__ void from_f32(unsigned short& d, float x) { d = f32_to_bf16(x); }
-__device__ __forceinline__ float to_f32(_Float16 x) { return (float)x; }
-__device__ __forceinline__ void from_f32(_Float16& d, float x) { d = (_Float16)x; }
 
 // The statistics. One pass gives the variance as E[v^2] - E[v]^2, and in float32 sums that difference loses log2(1 + (mean / std)^2) bits:
 // summing v and v^2 themselves, a slab whose mean lies ten standard deviations from zero came out 20x less accurate than torch's float32
@@ -107,7 +31,7 @@ __device__ __forceinline__ void from_f32(_Float16& d, float x) { d = (_Float16)x
 template <typename T>
 __global__ void __launch_bounds__(GN_THREADS)
 group_norm_silu_kernel(int C, int HW, int groups, const T* __restrict__ x, const float* __restrict__ pre_bias, const float* __restrict__ weight,
-                       const float* __restrict__ bias, float eps, int apply_silu, T* __restrict__ y)
+                       const float* __restrict__ bias, float eps, int apply_silu, T* __restrict__ y, float2* __restrict__ stats_out)
 {
     constexpr int PN = Packet<T>::N;
     const int g = blockIdx.x % groups;
@@ -156,6 +80,7 @@ group_norm_silu_kernel(int C, int HW, int groups, const T* __restrict__ x, const
         if (var < 0.0) var = 0.0;
         s_mean = (float)((double)K + d);
         s_rstd = (float)(1.0 / sqrt(var + (double)eps));
+        if (stats_out) stats_out[blockIdx.x] = make_float2(s_mean, s_rstd);       // [n][g]: what the backward (f3dg_groupnorm_bwd.hip) normalises with
     }
     __syncthreads();
     const float mean = s_mean, rstd = s_rstd;
@@ -191,13 +116,13 @@ group_norm_silu_kernel(int C, int HW, int groups, const T* __restrict__ x, const
 
 template <typename T>
 int launch_gn(void* stream, int N, int C, int HW, int groups, const T* x, const float* pre_bias, const float* weight, const float* bias, float eps,
-              int apply_silu, T* y)
+              int apply_silu, T* y, float2* stats_out = nullptr)
 {
     if (N < 0 || C <= 0 || HW <= 0 || groups <= 0 || C % groups != 0 || !x || !weight || !bias || !y) return F3DG_ERR_BAD_ARG;
     if (N == 0) return F3DG_OK;
     if (((uintptr_t)x | (uintptr_t)y) & 15u) return F3DG_ERR_BAD_ARG;       // 16-byte loads / stores
     F3DG_KLAUNCH(group_norm_silu_kernel<T>, dim3((unsigned)(N * groups)), dim3(GN_THREADS), 0, (hipStream_t)stream, C, HW,
-                       groups, x, pre_bias, weight, bias, eps, apply_silu, y);
+                       groups, x, pre_bias, weight, bias, eps, apply_silu, y, stats_out);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }
@@ -212,12 +137,7 @@ int launch_gn(void* stream, int N, int C, int HW, int groups, const T* x, const 
 //       partial[n][g][block] = (sum, sum of squares); gn_nhwc_finish_kernel adds the blocks in order -> (mean, rstd) per (sample, group);
 //   gn_nhwc_apply_kernel: the same mapping; scale / shift of the thread's PN channels once, then one pass: silu((x + pre_bias) * sc + sh).
 // Two reads (the second from L2 / MALL) and one write, as the NCHW kernel.
-// pixels per workgroup: 512 where a sample has enough of them to fill the device. Below 128 x 128 pixels a run of 512 left the backbone's 64^2 / 32^2
-// layers 8 / 2 workgroups per sample, each thread walking up to 256 pixels one load latency after the other. A function of HW alone: the
-// order of the additions, and so the result of a sample, does not depend on the batch it is in.
-constexpr int gn_nhwc_pix(int HW) { return HW >= 16384 ? 512 : 64; }
-constexpr int GN_NHWC_MAXC = 1024;
-constexpr int GN_NHWC_UNROLL = 4;     // independent 16-byte loads in flight per thread
+
 
 // the pivot of (sample n, group g): the first value of the slab, as the moments and the finish kernel both read it
 template <typename T>
@@ -377,7 +297,7 @@ extern "C" size_t f3dg_group_norm_nhwc_scratch_bytes(int N, int HW, int groups);
 
 template <typename T>
 int launch_gn_nhwc(void* stream, int N, int C, int HW, int groups, const T* x, const float* pre_bias, const float* weight, const float* bias, float eps,
-                   int apply_silu, T* y, double* moments, size_t moments_bytes)
+                   int apply_silu, T* y, double* moments, size_t moments_bytes, float2* stats_out = nullptr)
 {
     constexpr int PN = Packet<T>::N;
     if (N < 0 || C <= 0 || HW <= 0 || groups <= 0 || C % groups != 0 || !x || !weight || !bias || !y || !moments) return F3DG_ERR_BAD_ARG;
@@ -390,7 +310,8 @@ int launch_gn_nhwc(void* stream, int N, int C, int HW, int groups, const T* x, c
     const int ppp = C / PN, rows = 256 / ppp;
     hipStream_t s = (hipStream_t)stream;
     const int nb = (HW + gn_nhwc_pix(HW) - 1) / gn_nhwc_pix(HW);
-    float2* stats = reinterpret_cast<float2*>(moments + 2 * (size_t)N * nb * groups);
+    // (mean, rstd) per (sample, group): behind the partials, or where the caller keeps them for the backward
+    float2* stats = stats_out ? stats_out : reinterpret_cast<float2*>(moments + 2 * (size_t)N * nb * groups);
     const dim3 grid((unsigned)nb, (unsigned)N);
     const int Cg = C / groups;
     if (Cg % PN == 0)
@@ -513,6 +434,18 @@ extern "C" size_t f3dg_group_norm_nhwc_scratch_bytes(int N, int HW, int groups)
     if (N <= 0 || HW <= 0 || groups <= 0) return 0;
     const size_t nb = (size_t)(HW + gn_nhwc_pix(HW) - 1) / gn_nhwc_pix(HW);
     return sizeof(double) * 2 * (size_t)N * nb * groups + sizeof(float2) * (size_t)N * groups;
+}
+
+// The float32 forward that keeps its statistics: stats [N][groups] (mean, rstd), the pair f3dg_group_norm_silu_backward normalises with.
+// nhwc = 0: the NCHW kernel (moments unused, may be null); nhwc = 1: the channels-last kernels. Same kernels, same y as the entries below.
+extern "C" int f3dg_group_norm_silu_stats(void* stream, int N, int C, int HW, int groups, int nhwc, const float* x, const float* pre_bias,
+                                          const float* weight, const float* bias, float eps, int apply_silu, float* y, float* stats,
+                                          double* moments, size_t moments_bytes)
+{
+    if (!stats || ((uintptr_t)stats & 7u)) return F3DG_ERR_BAD_ARG;
+    if (nhwc)
+        return launch_gn_nhwc<float>(stream, N, C, HW, groups, x, pre_bias, weight, bias, eps, apply_silu, y, moments, moments_bytes, reinterpret_cast<float2*>(stats));
+    return launch_gn<float>(stream, N, C, HW, groups, x, pre_bias, weight, bias, eps, apply_silu, y, reinterpret_cast<float2*>(stats));
 }
 
 // GroupNorm (+ SiLU) with the producing convolution's bias folded in (pre_bias, nullable): NCHW ...

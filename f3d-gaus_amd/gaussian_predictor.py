@@ -134,27 +134,134 @@ class Conv2d(nn.Module):
         return x
 
 
+def _gn_nhwc_ok(x):
+    """The channels-last GroupNorm kernels take x as it lies (float32: whole 4-channel packets, at most 1024 channels, 16-byte aligned)."""
+    return _is_nhwc(x) and x.shape[1] % (4 if x.dtype == torch.float32 else 8) == 0 and x.shape[1] <= 1024 and x.data_ptr() % 16 == 0
+
+
+def _dense_like(g, nhwc):
+    """The cotangent in the layout the kernels read, float32, 16-byte aligned."""
+    g = g.float()
+    g = g.contiguous(memory_format=torch.channels_last) if nhwc else g.contiguous()
+    return g.clone() if g.data_ptr() % 16 else g
+
+
+class _GroupNormSiLU(torch.autograd.Function):
+    """``f3dg_group_norm_silu_stats`` with ``f3dg_group_norm_silu_backward`` behind it (float32, NCHW or channels-last). Saved: ``x``, the
+    parameters and the (mean, rstd) pair per (sample, group) -- not the output and not the normalised pre-activation, which the backward
+    kernel recomputes from ``x``."""
+
+    @staticmethod
+    def forward(ctx, x, pre_bias, weight, bias, groups, eps, silu):
+        L = _lib.lib()
+        nhwc = _gn_nhwc_ok(x)
+        if not nhwc:
+            x = x.contiguous()
+            if x.data_ptr() % 16:
+                x = x.clone()
+        N, Cc = x.shape[0], x.shape[1]
+        HW = x.numel() // (N * Cc)
+        y = torch.empty_like(x)             # preserves the strides
+        stats = torch.empty((N, groups, 2), dtype=torch.float32, device=x.device)
+        mom, mom_bytes = None, 0
+        if nhwc:
+            mom = torch.empty(L.f3dg_group_norm_nhwc_scratch_bytes(N, HW, groups) // 8 + 1, dtype=torch.float64, device=x.device)
+            mom_bytes = mom.numel() * 8
+        rc = L.f3dg_group_norm_silu_stats(_stream(), N, Cc, HW, groups, 1 if nhwc else 0, _lib.ptr(x), _lib.ptr(pre_bias), _lib.ptr(weight),
+                                          _lib.ptr(bias), float(eps), 1 if silu else 0, _lib.ptr(y), _lib.ptr(stats), _lib.ptr(mom), mom_bytes)
+        _lib.check(rc, "f3dg_group_norm_silu_stats")
+        ctx.save_for_backward(x, pre_bias, weight, bias, stats)
+        ctx.groups, ctx.silu, ctx.nhwc = groups, bool(silu), nhwc
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, pre_bias, weight, bias, stats = ctx.saved_tensors
+        L = _lib.lib()
+        N, Cc = x.shape[0], x.shape[1]
+        HW = x.numel() // (N * Cc)
+        gy = _dense_like(gy, ctx.nhwc)
+        need = ctx.needs_input_grad
+        new = lambda: torch.empty(Cc, dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x) if need[0] else None
+        dpb = new() if (pre_bias is not None and need[1]) else None
+        dw = new() if need[2] else None
+        db = new() if need[3] else None
+        nbytes = L.f3dg_group_norm_silu_backward_scratch_bytes(N, Cc, HW, ctx.groups, 1 if ctx.nhwc else 0)
+        scratch = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=x.device)
+        rc = L.f3dg_group_norm_silu_backward(_stream(), N, Cc, HW, ctx.groups, 1 if ctx.nhwc else 0, _lib.ptr(x), _lib.ptr(pre_bias), _lib.ptr(weight),
+                                             _lib.ptr(bias), _lib.ptr(stats), 1 if ctx.silu else 0, _lib.ptr(gy), _lib.ptr(dx), _lib.ptr(dw),
+                                             _lib.ptr(db), _lib.ptr(dpb), _lib.ptr(scratch), scratch.numel() * 8)
+        _lib.check(rc, "f3dg_group_norm_silu_backward")
+        return dx, dpb, dw, db, None, None, None
+
+
+class _ResidualJoin(torch.autograd.Function):
+    """``f3dg_residual_join`` out of place with ``f3dg_residual_join_backward`` behind it: nothing is saved, the backward is one pass over
+    the cotangent whose result is the gradient of ``a`` and of ``b`` alike, and whose per-channel sum is the gradient of either bias."""
+
+    @staticmethod
+    def forward(ctx, a, bias_a, b, bias_b, scale):
+        nhwc = _is_nhwc(a)
+        N, Cc, H, W = a.shape
+        y = torch.empty_like(a)
+        _lib.check(_lib.lib().f3dg_residual_join(_stream(), N, Cc, H * W, 1 if nhwc else 0, _lib.ptr(a), _lib.ptr(bias_a), _lib.ptr(b), _lib.ptr(bias_b),
+                                                 float(scale), _lib.ptr(y)), "f3dg_residual_join")
+        ctx.nhwc, ctx.scale = nhwc, float(scale)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        L = _lib.lib()
+        gy = _dense_like(gy, ctx.nhwc)
+        N, Cc, H, W = gy.shape
+        need = ctx.needs_input_grad
+        g = torch.empty_like(gy)
+        gb, scratch, nbytes = None, None, 0
+        if need[1] or need[3]:
+            gb = torch.empty(Cc, dtype=torch.float32, device=gy.device)
+            nbytes = L.f3dg_residual_join_backward_scratch_bytes(N, Cc, H * W, 1 if ctx.nhwc else 0)
+            scratch = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=gy.device)
+        rc = L.f3dg_residual_join_backward(_stream(), N, Cc, H * W, 1 if ctx.nhwc else 0, _lib.ptr(gy), ctx.scale, _lib.ptr(g), _lib.ptr(gb),
+                                           _lib.ptr(scratch), scratch.numel() * 8 if scratch is not None else 0)
+        _lib.check(rc, "f3dg_residual_join_backward")
+        # (each bias parameter gets a tensor of its own to keep as .grad)
+        return (g if need[0] else None), (gb if need[1] else None), (g if need[2] else None), ((gb.clone() if need[1] else gb) if need[3] else None), None
+
+
 class GroupNorm(nn.Module):
     def __init__(self, num_channels, num_groups=32, min_channels_per_group=4, eps=1e-5):
         super().__init__()
         self.num_groups = min(num_groups, num_channels // min_channels_per_group)
         self.eps = eps
+        self.fused_autograd = False         # set_fused_autograd(): under autograd the HIP forward + backward kernels instead of torch's operators
         self.weight = nn.Parameter(torch.ones(num_channels))
         self.bias = nn.Parameter(torch.zeros(num_channels))
 
     def _fusable(self, x):
-        """Inference on a HIP device in a dtype the kernels take: the fused HIP kernels run (no autograd through them)."""
-        return x.is_cuda and x.dtype in _KERNEL_SUFFIX and x.dim() >= 3 and x.numel() > 0 and self.weight.dtype == torch.float32 and not (
-            torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad))
+        """A HIP device and a dtype the kernels take: the fused HIP kernels run -- in inference always; under autograd only with the
+        ``fused_autograd`` switch on and in float32 (16-bit backbones are inference-only)."""
+        if not (x.is_cuda and x.dtype in _KERNEL_SUFFIX and x.dim() >= 3 and x.numel() > 0 and self.weight.dtype == torch.float32):
+            return False
+        if not (torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad)):
+            return True
+        return self.fused_autograd and x.dtype == torch.float32
 
     def forward(self, x, N_views_xa=1, silu=False, pre_bias=None):
         """``silu=True`` returns ``F.silu(group_norm(x))``: the pair the residual blocks always apply together. In
         inference on a HIP device the pair is ONE fused kernel (``f3dg_group_norm_silu``); with autograd
-        or on the host (the CPU fixtures of the backbone) it is the two PyTorch ops. ``pre_bias`` ([C] float32): the result is
+        or on the host (the CPU fixtures of the backbone) it is the two PyTorch ops -- unless ``fused_autograd`` is set
+        (``set_fused_autograd``), when float32 tensors on a HIP device take the kernels under autograd too, with
+        ``f3dg_group_norm_silu_backward`` behind them. ``pre_bias`` ([C] float32): the result is
         that of ``x + pre_bias[None, :, None, None]`` -- the bias of the convolution that produced ``x`` (``Conv2d.forward(bias=False)``)."""
         if self._fusable(x) and (pre_bias is None or pre_bias.dtype == torch.float32):
+            if self.fused_autograd and x.dtype == torch.float32 and self.bias.dtype == torch.float32 and torch.is_grad_enabled() and any(
+                    t is not None and t.requires_grad for t in (x, pre_bias, self.weight, self.bias)):
+                return _GroupNormSiLU.apply(x, pre_bias, self.weight, self.bias, self.num_groups, float(self.eps), bool(silu))
             L = _lib.lib()
-            if _is_nhwc(x) and x.shape[1] % (4 if x.dtype == torch.float32 else 8) == 0 and x.shape[1] <= 1024 and x.data_ptr() % 16 == 0:
+            if _gn_nhwc_ok(x):
                 # layout option "nhwc": the channels-last kernel, channels-last out
                 y = torch.empty_like(x)           # preserves the strides
                 N, Cc = x.shape[0], x.shape[1]
@@ -182,21 +289,26 @@ class GroupNorm(nn.Module):
         return F.silu(y) if silu else y
 
 
-def residual_join(a, bias_a, b, bias_b, scale):
+def residual_join(a, bias_a, b, bias_b, scale, fused_autograd=False):
     """((a + bias_a) + (b + bias_b)) * scale with per-channel biases (either may be None): the tail of a residual block. One HIP
     kernel (``f3dg_residual_join``) for inference tensors on a HIP device that share a dense layout (NCHW or channels-last); the
-    PyTorch ops otherwise. Writes into ``a``'s storage when it can."""
+    PyTorch ops otherwise. Writes into ``a``'s storage when it can. ``fused_autograd=True``: under autograd float32 tensors take the
+    kernel as well, out of place, with ``f3dg_residual_join_backward`` behind it."""
     def tb(t, bias):
         return t if bias is None else t + bias.to(t.dtype).reshape(1, -1, 1, 1)
+    grad = fused_autograd and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (a, b, bias_a, bias_b))
     ok = (a.is_cuda and a.dim() == 4 and a.dtype in _KERNEL_SUFFIX and b.dtype == a.dtype and a.shape == b.shape
-          and not (torch.is_grad_enabled() and (a.requires_grad or b.requires_grad))
+          and (a.dtype == torch.float32 if grad else not (torch.is_grad_enabled() and (a.requires_grad or b.requires_grad)))
           and all(t is None or (t.dtype == torch.float32 and t.is_contiguous()) for t in (bias_a, bias_b))
           and a.numel() % (4 if a.dtype == torch.float32 else 8) == 0)
     if ok:
         nhwc = _is_nhwc(a)
         same = (_is_nhwc(b) if nhwc else b.is_contiguous()) and (nhwc or a.is_contiguous()) and not (
             nhwc and a.shape[1] % (4 if a.dtype == torch.float32 else 8))
-        if same and (a.data_ptr() | b.data_ptr()) % 16 == 0:
+        if same and (a.data_ptr() | b.data_ptr()) % 16 == 0 and grad:
+            if not (nhwc and a.shape[1] > 1024):        # (the adjoint's channels-last limit)
+                return _ResidualJoin.apply(a, bias_a, b, bias_b, float(scale))
+        elif same and (a.data_ptr() | b.data_ptr()) % 16 == 0:
             N, Cc, H, W = a.shape
             fn = getattr(_lib.lib(), "f3dg_residual_join" + _KERNEL_SUFFIX[a.dtype])
             _lib.check(fn(_stream(), N, Cc, H * W, 1 if nhwc else 0, _lib.ptr(a), _lib.ptr(bias_a), _lib.ptr(b), _lib.ptr(bias_b), float(scale),
@@ -215,6 +327,7 @@ class UNetBlock(nn.Module):
         self.num_heads = 1 if attention else 0
         self.dropout = dropout
         self.skip_scale = math.sqrt(0.5)
+        self.fused_autograd = False         # set_fused_autograd(): the fused route below under autograd and in training mode as well
         self.norm0 = GroupNorm(in_channels, eps=1e-6)
         self.conv0 = Conv2d(in_channels, out_channels, 3, up=up, down=down)
         self.norm1 = GroupNorm(out_channels, eps=1e-6)
@@ -229,17 +342,20 @@ class UNetBlock(nn.Module):
 
     def forward(self, x, emb=None, N_views_xa=1):
         orig = x
-        if self.norm0._fusable(x) and not self.training:
+        if self.norm0._fusable(x) and (self.fused_autograd or not self.training):
             # inference on a HIP device: the three convolutions run without their biases, which go to the kernels that read the results
             # (norm1 takes conv0's; the residual join takes conv1's and the skip convolution's, adds, and scales): same float32
-            # operations in the same order as the lines below, five elementwise passes fewer
+            # operations in the same order as the lines below, five elementwise passes fewer. With the fused_autograd switch the same
+            # route under autograd (float32): the biases get their gradients from those kernels' adjoints
             x = self.conv0(self.norm0(x, silu=True), bias=False)
             x = self.norm1(x, silu=True, pre_bias=self.conv0.bias)
+            if self.training:
+                x = F.dropout(x, p=self.dropout, training=True)
             x = self.conv1(x, bias=False)
             if self.skip is not None:
-                x = residual_join(x, self.conv1.bias, self.skip(orig, bias=False), self.skip.bias, self.skip_scale)
+                x = residual_join(x, self.conv1.bias, self.skip(orig, bias=False), self.skip.bias, self.skip_scale, self.fused_autograd)
             else:
-                x = residual_join(x, self.conv1.bias, orig, None, self.skip_scale)
+                x = residual_join(x, self.conv1.bias, orig, None, self.skip_scale, self.fused_autograd)
         else:
             x = self.conv0(self.norm0(x, silu=True))
             x = self.norm1(x, silu=True)
@@ -262,6 +378,17 @@ class UNetBlock(nn.Module):
             if N_views_xa != 1:
                 x = x.reshape(B // N_views_xa, Cc, N_views_xa, H, W).permute(0, 2, 1, 3, 4).reshape(B, Cc, H, W)
         return x
+
+
+def set_fused_autograd(module, on=True):
+    """Switches every ``GroupNorm`` and ``UNetBlock`` below ``module`` (itself included) between the two backbone routes under autograd:
+    ``on`` = GroupNorm (+ SiLU) and the residual join as HIP kernels forward and backward, the convolutions without their bias passes
+    (float32 on a HIP device; anything else still takes the torch operators); off (the default of a new module) = torch's operators
+    whenever a gradient is wanted. Inference is the fused kernels either way. Returns ``module``."""
+    for mod in module.modules():
+        if isinstance(mod, (GroupNorm, UNetBlock)):
+            mod.fused_autograd = bool(on)
+    return module
 
 
 class SongUNet(nn.Module):
@@ -574,6 +701,14 @@ class GaussianSplatPredictor_gtunet(nn.Module):
         self.backbone_layout = str(m.get('backbone_layout', 'auto'))
         if self.backbone_layout not in ("auto", "nchw", "nhwc"):
             raise ValueError("backbone_layout must be 'auto', 'nchw' or 'nhwc'")
+        # extension: what the backbone's GroupNorm (+ SiLU), bias and residual-join passes run as UNDER AUTOGRAD: "torch" (default) =
+        # torch's operators, as ever; "fused" = the HIP kernels forward and backward (set_fused_autograd: float32 only -- the 16-bit
+        # options stay inference-only), and an explicit backbone_layout "nhwc" is then honoured under autograd too ("auto" stays NCHW)
+        self.backbone_autograd = str(m.get('backbone_autograd', 'torch'))
+        if self.backbone_autograd not in ("torch", "fused"):
+            raise ValueError("backbone_autograd must be 'torch' or 'fused'")
+        if self.backbone_autograd == "fused":
+            set_fused_autograd(self.network_with_offset, True)
         self.init_ray_dirs()
         self.init_sh_transform_matrices()
 
@@ -630,6 +765,8 @@ class GaussianSplatPredictor_gtunet(nn.Module):
             # ("auto": measured crossover -- fp32 25.9 against 26.4 ms at two images, bf16 11.5 against 10.8 at two and 24.2 against 25.4 at eight)
             if inference and (self.backbone_layout == "nhwc" or (self.backbone_layout == "auto" and xc.shape[0] >= (4 if half is not None else 2))):
                 xc = xc.contiguous(memory_format=torch.channels_last)       # (the filters follow per convolution: Conv2d._filter)
+            elif not inference and xc.is_cuda and self.backbone_autograd == "fused" and self.backbone_layout == "nhwc":
+                xc = xc.contiguous(memory_format=torch.channels_last)
             if half is not None:
                 with torch.autocast("cuda", dtype=half):
                     return self.network_with_offset(xc, film_camera_emb=None, N_views_xa=N_views_xa).float()

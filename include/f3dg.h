@@ -514,6 +514,41 @@ int f3dg_residual_join_bf16(void* stream, int N, int C, int HW, int nhwc, const 
                             const float* bias_b, float scale, uint16_t* y);
 int f3dg_residual_join_f16(void* stream, int N, int C, int HW, int nhwc, const uint16_t* a, const float* bias_a, const uint16_t* b,
                            const float* bias_b, float scale, uint16_t* y);
+/* Training through the backbone: the adjoints of the float32 kernels above, both layouts (nhwc = 0: [N,C,HW]; nhwc = 1: [N,HW,C]).
+ *
+ * f3dg_group_norm_silu_stats is the float32 forward (the same kernels and the same y as f3dg_group_norm_silu_pb / _nhwc_pb) that also
+ * keeps its statistics: stats [N, groups, 2] float32 = (mean, 1 / sqrt(var + eps)) per (sample, group), 8-byte aligned. `moments` /
+ * `moments_bytes` are the channels-last scratch (f3dg_group_norm_nhwc_scratch_bytes); with nhwc = 0 they are unused and may be NULL / 0.
+ *
+ * f3dg_group_norm_silu_backward recomputes everything else from x. With v = x + pre_bias, xh = (v - mean) * rstd, z = weight * xh + bias
+ * (formed as the forward forms it: the mean taken off before the scale), m = (C / groups) * HW:
+ *   dz = grad_y * s * (1 + z * (1 - s)), s = sigmoid(z)   (apply_silu != 0; dz = grad_y otherwise)
+ *   A[n, c] = sum_hw dz,  B[n, c] = sum_hw dz * xh,  s1[n, g] = sum_c weight[c] A / m,  s2[n, g] = sum_c weight[c] B / m
+ *   grad_x = rstd * (dz * weight - s1 - xh * s2)             [as x]
+ *   grad_weight[c] = sum_n B,  grad_bias[c] = sum_n A,  grad_pre_bias[c] = sum_{n, hw} grad_x      [C] each
+ * Any of the four outputs may be NULL (not wanted); the others are overwritten, not accumulated into. Every sum is taken in float32 over
+ * short runs and combined in float64 in a fixed order, without atomics: the gradients are bit-identical from run to run. pre_bias may be
+ * NULL. `scratch`: f3dg_group_norm_silu_backward_scratch_bytes(N, C, HW, groups, nhwc) bytes, 8-byte aligned (the per-(sample, channel)
+ * sums, the (s1, s2) pairs and, channels-last, a triple per workgroup and channel).
+ * Refused as the forward refuses, before anything is written: F3DG_ERR_BAD_ARG for a NULL x / weight / bias / stats / grad_y / scratch,
+ * groups that do not divide C, x / grad_y / grad_x not 16-byte aligned, channels-last C that is no multiple of 4 or above 1024;
+ * F3DG_ERR_WORKSPACE for scratch_bytes below the size above. N == 0: F3DG_OK and no work. */
+int f3dg_group_norm_silu_stats(void* stream, int N, int C, int HW, int groups, int nhwc, const float* x, const float* pre_bias,
+                               const float* weight, const float* bias, float eps, int apply_silu, float* y, float* stats,
+                               double* moments, size_t moments_bytes);
+size_t f3dg_group_norm_silu_backward_scratch_bytes(int N, int C, int HW, int groups, int nhwc);
+int f3dg_group_norm_silu_backward(void* stream, int N, int C, int HW, int groups, int nhwc, const float* x, const float* pre_bias,
+                                  const float* weight, const float* bias, const float* stats, int apply_silu, const float* grad_y,
+                                  float* grad_x, float* grad_weight, float* grad_bias, float* grad_pre_bias, void* scratch,
+                                  size_t scratch_bytes);
+/* The adjoint of f3dg_residual_join in ONE pass over grad_y: grad_ab = grad_y * scale [as grad_y], which is the gradient of a and of b
+ * alike, and grad_bias[c] = the sum of grad_ab over channel c ([C], the gradient of either bias; NULL = not wanted), summed in float64 in
+ * a fixed order without atomics. grad_ab may be grad_y. `scratch` (needed only with grad_bias): f3dg_residual_join_backward_scratch_bytes
+ * bytes, 8-byte aligned; less is F3DG_ERR_WORKSPACE. F3DG_ERR_BAD_ARG as the forward: N*C*HW no multiple of 4, pointers not 16-byte
+ * aligned, channels-last C no multiple of 4 (or above 1024). N == 0: F3DG_OK and no work. */
+size_t f3dg_residual_join_backward_scratch_bytes(int N, int C, int HW, int nhwc);
+int f3dg_residual_join_backward(void* stream, int N, int C, int HW, int nhwc, const float* grad_y, float scale, float* grad_ab,
+                                float* grad_bias, void* scratch, size_t scratch_bytes);
 
 /* Fused differentiable image loss: SSIM (+ L1, L2) of n_planes pairs of H x W planes -- a plane is one channel of one frame; img1, img2
  * and every plane set below are float32, planar and contiguous, [n_planes, H, W].
