@@ -237,7 +237,7 @@ int f3dg_set_hip_error(hipError_t e, const char* where)
     return F3DG_ERR_HIP;
 }
 
-extern "C" const char* f3dg_version(void) { return "f3dg-hip gfx950 0.2.0"; }
+extern "C" const char* f3dg_version(void) { return "f3dg-hip gfx950 0.3.0"; }
 extern "C" const char* f3dg_last_error(void) { return g_last_error; }
 
 int f3dg_sort_passes(int V, int T);

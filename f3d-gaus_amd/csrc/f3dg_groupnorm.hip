@@ -1,8 +1,8 @@
 // f3dg_groupnorm.hip -- what the SongUNet backbone of the predictor needs between MIOpen's convolutions:
-//   * fused GroupNorm (+ SiLU), NCHW and channels-last, float32 and bfloat16 activations, optionally with the bias of the convolution
-//     that produced the input folded in (f3dg_group_norm_silu*, reference src/gaussian_predictor.py:250-262 GroupNorm, :318-323
-//     `silu(norm(x))`);
-//   * the residual join of a block (f3dg_residual_join, :325-327): second convolution's bias + skip path (+ its bias) + skip_scale.
+//   * fused GroupNorm (+ SiLU), NCHW and channels-last, float32, bfloat16 and float16 activations, optionally with the bias of the
+//     convolution that produced the input folded in (f3dg_group_norm_silu_forward, reference src/gaussian_predictor.py:250-262 GroupNorm,
+//     :318-323 `silu(norm(x))`);
+//   * the residual join of a block (f3dg_residual_join_forward, :325-327): second convolution's bias + skip path (+ its bias) + skip_scale.
 //
 // The backbone calls GroupNorm 78 times per pass, each followed by SiLU in the residual blocks. On PyTorch-ROCm that is three
 // bandwidth-bound kernels per call (row moments, scale/shift, silu: five passes over the tensor); the NCHW kernel is ONE:
@@ -51,7 +51,7 @@ group_norm_silu_kernel(int C, int HW, int groups, const T* __restrict__ x, const
     for (size_t i = threadIdx.x; i < np; i += GN_THREADS) {
         Packet<T> p;
         p.load(xs + i * PN);
-        const float pb = pre_bias ? pre_bias[g * Cg + (idx32 ? (int)((unsigned)i / (unsigned)hwp) : (int)(i / hwp))] : 0.0f;
+        const float pb = pre_bias ? pre_bias[g * Cg + gn_nchw_chan(i, hwp, idx32)] : 0.0f;
         float a = 0.0f, b = 0.0f;
 #pragma unroll
         for (int k = 0; k < PN; k++) { const float v = (p.v[k] + pb) - K; a += v; b = __builtin_fmaf(v, v, b); }      // (the fused multiply-add pays for the subtraction)
@@ -59,14 +59,11 @@ group_norm_silu_kernel(int C, int HW, int groups, const T* __restrict__ x, const
         s2 += (double)b;
     }
     for (size_t i = np * PN + threadIdx.x; i < slab; i += GN_THREADS) {
-        const float v = (to_f32(xs[i]) + (pre_bias ? pre_bias[g * Cg + (idx32 ? (int)((unsigned)i / (unsigned)HW) : (int)(i / HW))] : 0.0f)) - K;
+        const float v = (to_f32(xs[i]) + (pre_bias ? pre_bias[g * Cg + gn_nchw_chan(i, HW, idx32)] : 0.0f)) - K;
         s1 += v; s2 += (double)(v * v);
     }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        s1 += __shfl_xor(s1, m, 64);
-        s2 += __shfl_xor(s2, m, 64);
-    }
+    s1 = gn_wave_sum(s1);
+    s2 = gn_wave_sum(s2);
     __shared__ double w1[GN_THREADS / 64], w2[GN_THREADS / 64];
     __shared__ float s_mean, s_rstd;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -83,20 +80,17 @@ group_norm_silu_kernel(int C, int HW, int groups, const T* __restrict__ x, const
         if (stats_out) stats_out[blockIdx.x] = make_float2(s_mean, s_rstd);       // [n][g]: what the backward (f3dg_groupnorm_bwd.hip) normalises with
     }
     __syncthreads();
-    const float mean = s_mean, rstd = s_rstd;
+    const float2 st = make_float2(s_mean, s_rstd);
 
     // ---- normalise, affine, (silu): the slab is re-read from L2
     if (vec) {
         for (size_t i = threadIdx.x; i < np; i += GN_THREADS) {
-            const int c = g * Cg + (idx32 ? (int)((unsigned)i / (unsigned)hwp) : (int)(i / hwp));
-            const float pb = (pre_bias ? pre_bias[c] : 0.0f) - mean;            // (x + pre_bias) - mean as x + (pre_bias - mean): see above
-            const float sc = weight[c] * rstd;
-            const float sh = bias[c];
+            const GnChan ch = gn_chan(g * Cg + gn_nchw_chan(i, hwp, idx32), st, pre_bias, weight, bias);
             Packet<T> p;
             p.load(xs + i * PN);
 #pragma unroll
             for (int k = 0; k < PN; k++) {
-                float v = (p.v[k] + pb) * sc + sh;
+                float v = gn_z(p.v[k], ch);
                 if (apply_silu) v = silu_of<T>(v);
                 p.v[k] = v;
             }
@@ -104,27 +98,11 @@ group_norm_silu_kernel(int C, int HW, int groups, const T* __restrict__ x, const
         }
     } else {
         for (size_t i = threadIdx.x; i < slab; i += GN_THREADS) {
-            const int c = g * Cg + (idx32 ? (int)((unsigned)i / (unsigned)HW) : (int)(i / HW));
-            const float pb = (pre_bias ? pre_bias[c] : 0.0f) - mean;
-            const float sc = weight[c] * rstd;
-            float v = (to_f32(xs[i]) + pb) * sc + bias[c];
+            float v = gn_z(to_f32(xs[i]), gn_chan(g * Cg + gn_nchw_chan(i, HW, idx32), st, pre_bias, weight, bias));
             if (apply_silu) v = silu_of<T>(v);
             from_f32(ys[i], v);
         }
     }
-}
-
-template <typename T>
-int launch_gn(void* stream, int N, int C, int HW, int groups, const T* x, const float* pre_bias, const float* weight, const float* bias, float eps,
-              int apply_silu, T* y, float2* stats_out = nullptr)
-{
-    if (N < 0 || C <= 0 || HW <= 0 || groups <= 0 || C % groups != 0 || !x || !weight || !bias || !y) return F3DG_ERR_BAD_ARG;
-    if (N == 0) return F3DG_OK;
-    if (((uintptr_t)x | (uintptr_t)y) & 15u) return F3DG_ERR_BAD_ARG;       // 16-byte loads / stores
-    F3DG_KLAUNCH(group_norm_silu_kernel<T>, dim3((unsigned)(N * groups)), dim3(GN_THREADS), 0, (hipStream_t)stream, C, HW,
-                       groups, x, pre_bias, weight, bias, eps, apply_silu, y, stats_out);
-    F3DG_HIP_CHECK(hipGetLastError());
-    return F3DG_OK;
 }
 
 // ---- channels-last (NHWC) variant ---------------------------------------------------------------------------------------------------
@@ -132,12 +110,12 @@ int launch_gn(void* stream, int N, int C, int HW, int groups, const T* x, const 
 // (15 % of a bf16 pass of the backbone, profiles/r04_final/unet.md), and torch's GroupNorm converts a channels_last tensor back, so the
 // layout only pays if GroupNorm keeps it. x is [N][HW][C]: a group's Cg channels are 8..64 bytes of every pixel's C-vector, so a
 // workgroup takes a run of pixels with ALL channels (whole lines), and the moments of a (sample, group) are summed across workgroups:
-//   gn_nhwc_moments_kernel: thread (row, col) owns the 16-byte packet `col` of the pixels row, row + rows, ...: float sums per channel
-//       over at most gn_nhwc_pix(HW) / rows pixels, per-channel totals over the rows in LDS, per-group totals in float64 written to
-//       partial[n][g][block] = (sum, sum of squares); gn_nhwc_finish_kernel adds the blocks in order -> (mean, rstd) per (sample, group);
-//   gn_nhwc_apply_kernel: the same mapping; scale / shift of the thread's PN channels once, then one pass: silu((x + pre_bias) * sc + sh).
+//   gn_nhwc_moments_kernel: the walk of f3dg_groupnorm.h (thread (row, col) owns the 16-byte packet `col` of the pixels row, row + rows,
+//       ...): float sums per channel over at most gn_nhwc_pix(HW) / rows pixels, per-channel totals over the rows in LDS, per-group totals
+//       in float64 written to partial[n][g][block] = (sum, sum of squares); gn_nhwc_finish_kernel adds the blocks in order -> (mean, rstd)
+//       per (sample, group);
+//   gn_nhwc_apply_kernel: the same walk; the constants of the thread's PN channels once, then one pass: silu(gn_z(x)).
 // Two reads (the second from L2 / MALL) and one write, as the NCHW kernel.
-
 
 // the pivot of (sample n, group g): the first value of the slab, as the moments and the finish kernel both read it
 template <typename T>
@@ -151,11 +129,8 @@ __global__ void __launch_bounds__(256)
 gn_nhwc_moments_kernel(int C, int HW, int groups, int rows, const T* __restrict__ x, const float* __restrict__ pre_bias, double* __restrict__ moments)
 {
     constexpr int PN = Packet<T>::N;
-    const int ppp = C / PN;                                   // packets per pixel
-    const int col = threadIdx.x % ppp, row = threadIdx.x / ppp;
-    const int n = blockIdx.y;
-    const int p0 = blockIdx.x * gn_nhwc_pix(HW);
-    const int p1 = min(p0 + gn_nhwc_pix(HW), HW);
+    const GnNhwcRun r = gn_nhwc_run<PN>(C, HW);
+    const int col = r.col, row = r.row, n = r.n;
     const int Cg = C / groups;
     float a[PN], b[PN], pb[PN];
 #pragma unroll
@@ -164,48 +139,29 @@ gn_nhwc_moments_kernel(int C, int HW, int groups, int rows, const T* __restrict_
         // K = gn_nhwc_pivot of each of the thread's channels' group (pixel 0 of the sample, first channel of the group): the sums are of (x + pb) - K
         // KP pivots per packet: 1 (the packet inside one group, Cg a multiple of PN), 2 (two whole groups: Cg = 4 and 8-wide packets, the
         // 16-bit backbone's 128-channel layers) or PN (any other Cg: a pivot is loaded where the packet enters a group). Chosen by the
-        // launch: a thread has as few as 8 trips of the loop below to spread this set-up over
+        // launch: a thread has as few as 8 trips of the walk to spread this set-up over
         float K[KP];
         if constexpr (KP < PN) {
             const int g = KP == 1 ? (col * PN) / Cg : col * KP;
 #pragma unroll
             for (int j = 0; j < KP; j++) K[j] = gn_nhwc_pivot(x, pre_bias, n, C, HW, Cg, g + j);
         } else {
-            int g = (col * PN) / Cg, r = col * PN - g * Cg;
+            int g = (col * PN) / Cg, rr = col * PN - g * Cg;
             float Kg = gn_nhwc_pivot(x, pre_bias, n, C, HW, Cg, g);
 #pragma unroll
             for (int k = 0; k < PN; k++) {
                 K[k] = Kg;
-                if (++r == Cg && k + 1 < PN) { r = 0; g++; Kg = gn_nhwc_pivot(x, pre_bias, n, C, HW, Cg, g); }
+                if (++rr == Cg && k + 1 < PN) { rr = 0; g++; Kg = gn_nhwc_pivot(x, pre_bias, n, C, HW, Cg, g); }
             }
         }
-        const T* xs = x + ((size_t)n * HW) * C + (size_t)col * PN;
-        for (int p = p0 + row; p < p1; p += rows * GN_NHWC_UNROLL) {
-            Packet<T> q[GN_NHWC_UNROLL];
+        const T* const in[1] = { x + ((size_t)n * HW) * C + (size_t)col * PN };
+        gn_nhwc_walk(r, rows, C, in, [&](const Packet<T> (&q)[1], size_t) {
 #pragma unroll
-            for (int u = 0; u < GN_NHWC_UNROLL; u++)
-                if (p + u * rows < p1) q[u].load(xs + (size_t)(p + u * rows) * C);
-#pragma unroll
-            for (int u = 0; u < GN_NHWC_UNROLL; u++)
-                if (p + u * rows < p1) {
-#pragma unroll
-                    for (int k = 0; k < PN; k++) { const float v = (q[u].v[k] + pb[k]) - K[k * KP / PN]; a[k] += v; b[k] = __builtin_fmaf(v, v, b[k]); }
-                }
-        }
+            for (int k = 0; k < PN; k++) { const float v = (q[0].v[k] + pb[k]) - K[k * KP / PN]; a[k] += v; b[k] = __builtin_fmaf(v, v, b[k]); }
+        });
     }
-    // per-channel totals over the rows: every (row, channel) has its own LDS word (rows * C <= 256 * PN), channel c is summed by thread c
-    __shared__ float sa[256 * PN], sb[256 * PN];
-    if (row < rows) {
-#pragma unroll
-        for (int k = 0; k < PN; k++) { sa[row * C + col * PN + k] = a[k]; sb[row * C + col * PN + k] = b[k]; }
-    }
-    __syncthreads();
     __shared__ float ca[GN_NHWC_MAXC], cb[GN_NHWC_MAXC];
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        float t1 = 0.0f, t2 = 0.0f;
-        for (int r = 0; r < rows; r++) { t1 += sa[r * C + c]; t2 += sb[r * C + c]; }
-        ca[c] = t1; cb[c] = t2;
-    }
+    gn_rows_to_channels<float>(C, rows, row, col, [&](int c, const float (&t)[2]) { ca[c] = t[0]; cb[c] = t[1]; }, a, b);
     __syncthreads();
     // per-group totals in float64, one (sum, sum of squares) pair per WORKGROUP: partial[n][g][block]. No atomics -- the second stage
     // (gn_nhwc_finish_kernel) adds a sample's blocks up in block order, so the statistics, and with them the whole backbone pass, are
@@ -238,11 +194,8 @@ gn_nhwc_finish_kernel(int N, int C, int HW, int groups, int nb, double cnt, floa
         const double* p = partial + 2 * (((size_t)n * groups + g) * nb + b);
         m1 += p[0]; m2 += p[1];
     }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        m1 += __shfl_xor(m1, m, 64);
-        m2 += __shfl_xor(m2, m, 64);
-    }
+    m1 = gn_wave_sum(m1);
+    m2 = gn_wave_sum(m2);
     if (lane == 0) {
         const double d = m1 / cnt;                                // mean - K: the partials are sums of v - K
         double var = m2 / cnt - d * d;
@@ -257,58 +210,42 @@ gn_nhwc_apply_kernel(int C, int HW, int groups, int rows, const T* __restrict__ 
                      const float* __restrict__ weight, const float* __restrict__ bias, int apply_silu, T* __restrict__ y)
 {
     constexpr int PN = Packet<T>::N;
-    const int ppp = C / PN;
-    const int col = threadIdx.x % ppp, row = threadIdx.x / ppp;
-    if (row >= rows) return;
-    const int n = blockIdx.y;
-    const int p0 = blockIdx.x * gn_nhwc_pix(HW);
-    const int p1 = min(p0 + gn_nhwc_pix(HW), HW);
-    const int Cg = C / groups;
-    float sc[PN], sh[PN], pb[PN];
+    const GnNhwcRun r = gn_nhwc_run<PN>(C, HW);
+    if (r.row >= rows) return;
+    GnChan ch[PN];
+    gn_nhwc_chan(ch, r, C / groups, groups, pre_bias, weight, bias, stats);
+    const size_t base = ((size_t)r.n * HW) * C + (size_t)r.col * PN;
+    const T* const in[1] = { x + base };
+    gn_nhwc_walk(r, rows, C, in, [&](Packet<T> (&q)[1], size_t off) {
 #pragma unroll
-    for (int k = 0; k < PN; k++) {
-        const int c = col * PN + k;
-        const float2 st = stats[(size_t)n * groups + c / Cg];        // (mean, rstd)
-        sc[k] = weight[c] * st.y;
-        sh[k] = bias[c];
-        pb[k] = (pre_bias ? pre_bias[c] : 0.0f) - st.x;              // pre_bias - mean
-    }
-    const size_t base = ((size_t)n * HW) * C + (size_t)col * PN;
-    for (int p = p0 + row; p < p1; p += rows * GN_NHWC_UNROLL) {
-        Packet<T> q[GN_NHWC_UNROLL];
-#pragma unroll
-        for (int u = 0; u < GN_NHWC_UNROLL; u++)
-            if (p + u * rows < p1) q[u].load(x + base + (size_t)(p + u * rows) * C);
-#pragma unroll
-        for (int u = 0; u < GN_NHWC_UNROLL; u++)
-            if (p + u * rows < p1) {
-#pragma unroll
-                for (int k = 0; k < PN; k++) {
-                    float v = (q[u].v[k] + pb[k]) * sc[k] + sh[k];
-                    if (apply_silu) v = silu_of<T>(v);
-                    q[u].v[k] = v;
-                }
-                q[u].store(y + base + (size_t)(p + u * rows) * C);
-            }
-    }
+        for (int k = 0; k < PN; k++) {
+            float v = gn_z(q[0].v[k], ch[k]);
+            if (apply_silu) v = silu_of<T>(v);
+            q[0].v[k] = v;
+        }
+        q[0].store(y + base + off);
+    });
 }
 
-extern "C" size_t f3dg_group_norm_nhwc_scratch_bytes(int N, int HW, int groups);
-
 template <typename T>
-int launch_gn_nhwc(void* stream, int N, int C, int HW, int groups, const T* x, const float* pre_bias, const float* weight, const float* bias, float eps,
-                   int apply_silu, T* y, double* moments, size_t moments_bytes, float2* stats_out = nullptr)
+int launch_gn(void* stream, int nhwc, int N, int C, int HW, int groups, const void* x_, const float* pre_bias, const float* weight, const float* bias,
+              float eps, int apply_silu, void* y_, float2* stats_out, void* scratch, size_t scratch_bytes)
 {
     constexpr int PN = Packet<T>::N;
-    if (N < 0 || C <= 0 || HW <= 0 || groups <= 0 || C % groups != 0 || !x || !weight || !bias || !y || !moments) return F3DG_ERR_BAD_ARG;
-    // the scratch grew when the statistics became atomics-free (round 5: a partial pair per workgroup): the caller says how much it
-    // handed over, an allocation sized by an older header is refused instead of being written past its end
-    if (N > 0 && moments_bytes < f3dg_group_norm_nhwc_scratch_bytes(N, HW, groups)) return F3DG_ERR_WORKSPACE;
-    if (C % PN != 0 || C / PN > 256 || C > GN_NHWC_MAXC) return F3DG_ERR_BAD_ARG;   // whole 16-byte packets per pixel, one packet column per thread
-    if (N == 0) return F3DG_OK;
-    if (((uintptr_t)x | (uintptr_t)y) & 15u) return F3DG_ERR_BAD_ARG;
-    const int ppp = C / PN, rows = 256 / ppp;
+    const T* x = static_cast<const T*>(x_);
+    T* y = static_cast<T*>(y_);
+    const int rc = gn_check_args(N, C, HW, groups, nhwc, PN, x && weight && bias && y && (!nhwc || scratch), scratch_bytes,
+                                 nhwc ? f3dg_group_norm_nhwc_scratch_bytes(N, HW, groups) : 0, (uintptr_t)x | (uintptr_t)y, 0);
+    if (rc != F3DG_OK || N == 0) return rc;
     hipStream_t s = (hipStream_t)stream;
+    if (!nhwc) {
+        F3DG_KLAUNCH(group_norm_silu_kernel<T>, dim3((unsigned)(N * groups)), dim3(GN_THREADS), 0, s, C, HW, groups, x, pre_bias, weight, bias, eps,
+                     apply_silu, y, stats_out);
+        F3DG_HIP_CHECK(hipGetLastError());
+        return F3DG_OK;
+    }
+    double* moments = static_cast<double*>(scratch);
+    const int ppp = C / PN, rows = 256 / ppp;
     const int nb = (HW + gn_nhwc_pix(HW) - 1) / gn_nhwc_pix(HW);
     // (mean, rstd) per (sample, group): behind the partials, or where the caller keeps them for the backward
     float2* stats = stats_out ? stats_out : reinterpret_cast<float2*>(moments + 2 * (size_t)N * nb * groups);
@@ -385,9 +322,12 @@ residual_join_kernel(size_t n_packets, int C, int HW, int nhwc, int packet_in_ch
 }
 
 template <typename T>
-int launch_join(void* stream, int N, int C, int HW, int nhwc, const T* a, const float* bias_a, const T* b, const float* bias_b, float scale, T* y)
+int launch_join(void* stream, int nhwc, int N, int C, int HW, const void* a_, const float* bias_a, const void* b_, const float* bias_b, float scale, void* y_)
 {
     constexpr int PN = Packet<T>::N;
+    const T* a = static_cast<const T*>(a_);
+    const T* b = static_cast<const T*>(b_);
+    T* y = static_cast<T*>(y_);
     if (N < 0 || C <= 0 || HW <= 0 || !a || !b || !y) return F3DG_ERR_BAD_ARG;
     const size_t total = (size_t)N * C * HW;
     if (total == 0) return F3DG_OK;
@@ -409,26 +349,7 @@ int launch_join(void* stream, int N, int C, int HW, int nhwc, const T* a, const 
 
 } // namespace
 
-extern "C" int f3dg_residual_join(void* stream, int N, int C, int HW, int nhwc, const float* a, const float* bias_a, const float* b,
-                                  const float* bias_b, float scale, float* y)
-{
-    return launch_join<float>(stream, N, C, HW, nhwc, a, bias_a, b, bias_b, scale, y);
-}
-
-extern "C" int f3dg_residual_join_bf16(void* stream, int N, int C, int HW, int nhwc, const uint16_t* a, const float* bias_a, const uint16_t* b,
-                                       const float* bias_b, float scale, uint16_t* y)
-{
-    return launch_join<unsigned short>(stream, N, C, HW, nhwc, a, bias_a, b, bias_b, scale, y);
-}
-
-extern "C" int f3dg_residual_join_f16(void* stream, int N, int C, int HW, int nhwc, const uint16_t* a, const float* bias_a, const uint16_t* b,
-                                      const float* bias_b, float scale, uint16_t* y)
-{
-    return launch_join<_Float16>(stream, N, C, HW, nhwc, reinterpret_cast<const _Float16*>(a), bias_a, reinterpret_cast<const _Float16*>(b), bias_b, scale,
-                                 reinterpret_cast<_Float16*>(y));
-}
-
-// bytes of the `moments` scratch of the channels-last GroupNorm: the workgroups' partial sums + the (mean, rstd) pairs
+// bytes of the scratch of the channels-last GroupNorm: the workgroups' partial sums + the (mean, rstd) pairs
 extern "C" size_t f3dg_group_norm_nhwc_scratch_bytes(int N, int HW, int groups)
 {
     if (N <= 0 || HW <= 0 || groups <= 0) return 0;
@@ -436,78 +357,21 @@ extern "C" size_t f3dg_group_norm_nhwc_scratch_bytes(int N, int HW, int groups)
     return sizeof(double) * 2 * (size_t)N * nb * groups + sizeof(float2) * (size_t)N * groups;
 }
 
-// The float32 forward that keeps its statistics: stats [N][groups] (mean, rstd), the pair f3dg_group_norm_silu_backward normalises with.
-// nhwc = 0: the NCHW kernel (moments unused, may be null); nhwc = 1: the channels-last kernels. Same kernels, same y as the entries below.
-extern "C" int f3dg_group_norm_silu_stats(void* stream, int N, int C, int HW, int groups, int nhwc, const float* x, const float* pre_bias,
-                                          const float* weight, const float* bias, float eps, int apply_silu, float* y, float* stats,
-                                          double* moments, size_t moments_bytes)
+// 16-bit activations travel as unsigned short (bfloat16) or _Float16
+extern "C" int f3dg_group_norm_silu_forward(void* stream, int dtype, int nhwc, int N, int C, int HW, int groups, const void* x, const float* pre_bias,
+                                            const float* weight, const float* bias, float eps, int apply_silu, void* y, float* stats, void* scratch,
+                                            size_t scratch_bytes)
 {
-    if (!stats || ((uintptr_t)stats & 7u)) return F3DG_ERR_BAD_ARG;
-    if (nhwc)
-        return launch_gn_nhwc<float>(stream, N, C, HW, groups, x, pre_bias, weight, bias, eps, apply_silu, y, moments, moments_bytes, reinterpret_cast<float2*>(stats));
-    return launch_gn<float>(stream, N, C, HW, groups, x, pre_bias, weight, bias, eps, apply_silu, y, reinterpret_cast<float2*>(stats));
+    // the statistics are kept for the backward, which is float32 only
+    if (dtype < F3DG_F32 || dtype > F3DG_F16 || (stats && (dtype != F3DG_F32 || ((uintptr_t)stats & 7u)))) return F3DG_ERR_BAD_ARG;
+    const auto launch = dtype == F3DG_F32 ? launch_gn<float> : dtype == F3DG_BF16 ? launch_gn<unsigned short> : launch_gn<_Float16>;
+    return launch(stream, nhwc, N, C, HW, groups, x, pre_bias, weight, bias, eps, apply_silu, y, reinterpret_cast<float2*>(stats), scratch, scratch_bytes);
 }
 
-// GroupNorm (+ SiLU) with the producing convolution's bias folded in (pre_bias, nullable): NCHW ...
-extern "C" int f3dg_group_norm_silu_pb(void* stream, int N, int C, int HW, int groups, const float* x, const float* pre_bias, const float* weight,
-                                       const float* bias, float eps, int apply_silu, float* y)
+extern "C" int f3dg_residual_join_forward(void* stream, int dtype, int nhwc, int N, int C, int HW, const void* a, const float* bias_a, const void* b,
+                                          const float* bias_b, float scale, void* y)
 {
-    return launch_gn<float>(stream, N, C, HW, groups, x, pre_bias, weight, bias, eps, apply_silu, y);
-}
-
-extern "C" int f3dg_group_norm_silu_pb_bf16(void* stream, int N, int C, int HW, int groups, const uint16_t* x, const float* pre_bias, const float* weight,
-                                            const float* bias, float eps, int apply_silu, uint16_t* y)
-{
-    return launch_gn<unsigned short>(stream, N, C, HW, groups, x, pre_bias, weight, bias, eps, apply_silu, y);
-}
-
-extern "C" int f3dg_group_norm_silu_pb_f16(void* stream, int N, int C, int HW, int groups, const uint16_t* x, const float* pre_bias, const float* weight,
-                                           const float* bias, float eps, int apply_silu, uint16_t* y)
-{
-    return launch_gn<_Float16>(stream, N, C, HW, groups, reinterpret_cast<const _Float16*>(x), pre_bias, weight, bias, eps, apply_silu, reinterpret_cast<_Float16*>(y));
-}
-
-// ... and channels-last
-extern "C" int f3dg_group_norm_silu_nhwc_pb_f16(void* stream, int N, int C, int HW, int groups, const uint16_t* x, const float* pre_bias,
-                                                const float* weight, const float* bias, float eps, int apply_silu, uint16_t* y, double* moments, size_t moments_bytes)
-{
-    return launch_gn_nhwc<_Float16>(stream, N, C, HW, groups, reinterpret_cast<const _Float16*>(x), pre_bias, weight, bias, eps, apply_silu,
-                                    reinterpret_cast<_Float16*>(y), moments, moments_bytes);
-}
-
-extern "C" int f3dg_group_norm_silu_nhwc_pb(void* stream, int N, int C, int HW, int groups, const float* x, const float* pre_bias, const float* weight,
-                                            const float* bias, float eps, int apply_silu, float* y, double* moments, size_t moments_bytes)
-{
-    return launch_gn_nhwc<float>(stream, N, C, HW, groups, x, pre_bias, weight, bias, eps, apply_silu, y, moments, moments_bytes);
-}
-
-extern "C" int f3dg_group_norm_silu_nhwc_pb_bf16(void* stream, int N, int C, int HW, int groups, const uint16_t* x, const float* pre_bias,
-                                                 const float* weight, const float* bias, float eps, int apply_silu, uint16_t* y, double* moments, size_t moments_bytes)
-{
-    return launch_gn_nhwc<unsigned short>(stream, N, C, HW, groups, x, pre_bias, weight, bias, eps, apply_silu, y, moments, moments_bytes);
-}
-
-// GroupNorm (+ SiLU) of a channels-last tensor, x and y [N][HW][C]; `moments` is scratch of f3dg_group_norm_nhwc_scratch_bytes(N, HW, groups) bytes
-extern "C" int f3dg_group_norm_silu_nhwc(void* stream, int N, int C, int HW, int groups, const float* x, const float* weight,
-                                         const float* bias, float eps, int apply_silu, float* y, double* moments, size_t moments_bytes)
-{
-    return launch_gn_nhwc<float>(stream, N, C, HW, groups, x, nullptr, weight, bias, eps, apply_silu, y, moments, moments_bytes);
-}
-
-extern "C" int f3dg_group_norm_silu_nhwc_bf16(void* stream, int N, int C, int HW, int groups, const uint16_t* x, const float* weight,
-                                              const float* bias, float eps, int apply_silu, uint16_t* y, double* moments, size_t moments_bytes)
-{
-    return launch_gn_nhwc<unsigned short>(stream, N, C, HW, groups, x, nullptr, weight, bias, eps, apply_silu, y, moments, moments_bytes);
-}
-
-extern "C" int f3dg_group_norm_silu(void* stream, int N, int C, int HW, int groups, const float* x, const float* weight,
-                                    const float* bias, float eps, int apply_silu, float* y)
-{
-    return launch_gn<float>(stream, N, C, HW, groups, x, nullptr, weight, bias, eps, apply_silu, y);
-}
-
-extern "C" int f3dg_group_norm_silu_bf16(void* stream, int N, int C, int HW, int groups, const uint16_t* x, const float* weight,
-                                         const float* bias, float eps, int apply_silu, uint16_t* y)
-{
-    return launch_gn<unsigned short>(stream, N, C, HW, groups, x, nullptr, weight, bias, eps, apply_silu, y);
+    if (dtype < F3DG_F32 || dtype > F3DG_F16) return F3DG_ERR_BAD_ARG;
+    const auto launch = dtype == F3DG_F32 ? launch_join<float> : dtype == F3DG_BF16 ? launch_join<unsigned short> : launch_join<_Float16>;
+    return launch(stream, nhwc, N, C, HW, a, bias_a, b, bias_b, scale, y);
 }

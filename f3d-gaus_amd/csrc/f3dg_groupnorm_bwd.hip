@@ -7,8 +7,8 @@
 //   s1[n][g] = sum_c weight[c] A / m,  s2[n][g] = sum_c weight[c] B / m
 //   dx = rstd * (dz * weight - s1 - xh * s2)
 //   dweight[c] = sum_n B,  dbias[c] = sum_n A,  dpre_bias[c] = sum_{n, hw} dx = sum_n rstd * (weight[c] A - HW s1 - s2 X)
-// (mean, rstd) are the forward's own, kept by f3dg_group_norm_silu_stats; z is formed with the forward's operations --
-// (x + (pre_bias - mean)) * (weight * rstd) + bias -- and the sigmoid with the forward's expf and IEEE division. Every sum is taken in
+// (mean, rstd) are the forward's own, kept by f3dg_group_norm_silu_forward; z is formed by the forward's own function from the forward's
+// own constants (gn_z, gn_chan of f3dg_groupnorm.h) and the sigmoid with the forward's expf and IEEE division. Every sum is taken in
 // float32 over short runs (a packet in NCHW, a thread's pixels of a run channels-last, as the forward's moments) and combined in float64
 // in a fixed order: no floating-point atomics anywhere, the gradients are bit-identical from run to run.
 // Nothing but x is needed from the forward: neither its output nor the normalised pre-activation is kept.
@@ -17,14 +17,13 @@
 
 namespace {
 
-// dz and xh of one element. pbm = pre_bias - mean, sc = weight * rstd, sh = bias: the forward's own scale / shift
-__device__ __forceinline__ void gn_bwd_elem(float x, float dy, float pbm, float rstd, float sc, float sh, int apply_silu, float& dz, float& xh)
+// dz and xh of one element
+__device__ __forceinline__ void gn_bwd_elem(float x, float dy, const GnChan& ch, int apply_silu, float& dz, float& xh)
 {
-    const float d = x + pbm;
-    xh = d * rstd;
+    xh = (x + ch.pbm) * ch.rstd;
     dz = dy;
     if (apply_silu) {
-        const float z = d * sc + sh;
+        const float z = gn_z(x, ch);
         const float s = 1.0f / (1.0f + expf(-z));
         dz = dy * (s * (1.0f + z * (1.0f - s)));
     }
@@ -52,7 +51,7 @@ gn_bwd_nchw_kernel(int C, int HW, int groups, const float* __restrict__ x, const
     const int n = blockIdx.x / groups;
     const int Cg = C / groups;
     const float2 st = stats[blockIdx.x];
-    const float mean = st.x, rstd = st.y;
+    const float rstd = st.y;
     const size_t base = ((size_t)n * C + (size_t)g * Cg) * HW;
     const bool vec = HW % PN == 0;                                // every channel plane then starts on a 16-byte boundary
     const int hwp = HW / PN;
@@ -62,9 +61,8 @@ gn_bwd_nchw_kernel(int C, int HW, int groups, const float* __restrict__ x, const
     double S1 = 0.0, S2 = 0.0;                                    // (thread 0)
     for (int j = 0; j < Cg; j++) {
         const int c = g * Cg + j;
-        const float pbm = (pre_bias ? pre_bias[c] : 0.0f) - mean;
+        const GnChan ch = gn_chan(c, st, pre_bias, weight, bias);
         const float wc = weight[c];
-        const float sc = wc * rstd, sh = bias[c];
         const float* xs = x + base + (size_t)j * HW;
         const float* ds = dy + base + (size_t)j * HW;
         double a = 0.0, b = 0.0, xx = 0.0;
@@ -77,7 +75,7 @@ gn_bwd_nchw_kernel(int C, int HW, int groups, const float* __restrict__ x, const
 #pragma unroll
                 for (int k = 0; k < PN; k++) {
                     float dz, xh;
-                    gn_bwd_elem(px.v[k], pd.v[k], pbm, rstd, sc, sh, apply_silu, dz, xh);
+                    gn_bwd_elem(px.v[k], pd.v[k], ch, apply_silu, dz, xh);
                     fa += dz; fb = __builtin_fmaf(dz, xh, fb); fx += xh;
                 }
                 a += (double)fa; b += (double)fb; xx += (double)fx;
@@ -85,16 +83,11 @@ gn_bwd_nchw_kernel(int C, int HW, int groups, const float* __restrict__ x, const
         } else {
             for (int i = threadIdx.x; i < HW; i += GN_THREADS) {
                 float dz, xh;
-                gn_bwd_elem(xs[i], ds[i], pbm, rstd, sc, sh, apply_silu, dz, xh);
+                gn_bwd_elem(xs[i], ds[i], ch, apply_silu, dz, xh);
                 a += (double)dz; b += (double)(dz * xh); xx += (double)xh;
             }
         }
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) {
-            a += __shfl_xor(a, m, 64);
-            b += __shfl_xor(b, m, 64);
-            xx += __shfl_xor(xx, m, 64);
-        }
+        a = gn_wave_sum(a); b = gn_wave_sum(b); xx = gn_wave_sum(xx);
         const int set = j & 1;
         if (lane == 0) { wsum[set][0][wave] = a; wsum[set][1][wave] = b; wsum[set][2][wave] = xx; }
         __syncthreads();
@@ -122,27 +115,26 @@ gn_bwd_nchw_kernel(int C, int HW, int groups, const float* __restrict__ x, const
     if (vec) {
         const size_t np = slab / PN;
         for (size_t i = threadIdx.x; i < np; i += GN_THREADS) {
-            const int c = g * Cg + (idx32 ? (int)((unsigned)i / (unsigned)hwp) : (int)(i / hwp));
-            const float pbm = (pre_bias ? pre_bias[c] : 0.0f) - mean;
+            const int c = g * Cg + gn_nchw_chan(i, hwp, idx32);
+            const GnChan ch = gn_chan(c, st, pre_bias, weight, bias);
             const float wc = weight[c];
-            const float sc = wc * rstd, sh = bias[c];
             Packet<float> px, pd;
             px.load(x + base + i * PN);
             pd.load(dy + base + i * PN);
 #pragma unroll
             for (int k = 0; k < PN; k++) {
                 float dz, xh;
-                gn_bwd_elem(px.v[k], pd.v[k], pbm, rstd, sc, sh, apply_silu, dz, xh);
+                gn_bwd_elem(px.v[k], pd.v[k], ch, apply_silu, dz, xh);
                 px.v[k] = rstd * ((dz * wc - s1) - xh * s2);
             }
             px.store(dx + base + i * PN);
         }
     } else {
         for (size_t i = threadIdx.x; i < slab; i += GN_THREADS) {
-            const int c = g * Cg + (idx32 ? (int)((unsigned)i / (unsigned)HW) : (int)(i / HW));
+            const int c = g * Cg + gn_nchw_chan(i, HW, idx32);
             const float wc = weight[c];
             float dz, xh;
-            gn_bwd_elem(x[base + i], dy[base + i], (pre_bias ? pre_bias[c] : 0.0f) - mean, rstd, wc * rstd, bias[c], apply_silu, dz, xh);
+            gn_bwd_elem(x[base + i], dy[base + i], gn_chan(c, st, pre_bias, weight, bias), apply_silu, dz, xh);
             dx[base + i] = rstd * ((dz * wc - s1) - xh * s2);
         }
     }
@@ -150,75 +142,37 @@ gn_bwd_nchw_kernel(int C, int HW, int groups, const float* __restrict__ x, const
 
 // ---- channels-last: the forward's pixel-run mapping -----------------------------------------------------------------------------------
 // gn_bwd_nhwc_partial_kernel: thread (row, col) owns the packet `col` of the pixels row, row + rows, ... of its workgroup's run: float
-//     sums of dz, dz * xh and xh per channel over at most gn_nhwc_pix(HW) / rows pixels, the rows added in float64 -> part[n][block][3][C];
+//     sums of dz, dz * xh and xh per channel over at most gn_nhwc_pix(HW) / rows pixels (gn_nhwc_walk), the rows added in float64 ->
+//     part[n][block][3][C];
 // gn_bwd_nhwc_finish_kernel: ONE WAVE per (sample, group) adds the blocks of each of its channels -- lane l takes blocks l, l + 64, ...
 //     in order, then a fixed butterfly -- and leaves (A, B, X) per (n, c) and (s1, s2) per (n, g);
 // gn_bwd_nhwc_apply_kernel: the same mapping as the first, one pass: dx.
-struct GnBwdChan { float pbm[4], rstd[4], sc[4], sh[4]; };
-
-__device__ __forceinline__ GnBwdChan gn_bwd_nhwc_chan(int n, int col, int Cg, int groups, const float* __restrict__ pre_bias, const float* __restrict__ weight,
-                                                      const float* __restrict__ bias, const float2* __restrict__ stats)
-{
-    GnBwdChan ch;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int c = col * 4 + k;
-        const float2 st = stats[(size_t)n * groups + c / Cg];
-        ch.pbm[k] = (pre_bias ? pre_bias[c] : 0.0f) - st.x;
-        ch.rstd[k] = st.y;
-        ch.sc[k] = weight[c] * st.y;
-        ch.sh[k] = bias[c];
-    }
-    return ch;
-}
-
 __global__ void __launch_bounds__(256)
 gn_bwd_nhwc_partial_kernel(int C, int HW, int groups, int rows, const float* __restrict__ x, const float* __restrict__ pre_bias,
                            const float* __restrict__ weight, const float* __restrict__ bias, const float2* __restrict__ stats, int apply_silu,
                            const float* __restrict__ dy, double* __restrict__ part)
 {
     constexpr int PN = 4;
-    const int ppp = C / PN;
-    const int col = threadIdx.x % ppp, row = threadIdx.x / ppp;
-    const int n = blockIdx.y;
-    const int p0 = blockIdx.x * gn_nhwc_pix(HW);
-    const int p1 = min(p0 + gn_nhwc_pix(HW), HW);
+    const GnNhwcRun r = gn_nhwc_run<PN>(C, HW);
     float a[PN], b[PN], xx[PN];
 #pragma unroll
     for (int k = 0; k < PN; k++) { a[k] = 0.0f; b[k] = 0.0f; xx[k] = 0.0f; }
-    if (row < rows) {
-        const GnBwdChan ch = gn_bwd_nhwc_chan(n, col, C / groups, groups, pre_bias, weight, bias, stats);
-        const size_t base = ((size_t)n * HW) * C + (size_t)col * PN;
-        for (int p = p0 + row; p < p1; p += rows * GN_NHWC_UNROLL) {
-            Packet<float> qx[GN_NHWC_UNROLL], qd[GN_NHWC_UNROLL];
+    if (r.row < rows) {
+        GnChan ch[PN];
+        gn_nhwc_chan(ch, r, C / groups, groups, pre_bias, weight, bias, stats);
+        const size_t base = ((size_t)r.n * HW) * C + (size_t)r.col * PN;
+        const float* const in[2] = { x + base, dy + base };
+        gn_nhwc_walk(r, rows, C, in, [&](const Packet<float> (&q)[2], size_t) {
 #pragma unroll
-            for (int u = 0; u < GN_NHWC_UNROLL; u++)
-                if (p + u * rows < p1) { qx[u].load(x + base + (size_t)(p + u * rows) * C); qd[u].load(dy + base + (size_t)(p + u * rows) * C); }
-#pragma unroll
-            for (int u = 0; u < GN_NHWC_UNROLL; u++)
-                if (p + u * rows < p1) {
-#pragma unroll
-                    for (int k = 0; k < PN; k++) {
-                        float dz, xh;
-                        gn_bwd_elem(qx[u].v[k], qd[u].v[k], ch.pbm[k], ch.rstd[k], ch.sc[k], ch.sh[k], apply_silu, dz, xh);
-                        a[k] += dz; b[k] = __builtin_fmaf(dz, xh, b[k]); xx[k] += xh;
-                    }
-                }
-        }
+            for (int k = 0; k < PN; k++) {
+                float dz, xh;
+                gn_bwd_elem(q[0].v[k], q[1].v[k], ch[k], apply_silu, dz, xh);
+                a[k] += dz; b[k] = __builtin_fmaf(dz, xh, b[k]); xx[k] += xh;
+            }
+        });
     }
-    // per-channel totals over the rows: every (row, channel) has its own LDS word (rows * C <= 256 * PN), channel c is summed by thread c
-    __shared__ float sa[256 * PN], sb[256 * PN], sx[256 * PN];
-    if (row < rows) {
-#pragma unroll
-        for (int k = 0; k < PN; k++) { sa[row * C + col * PN + k] = a[k]; sb[row * C + col * PN + k] = b[k]; sx[row * C + col * PN + k] = xx[k]; }
-    }
-    __syncthreads();
-    double* o = part + ((size_t)n * gridDim.x + blockIdx.x) * 3 * (size_t)C;
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        double t1 = 0.0, t2 = 0.0, t3 = 0.0;
-        for (int r = 0; r < rows; r++) { t1 += (double)sa[r * C + c]; t2 += (double)sb[r * C + c]; t3 += (double)sx[r * C + c]; }
-        o[c] = t1; o[C + c] = t2; o[2 * C + c] = t3;
-    }
+    double* o = part + ((size_t)r.n * gridDim.x + blockIdx.x) * 3 * (size_t)C;
+    gn_rows_to_channels<double>(C, rows, r.row, r.col, [&](int c, const double (&t)[3]) { o[c] = t[0]; o[C + c] = t[1]; o[2 * C + c] = t[2]; }, a, b, xx);
 }
 
 __global__ void __launch_bounds__(256)
@@ -238,11 +192,7 @@ gn_bwd_nhwc_finish_kernel(int N, int C, int HW, int groups, int nb, const float*
             t[0] += p[0]; t[1] += p[C]; t[2] += p[2 * (size_t)C];
         }
 #pragma unroll
-        for (int m = 32; m > 0; m >>= 1) {
-            t[0] += __shfl_xor(t[0], m, 64);
-            t[1] += __shfl_xor(t[1], m, 64);
-            t[2] += __shfl_xor(t[2], m, 64);
-        }
+        for (int k = 0; k < 3; k++) t[k] = gn_wave_sum(t[k]);
         if (lane == 0) {
             double* o = nc + ((size_t)n * C + c) * 3;
             o[0] = t[0]; o[1] = t[1]; o[2] = t[2];
@@ -264,41 +214,31 @@ gn_bwd_nhwc_apply_kernel(int C, int HW, int groups, int rows, const float* __res
                          const float* __restrict__ dy, const double* __restrict__ sg, float* __restrict__ dx)
 {
     constexpr int PN = 4;
-    const int ppp = C / PN;
-    const int col = threadIdx.x % ppp, row = threadIdx.x / ppp;
-    if (row >= rows) return;
-    const int n = blockIdx.y;
-    const int p0 = blockIdx.x * gn_nhwc_pix(HW);
-    const int p1 = min(p0 + gn_nhwc_pix(HW), HW);
+    const GnNhwcRun r = gn_nhwc_run<PN>(C, HW);
+    if (r.row >= rows) return;
     const int Cg = C / groups;
-    const GnBwdChan ch = gn_bwd_nhwc_chan(n, col, Cg, groups, pre_bias, weight, bias, stats);
+    GnChan ch[PN];
+    gn_nhwc_chan(ch, r, Cg, groups, pre_bias, weight, bias, stats);
     float wc[PN], s1[PN], s2[PN];
 #pragma unroll
     for (int k = 0; k < PN; k++) {
-        const int c = col * PN + k;
-        const double* s = sg + ((size_t)n * groups + c / Cg) * 2;
+        const int c = r.col * PN + k;
+        const double* s = sg + ((size_t)r.n * groups + c / Cg) * 2;
         wc[k] = weight[c];
         s1[k] = (float)s[0];
         s2[k] = (float)s[1];
     }
-    const size_t base = ((size_t)n * HW) * C + (size_t)col * PN;
-    for (int p = p0 + row; p < p1; p += rows * GN_NHWC_UNROLL) {
-        Packet<float> qx[GN_NHWC_UNROLL], qd[GN_NHWC_UNROLL];
+    const size_t base = ((size_t)r.n * HW) * C + (size_t)r.col * PN;
+    const float* const in[2] = { x + base, dy + base };
+    gn_nhwc_walk(r, rows, C, in, [&](Packet<float> (&q)[2], size_t off) {
 #pragma unroll
-        for (int u = 0; u < GN_NHWC_UNROLL; u++)
-            if (p + u * rows < p1) { qx[u].load(x + base + (size_t)(p + u * rows) * C); qd[u].load(dy + base + (size_t)(p + u * rows) * C); }
-#pragma unroll
-        for (int u = 0; u < GN_NHWC_UNROLL; u++)
-            if (p + u * rows < p1) {
-#pragma unroll
-                for (int k = 0; k < PN; k++) {
-                    float dz, xh;
-                    gn_bwd_elem(qx[u].v[k], qd[u].v[k], ch.pbm[k], ch.rstd[k], ch.sc[k], ch.sh[k], apply_silu, dz, xh);
-                    qx[u].v[k] = ch.rstd[k] * ((dz * wc[k] - s1[k]) - xh * s2[k]);
-                }
-                qx[u].store(dx + base + (size_t)(p + u * rows) * C);
-            }
-    }
+        for (int k = 0; k < PN; k++) {
+            float dz, xh;
+            gn_bwd_elem(q[0].v[k], q[1].v[k], ch[k], apply_silu, dz, xh);
+            q[0].v[k] = ch[k].rstd * ((dz * wc[k] - s1[k]) - xh * s2[k]);
+        }
+        q[0].store(dx + base + off);
+    });
 }
 
 // ---- second stage, both layouts: the per-(n, c) sums over n, in order, one thread per channel ------------------------------------------
@@ -366,8 +306,7 @@ join_bwd_nchw_kernel(int C, int HW, int cpp, int vec, const float* gy, float sca
         }
     }
     if (!part) return;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m, 64);
+    s = gn_wave_sum(s);
     __shared__ double ws[4];
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
     __syncthreads();
@@ -393,17 +332,7 @@ join_bwd_nhwc_kernel(int C, size_t P, int rows, const float* gy, float scale, fl
         }
     }
     if (!part) return;
-    __shared__ double ss[256 * PN];                               // (row, channel): rows * C <= 256 * PN
-    if (row < rows) {
-#pragma unroll
-        for (int k = 0; k < PN; k++) ss[row * C + col * PN + k] = s[k];
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        double t = 0.0;
-        for (int r = 0; r < rows; r++) t += ss[r * C + c];
-        part[(size_t)blockIdx.x * C + c] = t;
-    }
+    gn_rows_to_channels<double>(C, rows, row, col, [&](int c, const double (&t)[1]) { part[(size_t)blockIdx.x * C + c] = t[0]; }, s);
 }
 
 __global__ void __launch_bounds__(256)
@@ -414,8 +343,7 @@ join_bwd_finish_kernel(int C, size_t nseg, const double* __restrict__ part, floa
     const int lane = threadIdx.x & 63;
     double t = 0.0;
     for (size_t s = lane; s < nseg; s += 64) t += part[s * C + c];
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) t += __shfl_xor(t, m, 64);
+    t = gn_wave_sum(t);
     if (lane == 0) gbias[c] = (float)t;
 }
 
@@ -438,11 +366,10 @@ extern "C" int f3dg_group_norm_silu_backward(void* stream, int N, int C, int HW,
                                              float* grad_x, float* grad_weight, float* grad_bias, float* grad_pre_bias, void* scratch,
                                              size_t scratch_bytes)
 {
-    if (N < 0 || C <= 0 || HW <= 0 || groups <= 0 || C % groups != 0 || !x || !weight || !bias || !stats || !grad_y || !scratch) return F3DG_ERR_BAD_ARG;
-    if (N > 0 && scratch_bytes < f3dg_group_norm_silu_backward_scratch_bytes(N, C, HW, groups, nhwc)) return F3DG_ERR_WORKSPACE;
-    if (nhwc && (C % 4 != 0 || C / 4 > 256 || C > GN_NHWC_MAXC)) return F3DG_ERR_BAD_ARG;
-    if (N == 0) return F3DG_OK;
-    if ((((uintptr_t)x | (uintptr_t)grad_y | (uintptr_t)grad_x) & 15u) || (((uintptr_t)stats | (uintptr_t)scratch) & 7u)) return F3DG_ERR_BAD_ARG;
+    const int rc = gn_check_args(N, C, HW, groups, nhwc, 4, x && weight && bias && stats && grad_y && scratch, scratch_bytes,
+                                 f3dg_group_norm_silu_backward_scratch_bytes(N, C, HW, groups, nhwc), (uintptr_t)x | (uintptr_t)grad_y | (uintptr_t)grad_x,
+                                 (uintptr_t)stats | (uintptr_t)scratch);
+    if (rc != F3DG_OK || N == 0) return rc;
     if ((long long)N * groups > 0x7FFFFFFFll || (nhwc && N > 65535)) return F3DG_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     const float2* st = reinterpret_cast<const float2*>(stats);

@@ -62,7 +62,7 @@ def _is_nhwc(t):
 
 
 _HALF_DTYPES = (torch.bfloat16, torch.float16)
-_KERNEL_SUFFIX = {torch.float32: "", torch.bfloat16: "_bf16", torch.float16: "_f16"}      # of the GroupNorm / residual-join entry points
+_KERNEL_DTYPE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}      # the dtypes the GroupNorm / residual-join kernels take: F3DG_F32, _BF16, _F16
 
 
 class Conv2d(nn.Module):
@@ -146,30 +146,38 @@ def _dense_like(g, nhwc):
     return g.clone() if g.data_ptr() % 16 else g
 
 
+def _gn_forward(x, pre_bias, weight, bias, groups, eps, silu, keep_stats=False):
+    """``f3dg_group_norm_silu_forward`` on ``x`` as it lies where the channels-last kernels take it (channels-last out), on a dense
+    16-byte aligned NCHW copy otherwise. Returns ``(x as the kernel read it, y, nhwc, stats)``; ``keep_stats`` (float32 only) keeps the
+    (mean, rstd) pair per (sample, group) that the backward normalises with."""
+    L = _lib.lib()
+    nhwc = _gn_nhwc_ok(x)
+    if not nhwc:
+        x = x.contiguous()
+        if x.data_ptr() % 16:               # a dense view that starts inside an allocation: the kernels load 16-byte packets
+            x = x.clone()
+    N, Cc = x.shape[0], x.shape[1]
+    HW = x.numel() // (N * Cc)
+    y = torch.empty_like(x)                 # preserves the strides
+    stats = torch.empty((N, groups, 2), dtype=torch.float32, device=x.device) if keep_stats else None
+    scratch, nbytes = None, 0
+    if nhwc:
+        scratch = torch.empty(L.f3dg_group_norm_nhwc_scratch_bytes(N, HW, groups) // 8 + 1, dtype=torch.float64, device=x.device)
+        nbytes = scratch.numel() * 8
+    rc = L.f3dg_group_norm_silu_forward(_stream(), _KERNEL_DTYPE[x.dtype], 1 if nhwc else 0, N, Cc, HW, groups, _lib.ptr(x), _lib.ptr(pre_bias),
+                                        _lib.ptr(weight), _lib.ptr(bias), float(eps), 1 if silu else 0, _lib.ptr(y), _lib.ptr(stats), _lib.ptr(scratch), nbytes)
+    _lib.check(rc, "f3dg_group_norm_silu_forward")
+    return x, y, nhwc, stats
+
+
 class _GroupNormSiLU(torch.autograd.Function):
-    """``f3dg_group_norm_silu_stats`` with ``f3dg_group_norm_silu_backward`` behind it (float32, NCHW or channels-last). Saved: ``x``, the
-    parameters and the (mean, rstd) pair per (sample, group) -- not the output and not the normalised pre-activation, which the backward
-    kernel recomputes from ``x``."""
+    """``f3dg_group_norm_silu_forward`` keeping its statistics, with ``f3dg_group_norm_silu_backward`` behind it (float32, NCHW or
+    channels-last). Saved: ``x``, the parameters and the (mean, rstd) pair per (sample, group) -- not the output and not the normalised
+    pre-activation, which the backward kernel recomputes from ``x``."""
 
     @staticmethod
     def forward(ctx, x, pre_bias, weight, bias, groups, eps, silu):
-        L = _lib.lib()
-        nhwc = _gn_nhwc_ok(x)
-        if not nhwc:
-            x = x.contiguous()
-            if x.data_ptr() % 16:
-                x = x.clone()
-        N, Cc = x.shape[0], x.shape[1]
-        HW = x.numel() // (N * Cc)
-        y = torch.empty_like(x)             # preserves the strides
-        stats = torch.empty((N, groups, 2), dtype=torch.float32, device=x.device)
-        mom, mom_bytes = None, 0
-        if nhwc:
-            mom = torch.empty(L.f3dg_group_norm_nhwc_scratch_bytes(N, HW, groups) // 8 + 1, dtype=torch.float64, device=x.device)
-            mom_bytes = mom.numel() * 8
-        rc = L.f3dg_group_norm_silu_stats(_stream(), N, Cc, HW, groups, 1 if nhwc else 0, _lib.ptr(x), _lib.ptr(pre_bias), _lib.ptr(weight),
-                                          _lib.ptr(bias), float(eps), 1 if silu else 0, _lib.ptr(y), _lib.ptr(stats), _lib.ptr(mom), mom_bytes)
-        _lib.check(rc, "f3dg_group_norm_silu_stats")
+        x, y, nhwc, stats = _gn_forward(x, pre_bias, weight, bias, groups, eps, silu, keep_stats=True)
         ctx.save_for_backward(x, pre_bias, weight, bias, stats)
         ctx.groups, ctx.silu, ctx.nhwc = groups, bool(silu), nhwc
         return y
@@ -197,17 +205,22 @@ class _GroupNormSiLU(torch.autograd.Function):
         return dx, dpb, dw, db, None, None, None
 
 
+def _join_forward(a, bias_a, b, bias_b, scale, y, nhwc):
+    N, Cc, H, W = a.shape
+    rc = _lib.lib().f3dg_residual_join_forward(_stream(), _KERNEL_DTYPE[a.dtype], 1 if nhwc else 0, N, Cc, H * W, _lib.ptr(a), _lib.ptr(bias_a),
+                                               _lib.ptr(b), _lib.ptr(bias_b), float(scale), _lib.ptr(y))
+    _lib.check(rc, "f3dg_residual_join_forward")
+
+
 class _ResidualJoin(torch.autograd.Function):
-    """``f3dg_residual_join`` out of place with ``f3dg_residual_join_backward`` behind it: nothing is saved, the backward is one pass over
+    """``f3dg_residual_join_forward`` out of place with ``f3dg_residual_join_backward`` behind it: nothing is saved, the backward is one pass over
     the cotangent whose result is the gradient of ``a`` and of ``b`` alike, and whose per-channel sum is the gradient of either bias."""
 
     @staticmethod
     def forward(ctx, a, bias_a, b, bias_b, scale):
         nhwc = _is_nhwc(a)
-        N, Cc, H, W = a.shape
         y = torch.empty_like(a)
-        _lib.check(_lib.lib().f3dg_residual_join(_stream(), N, Cc, H * W, 1 if nhwc else 0, _lib.ptr(a), _lib.ptr(bias_a), _lib.ptr(b), _lib.ptr(bias_b),
-                                                 float(scale), _lib.ptr(y)), "f3dg_residual_join")
+        _join_forward(a, bias_a, b, bias_b, scale, y, nhwc)
         ctx.nhwc, ctx.scale = nhwc, float(scale)
         return y
 
@@ -243,7 +256,7 @@ class GroupNorm(nn.Module):
     def _fusable(self, x):
         """A HIP device and a dtype the kernels take: the fused HIP kernels run -- in inference always; under autograd only with the
         ``fused_autograd`` switch on and in float32 (16-bit backbones are inference-only)."""
-        if not (x.is_cuda and x.dtype in _KERNEL_SUFFIX and x.dim() >= 3 and x.numel() > 0 and self.weight.dtype == torch.float32):
+        if not (x.is_cuda and x.dtype in _KERNEL_DTYPE and x.dim() >= 3 and x.numel() > 0 and self.weight.dtype == torch.float32):
             return False
         if not (torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad)):
             return True
@@ -251,7 +264,7 @@ class GroupNorm(nn.Module):
 
     def forward(self, x, N_views_xa=1, silu=False, pre_bias=None):
         """``silu=True`` returns ``F.silu(group_norm(x))``: the pair the residual blocks always apply together. In
-        inference on a HIP device the pair is ONE fused kernel (``f3dg_group_norm_silu``); with autograd
+        inference on a HIP device the pair is ONE fused kernel (``f3dg_group_norm_silu_forward``); with autograd
         or on the host (the CPU fixtures of the backbone) it is the two PyTorch ops -- unless ``fused_autograd`` is set
         (``set_fused_autograd``), when float32 tensors on a HIP device take the kernels under autograd too, with
         ``f3dg_group_norm_silu_backward`` behind them. ``pre_bias`` ([C] float32): the result is
@@ -260,29 +273,7 @@ class GroupNorm(nn.Module):
             if self.fused_autograd and x.dtype == torch.float32 and self.bias.dtype == torch.float32 and torch.is_grad_enabled() and any(
                     t is not None and t.requires_grad for t in (x, pre_bias, self.weight, self.bias)):
                 return _GroupNormSiLU.apply(x, pre_bias, self.weight, self.bias, self.num_groups, float(self.eps), bool(silu))
-            L = _lib.lib()
-            if _gn_nhwc_ok(x):
-                # layout option "nhwc": the channels-last kernel, channels-last out
-                y = torch.empty_like(x)           # preserves the strides
-                N, Cc = x.shape[0], x.shape[1]
-                HW = x.shape[2] * x.shape[3]
-                mom = torch.empty(L.f3dg_group_norm_nhwc_scratch_bytes(N, HW, self.num_groups) // 8 + 1, dtype=torch.float64, device=x.device)
-                mom_bytes = mom.numel() * 8
-                fn = getattr(L, "f3dg_group_norm_silu_nhwc_pb" + _KERNEL_SUFFIX[x.dtype])
-                rc = fn(_stream(), N, Cc, x.shape[2] * x.shape[3], self.num_groups, _lib.ptr(x), _lib.ptr(pre_bias), _lib.ptr(self.weight),
-                        _lib.ptr(self.bias), float(self.eps), 1 if silu else 0, _lib.ptr(y), _lib.ptr(mom), mom_bytes)
-                _lib.check(rc, "f3dg_group_norm_silu_nhwc_pb")
-                return y
-            xc = x.contiguous()
-            if xc.data_ptr() % 16:              # a dense view that starts inside an allocation: the kernels load 16-byte packets
-                xc = xc.clone()
-            y = torch.empty_like(xc)
-            N, Cc = xc.shape[0], xc.shape[1]
-            fn = getattr(L, "f3dg_group_norm_silu_pb" + _KERNEL_SUFFIX[x.dtype])
-            rc = fn(_stream(), N, Cc, xc.numel() // max(N * Cc, 1), self.num_groups, _lib.ptr(xc), _lib.ptr(pre_bias), _lib.ptr(self.weight),
-                    _lib.ptr(self.bias), float(self.eps), 1 if silu else 0, _lib.ptr(y))
-            _lib.check(rc, "f3dg_group_norm_silu_pb")
-            return y
+            return _gn_forward(x, pre_bias, self.weight, self.bias, self.num_groups, self.eps, silu)[1]
         if pre_bias is not None:
             x = x + pre_bias.to(x.dtype).reshape(1, -1, *([1] * (x.dim() - 2)))
         y = F.group_norm(x, self.num_groups, self.weight.to(x.dtype), self.bias.to(x.dtype), self.eps)
@@ -291,13 +282,13 @@ class GroupNorm(nn.Module):
 
 def residual_join(a, bias_a, b, bias_b, scale, fused_autograd=False):
     """((a + bias_a) + (b + bias_b)) * scale with per-channel biases (either may be None): the tail of a residual block. One HIP
-    kernel (``f3dg_residual_join``) for inference tensors on a HIP device that share a dense layout (NCHW or channels-last); the
+    kernel (``f3dg_residual_join_forward``) for inference tensors on a HIP device that share a dense layout (NCHW or channels-last); the
     PyTorch ops otherwise. Writes into ``a``'s storage when it can. ``fused_autograd=True``: under autograd float32 tensors take the
     kernel as well, out of place, with ``f3dg_residual_join_backward`` behind it."""
     def tb(t, bias):
         return t if bias is None else t + bias.to(t.dtype).reshape(1, -1, 1, 1)
     grad = fused_autograd and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (a, b, bias_a, bias_b))
-    ok = (a.is_cuda and a.dim() == 4 and a.dtype in _KERNEL_SUFFIX and b.dtype == a.dtype and a.shape == b.shape
+    ok = (a.is_cuda and a.dim() == 4 and a.dtype in _KERNEL_DTYPE and b.dtype == a.dtype and a.shape == b.shape
           and (a.dtype == torch.float32 if grad else not (torch.is_grad_enabled() and (a.requires_grad or b.requires_grad)))
           and all(t is None or (t.dtype == torch.float32 and t.is_contiguous()) for t in (bias_a, bias_b))
           and a.numel() % (4 if a.dtype == torch.float32 else 8) == 0)
@@ -309,10 +300,7 @@ def residual_join(a, bias_a, b, bias_b, scale, fused_autograd=False):
             if not (nhwc and a.shape[1] > 1024):        # (the adjoint's channels-last limit)
                 return _ResidualJoin.apply(a, bias_a, b, bias_b, float(scale))
         elif same and (a.data_ptr() | b.data_ptr()) % 16 == 0:
-            N, Cc, H, W = a.shape
-            fn = getattr(_lib.lib(), "f3dg_residual_join" + _KERNEL_SUFFIX[a.dtype])
-            _lib.check(fn(_stream(), N, Cc, H * W, 1 if nhwc else 0, _lib.ptr(a), _lib.ptr(bias_a), _lib.ptr(b), _lib.ptr(bias_b), float(scale),
-                          _lib.ptr(a)), "f3dg_residual_join")
+            _join_forward(a, bias_a, b, bias_b, scale, a, nhwc)
             return a
     return (tb(a, bias_a) + tb(b, bias_b)) * scale
 

@@ -462,65 +462,41 @@ int f3dg_cycle_inputs(void* stream, int B, int V, int H, int W, const float* ras
 int f3dg_cycle_inputs_backward(void* stream, int B, int V, int H, int W, const float* raster,
                                const float* g_xin, const float* g_depth, float* d_raster);
 
-/* Fused GroupNorm (+ SiLU when apply_silu != 0) of the predictor's SongUNet backbone (src/gaussian_predictor.py:250-262 and the
- * `silu(norm(x))` of its residual blocks, :318-323): x, y [N,C,HW] float32 contiguous (NCHW), weight / bias [C],
- * statistics per (sample, group) over C/groups x HW values, biased variance, y = (x - mean) / sqrt(var + eps) * weight + bias.
- * x == y (in place) is allowed. SURVEY.md 8f-3. */
-int f3dg_group_norm_silu(void* stream, int N, int C, int HW, int groups, const float* x, const float* weight,
-                         const float* bias, float eps, int apply_silu, float* y);
-/* The same with bfloat16 activations in and out (the bf16 option of the backbone); weight / bias and all arithmetic float32,
- * the moments float64. */
-int f3dg_group_norm_silu_bf16(void* stream, int N, int C, int HW, int groups, const uint16_t* x, const float* weight,
-                              const float* bias, float eps, int apply_silu, uint16_t* y);
-/* The same for channels-last activations (the backbone's "nhwc" layout option: MIOpen's NHWC convolution kernels without the layout
- * transposes around them): x, y [N,HW,C] contiguous, C a multiple of 4 (float32) / 8 (bfloat16) and at most 1024;
- * `moments` is scratch of f3dg_group_norm_nhwc_scratch_bytes(N, HW, groups) bytes: one (sum, sum of squares) pair per workgroup, sample
- * and group, added up in workgroup order by a second-stage kernel -- no atomics, the statistics are bit-reproducible from run to run
- * (round 5; until then the workgroups added into 8 atomic slots in arrival order). Same statistics, same formula.
- * `moments_bytes` = the size of the buffer behind `moments` (round 6: the scratch has grown with the kernel -- a pair per workgroup, then
- * workgroups of 64 instead of 512 pixels for samples below 128 x 128 pixels; a buffer smaller than
- * f3dg_group_norm_nhwc_scratch_bytes() is refused with F3DG_ERR_WORKSPACE instead of being written past its end).
- * Both layouts sum (x - K) and (x - K)^2, K the first value of the (sample, group), so that the variance keeps torch's float32 accuracy
- * when a group's mean is far from zero (measured up to |mean| / std = 100 and on constant groups: tests/test_backbone_kernels_gpu.py). */
+/* The SongUNet backbone's kernels between the convolutions. `dtype` names the activations' type -- F3DG_BF16 and F3DG_F16 are the bf16 /
+ * fp16 options of the backbone, 16-bit values in and out; parameters, statistics and all arithmetic are float32 / float64 whatever it is.
+ * `nhwc` their layout: 0 = [N,C,HW] contiguous (NCHW), 1 = [N,HW,C] (channels-last, the backbone's "nhwc" layout option: MIOpen's NHWC
+ * convolution kernels without the layout transposes around them). */
+enum { F3DG_F32 = 0, F3DG_BF16 = 1, F3DG_F16 = 2 };
+
+/* Fused GroupNorm (+ SiLU when apply_silu != 0; src/gaussian_predictor.py:250-262 and the `silu(norm(x))` of the residual blocks,
+ * :318-323): x, y as `dtype` and `nhwc` say, weight / bias [C] float32, statistics per (sample, group) over C/groups x HW
+ * values, biased variance, y = (v - mean) / sqrt(var + eps) * weight + bias with v = x + pre_bias[c]. pre_bias ([C] float32, may be NULL)
+ * is the bias of the convolution that produced x, which PyTorch-ROCm would apply as a separate elementwise pass behind MIOpen's kernel
+ * (src/gaussian_predictor.py:163-178); the residual blocks hand it to the GroupNorm that follows. x == y (in place) is allowed.
+ * Both layouts sum (v - K) and (v - K)^2, K the first value of the (sample, group), so that the variance keeps torch's float32 accuracy
+ * when a group's mean is far from zero (measured up to |mean| / std = 100 and on constant groups: tests/test_backbone_kernels_gpu.py).
+ * `stats` (may be NULL; F3DG_F32 only, 8-byte aligned): [N, groups, 2] float32 = (mean, 1 / sqrt(var + eps)) per (sample, group), kept
+ * for f3dg_group_norm_silu_backward; y is the same with and without it.
+ * `scratch` / `scratch_bytes`: channels-last only (NULL / 0 with nhwc = 0), f3dg_group_norm_nhwc_scratch_bytes(N, HW, groups) bytes: one
+ * (sum, sum of squares) pair per workgroup, sample and group, added up in workgroup order by a second-stage kernel -- no atomics, the
+ * statistics are bit-reproducible from run to run. `scratch_bytes` is the size of the buffer behind `scratch`: the scratch has grown with
+ * the kernels, and a buffer sized by an older header is refused with F3DG_ERR_WORKSPACE instead of being written past its end.
+ * F3DG_ERR_BAD_ARG before any HIP call, nothing written: a dtype outside 0..2, stats with a 16-bit dtype or off the 8-byte grid, a NULL
+ * x / weight / bias / y (channels-last: scratch), non-positive C / HW / groups, N < 0, groups that do not divide C, x or y not 16-byte
+ * aligned, channels-last C that is no multiple of 4 (float32) / 8 (16-bit) or above 1024. N == 0: F3DG_OK and no work. */
 size_t f3dg_group_norm_nhwc_scratch_bytes(int N, int HW, int groups);
-int f3dg_group_norm_silu_nhwc(void* stream, int N, int C, int HW, int groups, const float* x, const float* weight,
-                              const float* bias, float eps, int apply_silu, float* y, double* moments, size_t moments_bytes);
-int f3dg_group_norm_silu_nhwc_bf16(void* stream, int N, int C, int HW, int groups, const uint16_t* x, const float* weight,
-                                   const float* bias, float eps, int apply_silu, uint16_t* y, double* moments, size_t moments_bytes);
-/* The four GroupNorm entry points with the bias of the convolution that produced x folded in: y = gn(x + pre_bias[c]) (pre_bias [C]
- * float32, may be null). PyTorch-ROCm applies a convolution's bias as a separate elementwise pass behind MIOpen's kernel
- * (src/gaussian_predictor.py:163-178 `x = conv2d(x, w) ; x = x.add_(b)`); the residual blocks hand it to the GroupNorm that follows. */
-int f3dg_group_norm_silu_pb(void* stream, int N, int C, int HW, int groups, const float* x, const float* pre_bias, const float* weight,
-                            const float* bias, float eps, int apply_silu, float* y);
-int f3dg_group_norm_silu_pb_bf16(void* stream, int N, int C, int HW, int groups, const uint16_t* x, const float* pre_bias, const float* weight,
-                                 const float* bias, float eps, int apply_silu, uint16_t* y);
-int f3dg_group_norm_silu_nhwc_pb(void* stream, int N, int C, int HW, int groups, const float* x, const float* pre_bias, const float* weight,
-                                 const float* bias, float eps, int apply_silu, float* y, double* moments, size_t moments_bytes);
-int f3dg_group_norm_silu_nhwc_pb_bf16(void* stream, int N, int C, int HW, int groups, const uint16_t* x, const float* pre_bias,
-                                      const float* weight, const float* bias, float eps, int apply_silu, uint16_t* y, double* moments, size_t moments_bytes);
-/* ... and with IEEE float16 activations in and out (the fp16 option of the backbone, round 5: the bf16 MFMA rate with 10 mantissa bits
- * instead of 7; every activation of the backbone is GroupNorm-bounded). Weight / bias and all arithmetic float32, the moments float64. */
-int f3dg_group_norm_silu_pb_f16(void* stream, int N, int C, int HW, int groups, const uint16_t* x, const float* pre_bias, const float* weight,
-                                const float* bias, float eps, int apply_silu, uint16_t* y);
-int f3dg_group_norm_silu_nhwc_pb_f16(void* stream, int N, int C, int HW, int groups, const uint16_t* x, const float* pre_bias,
-                                     const float* weight, const float* bias, float eps, int apply_silu, uint16_t* y, double* moments, size_t moments_bytes);
+int f3dg_group_norm_silu_forward(void* stream, int dtype, int nhwc, int N, int C, int HW, int groups,
+                                 const void* x, const float* pre_bias, const float* weight, const float* bias,
+                                 float eps, int apply_silu, void* y, float* stats, void* scratch, size_t scratch_bytes);
 /* The residual join of a backbone block (src/gaussian_predictor.py:325-327: the second convolution's bias, `x = x + skip(orig)` with the
  * skip convolution's bias, `x = x * skip_scale`) as ONE elementwise pass: y = ((a + bias_a[c]) + (b + bias_b[c])) * scale in float32,
- * the reference's order. a, b, y [N,C,HW] (nhwc = 0) or [N,HW,C] (nhwc = 1), 16-byte aligned, N*C*HW a multiple of 4 (float32) / 8
- * (bfloat16) -- and C as well when nhwc = 1; either bias may be null; y may alias a or b. */
-int f3dg_residual_join(void* stream, int N, int C, int HW, int nhwc, const float* a, const float* bias_a, const float* b,
-                       const float* bias_b, float scale, float* y);
-int f3dg_residual_join_bf16(void* stream, int N, int C, int HW, int nhwc, const uint16_t* a, const float* bias_a, const uint16_t* b,
-                            const float* bias_b, float scale, uint16_t* y);
-int f3dg_residual_join_f16(void* stream, int N, int C, int HW, int nhwc, const uint16_t* a, const float* bias_a, const uint16_t* b,
-                           const float* bias_b, float scale, uint16_t* y);
+ * the reference's order. a, b, y as `dtype` and `nhwc` say, 16-byte aligned, N*C*HW a multiple of 4 (float32) / 8 (16-bit) -- and C as
+ * well when nhwc = 1; either bias may be null; y may alias a or b. Anything else, and a dtype outside 0..2, is F3DG_ERR_BAD_ARG. */
+int f3dg_residual_join_forward(void* stream, int dtype, int nhwc, int N, int C, int HW,
+                               const void* a, const float* bias_a, const void* b, const float* bias_b, float scale, void* y);
 /* Training through the backbone: the adjoints of the float32 kernels above, both layouts (nhwc = 0: [N,C,HW]; nhwc = 1: [N,HW,C]).
  *
- * f3dg_group_norm_silu_stats is the float32 forward (the same kernels and the same y as f3dg_group_norm_silu_pb / _nhwc_pb) that also
- * keeps its statistics: stats [N, groups, 2] float32 = (mean, 1 / sqrt(var + eps)) per (sample, group), 8-byte aligned. `moments` /
- * `moments_bytes` are the channels-last scratch (f3dg_group_norm_nhwc_scratch_bytes); with nhwc = 0 they are unused and may be NULL / 0.
- *
- * f3dg_group_norm_silu_backward recomputes everything else from x. With v = x + pre_bias, xh = (v - mean) * rstd, z = weight * xh + bias
+ * f3dg_group_norm_silu_backward takes `stats` from f3dg_group_norm_silu_forward and recomputes everything else from x. With v = x + pre_bias, xh = (v - mean) * rstd, z = weight * xh + bias
  * (formed as the forward forms it: the mean taken off before the scale), m = (C / groups) * HW:
  *   dz = grad_y * s * (1 + z * (1 - s)), s = sigmoid(z)   (apply_silu != 0; dz = grad_y otherwise)
  *   A[n, c] = sum_hw dz,  B[n, c] = sum_hw dz * xh,  s1[n, g] = sum_c weight[c] A / m,  s2[n, g] = sum_c weight[c] B / m
@@ -533,15 +509,12 @@ int f3dg_residual_join_f16(void* stream, int N, int C, int HW, int nhwc, const u
  * Refused as the forward refuses, before anything is written: F3DG_ERR_BAD_ARG for a NULL x / weight / bias / stats / grad_y / scratch,
  * groups that do not divide C, x / grad_y / grad_x not 16-byte aligned, channels-last C that is no multiple of 4 or above 1024;
  * F3DG_ERR_WORKSPACE for scratch_bytes below the size above. N == 0: F3DG_OK and no work. */
-int f3dg_group_norm_silu_stats(void* stream, int N, int C, int HW, int groups, int nhwc, const float* x, const float* pre_bias,
-                               const float* weight, const float* bias, float eps, int apply_silu, float* y, float* stats,
-                               double* moments, size_t moments_bytes);
 size_t f3dg_group_norm_silu_backward_scratch_bytes(int N, int C, int HW, int groups, int nhwc);
 int f3dg_group_norm_silu_backward(void* stream, int N, int C, int HW, int groups, int nhwc, const float* x, const float* pre_bias,
                                   const float* weight, const float* bias, const float* stats, int apply_silu, const float* grad_y,
                                   float* grad_x, float* grad_weight, float* grad_bias, float* grad_pre_bias, void* scratch,
                                   size_t scratch_bytes);
-/* The adjoint of f3dg_residual_join in ONE pass over grad_y: grad_ab = grad_y * scale [as grad_y], which is the gradient of a and of b
+/* The adjoint of f3dg_residual_join_forward in ONE pass over grad_y: grad_ab = grad_y * scale [as grad_y], which is the gradient of a and of b
  * alike, and grad_bias[c] = the sum of grad_ab over channel c ([C], the gradient of either bias; NULL = not wanted), summed in float64 in
  * a fixed order without atomics. grad_ab may be grad_y. `scratch` (needed only with grad_bias): f3dg_residual_join_backward_scratch_bytes
  * bytes, 8-byte aligned; less is F3DG_ERR_WORKSPACE. F3DG_ERR_BAD_ARG as the forward: N*C*HW no multiple of 4, pointers not 16-byte

@@ -85,14 +85,41 @@ def test_backward_entry_points_refuse_on_the_host_and_size_their_scratch(f3d):
         assert bwd(0, 64, 16, 16, nhwc, nbytes=0) == 0                                 # an empty batch: no error, no work
     assert bwd(2, 22, 16, 1, 1) == bad and bwd(1, 1032, 16, 24, 1) == bad              # channels-last: whole packets, at most 1024 channels
 
-    def stats_fwd(N, Cc, HW, groups, nhwc, x=p(), y=p(), stats=p(), nbytes=big):
-        return L.f3dg_group_norm_silu_stats(None, N, Cc, HW, groups, nhwc, x, p(), p(), p(), 1e-6, 1, y, stats, p(), nbytes)
+    def stats_fwd(N, Cc, HW, groups, nhwc, x=p(), y=p(), stats=p(), nbytes=big, dtype=0, scratch=p()):
+        return L.f3dg_group_norm_silu_forward(None, dtype, nhwc, N, Cc, HW, groups, x, p(), p(), p(), 1e-6, 1, y, stats, scratch, nbytes)
 
     for nhwc in (0, 1):
         assert stats_fwd(2, 64, 16, 24, nhwc) == bad and stats_fwd(2, 64, 16, 16, nhwc, x=p(4)) == bad and stats_fwd(2, 64, 16, 16, nhwc, y=p(4)) == bad
-        assert stats_fwd(2, 64, 16, 16, nhwc, stats=None) == bad and stats_fwd(2, 64, 16, 16, nhwc, stats=p(4)) == bad
+        assert stats_fwd(2, 64, 16, 16, nhwc, stats=p(4)) == bad             # (stats = NULL is the forward that keeps none: no refusal)
         assert stats_fwd(0, 64, 16, 16, nhwc) == 0
     assert stats_fwd(2, 64, 16, 16, 1, nbytes=8) == ws and stats_fwd(2, 22, 16, 1, 1) == bad
+    # the one forward entry: a dtype it does not know, statistics of a 16-bit call, and per dtype what the forward refused before
+    need = L.f3dg_group_norm_nhwc_scratch_bytes(2, 16, 16)
+    assert need > 0
+    for nhwc in (0, 1):
+        assert stats_fwd(2, 64, 16, 16, nhwc, dtype=-1) == bad and stats_fwd(2, 64, 16, 16, nhwc, dtype=3) == bad
+        assert stats_fwd(2, 64, 16, 16, nhwc, dtype=-1, stats=None) == bad and stats_fwd(2, 64, 16, 16, nhwc, dtype=3, stats=None) == bad
+        assert stats_fwd(2, 64, 16, 16, nhwc, dtype=1) == bad and stats_fwd(2, 64, 16, 16, nhwc, dtype=2) == bad
+        for dtype in (0, 1, 2):
+            assert stats_fwd(2, 64, 16, 24, nhwc, dtype=dtype, stats=None) == bad and stats_fwd(2, 64, 16, 16, nhwc, dtype=dtype, stats=None, x=None) == bad
+            assert stats_fwd(2, 64, 16, 16, nhwc, dtype=dtype, stats=None, x=p(4)) == bad and stats_fwd(2, 64, 16, 16, nhwc, dtype=dtype, stats=None, y=p(4)) == bad
+            assert stats_fwd(0, 64, 16, 16, nhwc, dtype=dtype, stats=None) == 0
+    for dtype in (0, 1, 2):
+        assert stats_fwd(2, 64, 16, 16, 1, dtype=dtype, stats=None, nbytes=need - 1) == ws
+        assert stats_fwd(2, 64, 16, 16, 1, dtype=dtype, stats=None, scratch=None) == bad
+        assert stats_fwd(0, 64, 16, 16, 0, dtype=dtype, stats=None, scratch=None, nbytes=0) == 0
+    assert stats_fwd(2, 36, 16, 9, 1, dtype=1, stats=None) == bad and stats_fwd(1, 1032, 16, 24, 1, stats=None) == bad    # 4.5 packets of 8; above 1024 channels
+
+    def jf(N, Cc, HW, nhwc, dtype=0, a=p(), b=p(), y=p()):
+        return L.f3dg_residual_join_forward(None, dtype, nhwc, N, Cc, HW, a, p(), b, p(), 0.5, y)
+
+    for nhwc in (0, 1):
+        assert jf(2, 64, 16, nhwc, dtype=3) == bad and jf(2, 64, 16, nhwc, dtype=-1) == bad
+        for dtype in (0, 1, 2):
+            assert jf(2, 64, 16, nhwc, dtype, a=p(4)) == bad and jf(2, 64, 16, nhwc, dtype, b=p(4)) == bad and jf(2, 64, 16, nhwc, dtype, y=p(4)) == bad
+            assert jf(2, 64, 16, nhwc, dtype, a=None) == bad and jf(-1, 64, 16, nhwc, dtype) == bad and jf(2, 0, 16, nhwc, dtype) == bad
+            assert jf(0, 64, 16, nhwc, dtype) == 0
+    assert jf(1, 3, 5, 0) == bad and jf(3, 1, 3, 0) == bad and jf(2, 22, 16, 1) == bad and jf(2, 36, 16, 1, dtype=1) == bad      # no whole number of packets
 
     def jb(N, Cc, HW, nhwc, gy=p(), g=p(), gb=p(), scratch=p(), nbytes=big):
         return L.f3dg_residual_join_backward(None, N, Cc, HW, nhwc, gy, 0.5, g, gb, scratch, nbytes)

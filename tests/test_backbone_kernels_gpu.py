@@ -217,8 +217,7 @@ def _all_nan(t):
 @pytest.mark.parametrize("dt", DTYPES, ids=lambda d: NAME[d])
 def test_c_abi_refuses_what_the_kernels_cannot_take_and_writes_nothing(gpu_device, dt):
     L = _lib.lib()
-    sfx = gp._KERNEL_SUFFIX[dt]
-    gn, gn_cl, join = (getattr(L, n + sfx) for n in ("f3dg_group_norm_silu_pb", "f3dg_group_norm_silu_nhwc_pb", "f3dg_residual_join"))
+    kd = gp._KERNEL_DTYPE[dt]
     pn, dev = PN[dt], gpu_device
     big = 1032 * 16 + 64
     x = torch.ones(big, device=dev).to(dt)
@@ -229,13 +228,14 @@ def test_c_abi_refuses_what_the_kernels_cannot_take_and_writes_nothing(gpu_devic
     mom = torch.zeros(mom_bytes // 8, dtype=torch.float64, device=dev)
 
     def nchw(N, Cc, HW, groups, xo=0, yo=0):
-        return gn(_stream(), N, Cc, HW, groups, _off(x, xo), _off(pb), _off(w), _off(b), 1e-6, 1, _off(y, yo))
+        return L.f3dg_group_norm_silu_forward(_stream(), kd, 0, N, Cc, HW, groups, _off(x, xo), _off(pb), _off(w), _off(b), 1e-6, 1, _off(y, yo), None, None, 0)
 
     def nhwc(N, Cc, HW, groups, xo=0, yo=0):
-        return gn_cl(_stream(), N, Cc, HW, groups, _off(x, xo), _off(pb), _off(w), _off(b), 1e-6, 1, _off(y, yo), _off(mom), mom_bytes)
+        return L.f3dg_group_norm_silu_forward(_stream(), kd, 1, N, Cc, HW, groups, _off(x, xo), _off(pb), _off(w), _off(b), 1e-6, 1, _off(y, yo), None,
+                                              _off(mom), mom_bytes)
 
     def jn(N, Cc, HW, cl, ao=0, bo=0, yo=0):
-        return join(_stream(), N, Cc, HW, cl, _off(x, ao), _off(pb), _off(b2, bo), _off(pb), 0.5, _off(y, yo))
+        return L.f3dg_residual_join_forward(_stream(), kd, cl, N, Cc, HW, _off(x, ao), _off(pb), _off(b2, bo), _off(pb), 0.5, _off(y, yo))
 
     bad = _lib.ERR_BAD_ARG
     # a pointer 4 bytes off the 16-byte grid

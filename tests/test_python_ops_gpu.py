@@ -138,7 +138,7 @@ def test_cycle_loop_batched_equals_reference_shaped_loop(gpu_device):
 
 
 def test_group_norm_silu_kernel_matches_torch(gpu_device):
-    """f3dg_group_norm_silu vs torch.nn.functional.group_norm (+ silu) in float32 on the shapes the backbone uses."""
+    """f3dg_group_norm_silu_forward vs torch.nn.functional.group_norm (+ silu) in float32 on the shapes the backbone uses."""
     import torch.nn.functional as F
     from f3dgaus_amd.gaussian_predictor import GroupNorm
     torch.manual_seed(0)
@@ -309,7 +309,7 @@ def test_backbone_bf16_option(gpu_device):
 
 
 def test_group_norm_silu_channels_last_kernel(gpu_device):
-    """f3dg_group_norm_silu_nhwc(_bf16): the channels-last GroupNorm (+ SiLU) of the backbone's "nhwc" layout option against float64
+    """f3dg_group_norm_silu_forward, nhwc = 1: the channels-last GroupNorm (+ SiLU) of the backbone's "nhwc" layout option against float64
     torch, on the channel counts of the backbone (128 / 256 / 384 / 512: 16..128 packets per pixel, incl. the two that do not divide
     the workgroup) and on pixel counts that are not a multiple of a workgroup's run; the output stays channels-last."""
     import torch.nn.functional as F
@@ -352,10 +352,10 @@ def test_group_norm_channels_last_refuses_an_undersized_scratch(gpu_device):
     assert need > old
     mom = torch.zeros(need // 8 + 1, dtype=torch.float64, device=gpu_device)
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    args = (s, N, Cc, H * W, groups, _lib.ptr(x), _lib.ptr(w), _lib.ptr(b), 1e-6, 1, _lib.ptr(y), _lib.ptr(mom))
-    assert L.f3dg_group_norm_silu_nhwc(*args, old) == _lib.ERR_WORKSPACE
-    assert L.f3dg_group_norm_silu_nhwc(*args, need - 1) == _lib.ERR_WORKSPACE
-    assert L.f3dg_group_norm_silu_nhwc(*args, need) == 0
+    args = (s, 0, 1, N, Cc, H * W, groups, _lib.ptr(x), None, _lib.ptr(w), _lib.ptr(b), 1e-6, 1, _lib.ptr(y), None, _lib.ptr(mom))
+    assert L.f3dg_group_norm_silu_forward(*args, old) == _lib.ERR_WORKSPACE
+    assert L.f3dg_group_norm_silu_forward(*args, need - 1) == _lib.ERR_WORKSPACE
+    assert L.f3dg_group_norm_silu_forward(*args, need) == 0
     torch.cuda.synchronize()
     assert torch.isfinite(y).all()
 
@@ -364,7 +364,7 @@ def test_group_norm_channels_last_refuses_an_undersized_scratch(gpu_device):
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_conv_bias_folding_and_residual_join(dtype, gpu_device):
     """GroupNorm(pre_bias=) and residual_join() -- the kernels that take over the convolutions' bias passes and the residual add + scale
-    of a block (f3dg_group_norm_silu*_pb, f3dg_residual_join) -- against the unfused PyTorch expressions, in both layouts; and a whole
+    of a block (f3dg_group_norm_silu_forward, f3dg_residual_join_forward) -- against the unfused PyTorch expressions, in both layouts; and a whole
     residual block through the fused path against the same block through the unfused lines."""
     from f3dgaus_amd import gaussian_predictor as gp
     dt = torch.float32 if dtype == "fp32" else torch.bfloat16

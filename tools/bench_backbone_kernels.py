@@ -50,19 +50,20 @@ def main():
         HW, groups = H * W, 32
         torch.manual_seed(0)
         w, b, pb = torch.rand(Cc, device=dev) + 0.5, torch.rand(Cc, device=dev) - 0.5, torch.randn(Cc, device=dev) * 0.3
-        for dt, sfx in ((torch.float32, ""), (torch.bfloat16, "_bf16")):
+        for dt, kd in ((torch.float32, 0), (torch.bfloat16, 1)):            # F3DG_F32, F3DG_BF16
             x = (torch.randn(N * Cc * HW, device=dev) * 2 + 0.5).to(dt)
             for layout in ("nhwc", "nchw"):
                 outs, times, scratch = {}, {k: [] for k, _ in libs}, {}
 
                 def call(L, y):
+                    mom, nbytes = None, 0
                     if layout == "nhwc":
                         mom = scratch.get(id(L))                     # (each build sizes its own scratch)
                         if mom is None:
                             mom = scratch[id(L)] = torch.empty(L.f3dg_group_norm_nhwc_scratch_bytes(N, HW, groups) // 8 + 1, dtype=torch.float64, device=dev)
-                        rc = getattr(L, "f3dg_group_norm_silu_nhwc_pb" + sfx)(stream, N, Cc, HW, groups, p(x), p(pb), p(w), p(b), 1e-6, 1, p(y), p(mom), mom.numel() * 8)
-                    else:
-                        rc = getattr(L, "f3dg_group_norm_silu_pb" + sfx)(stream, N, Cc, HW, groups, p(x), p(pb), p(w), p(b), 1e-6, 1, p(y))
+                        nbytes = mom.numel() * 8
+                    rc = L.f3dg_group_norm_silu_forward(stream, kd, 1 if layout == "nhwc" else 0, N, Cc, HW, groups, p(x), p(pb), p(w), p(b), 1e-6, 1, p(y),
+                                                        None, p(mom) if mom is not None else None, nbytes)
                     assert rc == 0, rc
 
                 def measure(L, y):

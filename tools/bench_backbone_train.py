@@ -1,6 +1,6 @@
 """Times one backbone forward + backward under autograd at B = 8 images, 256 x 256, float32 (run on the GPU box): the torch route
 (``cfg['model']['backbone_autograd'] = 'torch'``: torch's GroupNorm / SiLU / bias / add operators between MIOpen's convolutions) against
-the fused route (``'fused'``: ``f3dg_group_norm_silu_stats`` / ``f3dg_group_norm_silu_backward`` / ``f3dg_residual_join(_backward)``) in both
+the fused route (``'fused'``: ``f3dg_group_norm_silu_forward`` / ``f3dg_group_norm_silu_backward`` / ``f3dg_residual_join_forward`` / ``_backward``) in both
 layouts; prints ONE JSON line and, with ``--markdown PATH``, writes the table of profiles/backbone_train.md.
 
 step      ``GaussianSplatPredictor_gtunet(..., head=False)`` on 8 images + ``backward`` of a fixed cotangent on ``net_out``, parameters'
@@ -69,8 +69,8 @@ def _kernel_calls(torch, dev):
         y, dx = torch.empty_like(xl), torch.empty_like(xl)
         stats = torch.empty(N, G, 2, device=dev)
         mom = torch.empty(L.f3dg_group_norm_nhwc_scratch_bytes(N, HW, G) // 8 + 1, dtype=torch.float64, device=dev)
-        _lib.check(L.f3dg_group_norm_silu_stats(_stream(), N, Cc, HW, G, nhwc, p(xl), p(pb), p(w), p(b), 1e-6, 1, p(y), p(stats), p(mom), mom.numel() * 8),
-                   "f3dg_group_norm_silu_stats")
+        _lib.check(L.f3dg_group_norm_silu_forward(_stream(), 0, nhwc, N, Cc, HW, G, p(xl), p(pb), p(w), p(b), 1e-6, 1, p(y), p(stats), p(mom), mom.numel() * 8),
+                   "f3dg_group_norm_silu_forward")
         scratch = torch.empty(L.f3dg_group_norm_silu_backward_scratch_bytes(N, Cc, HW, G, nhwc) // 8 + 1, dtype=torch.float64, device=dev)
         dw, db, dpb = (torch.empty(Cc, device=dev) for _ in range(3))
         args = (N, Cc, HW, G, nhwc, p(xl), p(pb), p(w), p(b), p(stats), 1, p(gl), p(dx), p(dw), p(db), p(dpb), p(scratch), scratch.numel() * 8)
