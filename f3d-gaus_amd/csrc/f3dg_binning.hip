@@ -1,7 +1,8 @@
-// f3dg_binning.hip -- tile binning: prefix sum, key duplication, stable LSD radix sort, tile ranges.
+// f3dg_binning.hip -- tile binning: block sums, key duplication, stable LSD radix sort, tile ranges.
 //
 // Replaces, for ALL views of a call at once (reference RAST/cuda_rasterizer/rasterizer_impl.cu):
-//   cub::DeviceScan::InclusiveSum      :332      -> scan_* kernels (hand-written reduce / scan / propagate)
+//   cub::DeviceScan::InclusiveSum      :332      -> sums per 256 depth positions + block_sums_scan_kernel / view_segments_kernel (placing the
+//                                                    instances); scan_* kernels (hand-written reduce / scan / propagate: the general scan)
 //   the blocking D2H of num_rendered   :336      -> count stays on the device (workspace header)
 //   duplicateWithKeys                  :70-111   -> duplicate_sorted_kernel
 //   cub::DeviceRadixSort::SortPairs    :358-363  -> gsort_* (depth, per Gaussian) and radix2_*_var (tile, per instance) passes of 8 bits
@@ -144,8 +145,8 @@ scan_apply_kernel(const u32* in, u32* out /* may alias in */, u64 n, const u32* 
 // Gaussian). A Gaussian's depth is the same in all its tiles, so the depth order is established once per (view, Gaussian) instead:
 //   1. gsort: stable LSD radix sort of each view's P Gaussians by their depth bits (4 passes of 8 bits over V*P keys; culled
 //      Gaussians get the key ~0 and produce no instances) -> perm[V][P], ascending (depth, Gaussian id);
-//   2. the tile rectangles gathered in that order, prefix sum of their areas, and the instances are GENERATED in (view, depth, id)
-//      order, as two streams: group (view << tile_bits | tile, u16 or u32) and Gaussian id;
+//   2. the tile rectangles gathered in that order, their areas summed per 256 positions and those sums scanned, and the instances are
+//      GENERATED in (view, depth, id) order, as two streams: group (view << tile_bits | tile, u16 or u32) and Gaussian id;
 //   3. stable pass(es) over the tile bits INSIDE every view's segment of the instance arrays: the result is in (view, tile, depth,
 //      id) order, i.e. the final list, and a view's instances never leave one XCD's L2;
 //   4. identifyTileRanges on the final group stream.
@@ -338,9 +339,10 @@ __device__ __forceinline__ void scatter_chunk(const K* __restrict__ keys_in, con
 // ---- equal segments of seg_len elements (the per-view depth sort of the Gaussians): one chunk per workgroup.
 // Pass 1 also finds every chunk's key range, reduced to every view's [kmin, kmax] (minmax[2 v], [2 v + 1]) by gsort_range_kernel. A view whose
 // range fits 2^24 above kbase = kmin & ~0xFFFF is "compact": its third pass sorts by (key - kbase) >> 16 and is its last, the fourth
-// returns at once (its histogram is a stand-in with the right sum so that the scan keeps the other views' positions), and the
-// view's order is the OUTPUT OF PASS 2 (see gsort_perm_is_pass2). Depth ranges within a factor of 2-4 -- object-centric cameras --
-// are compact; others take the four plain passes.
+// returns at once -- histogram, per-view scan and scatter; only under the general scan, which spans all views, its histogram is a
+// stand-in with the right sum so that the scan keeps the other views' positions --, and the view's order is the OUTPUT OF PASS 2
+// (see gsort_perm_is_pass2). Depth ranges within a factor of 2-4 -- object-centric cameras -- are compact; others take the four
+// plain passes.
 __device__ __forceinline__ SegChunk fixed_chunk(u32 seg_len, u32 cps)
 {
     u32 seg, c;
@@ -360,7 +362,7 @@ __device__ __forceinline__ bool gsort_compact(const u32* __restrict__ minmax, u3
 template <int PASS>
 __global__ void __launch_bounds__(F3DG_BLOCK)
 gsort_hist_kernel(const u32* __restrict__ keys, u32 seg_len, u32 cps, u32* __restrict__ hist, const u32* __restrict__ minmax,
-                  u32* __restrict__ chunk_minmax)
+                  u32* __restrict__ chunk_minmax, int standin /* pass 3 of a compact view: 1 when ONE scan spans all views */)
 {
     __shared__ u32 h[F3DG_BLOCK / 64][256];
     const SegChunk ck = fixed_chunk(seg_len, cps);
@@ -375,7 +377,7 @@ gsort_hist_kernel(const u32* __restrict__ keys, u32 seg_len, u32 cps, u32* __res
             hist_chunk<u32, ShiftDigit>(keys, ck, ShiftDigit{8 * PASS}, hist, h);
         } else if constexpr (PASS == 2) {
             hist_chunk<u32, CompactDigit>(keys, ck, CompactDigit{kbase}, hist, h);
-        } else {
+        } else if (standin) {
             const u64 base = (u64)ck.c * F3DG_SORT_CHUNK;
             const u32 in_chunk = (u32)((ck.n - base) < (u64)F3DG_SORT_CHUNK ? (ck.n - base) : (u64)F3DG_SORT_CHUNK);
             hist[ck.obase + (u64)threadIdx.x * ck.cps + ck.c] = threadIdx.x == 0 ? in_chunk : 0u;
@@ -387,10 +389,12 @@ gsort_hist_kernel(const u32* __restrict__ keys, u32 seg_len, u32 cps, u32* __res
 // position ranges are known in advance (seg_len each), so every view is scanned by its own workgroup -- one launch per pass
 // instead of the three of the general scan
 __global__ void __launch_bounds__(1024)
-gsort_scan_kernel(u32 n_per_seg /* 256 cps */, u32 seg_len, u32* __restrict__ hist)
+gsort_scan_kernel(u32 n_per_seg /* 256 cps */, u32 seg_len, u32* __restrict__ hist, const u32* __restrict__ skip_compact /* pass 3: minmax */)
 {
     __shared__ u32 wtot[16];
     __shared__ u32 carry_s;
+    u32 kbase;
+    if (skip_compact && gsort_compact(skip_compact, blockIdx.x, kbase)) return;      // nothing reads the table of a compact view's pass 3
     u32* h = hist + (size_t)blockIdx.x * n_per_seg;
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     if (threadIdx.x == 0) carry_s = blockIdx.x * seg_len;
@@ -460,21 +464,93 @@ gsort_scatter_kernel(const u32* __restrict__ keys_in, const u32* __restrict__ va
 
 // ---- the instances of every view (variable segments): persistent workgroups. Workgroup b belongs to XCD b % 8 and walks that
 // XCD's list of (view, chunk) pairs -- views x, x + 8, ... chunk by chunk -- with stride gridDim.x / 8.
-// vstart / bglob / xprefix from the prefix sum of tiles_touched in (view, depth) order; all zero chunks on overflow.
+
+// exclusive scan in place of one view's nb block sums (gsort_gather_rects_kernel), view-local; the view's total goes to view_total[view]
+// in 64 bits (a batch can hold more than 2^32 instances: V * P * tiles)
+__global__ void __launch_bounds__(1024)
+block_sums_scan_kernel(u32 nb, u32* __restrict__ block_sums, u64* __restrict__ view_total)
+{
+    __shared__ u32 wtot[16];
+    __shared__ u32 carry_s;
+    __shared__ u64 carry64_s, wtot64[16];
+    u32* b = block_sums + (size_t)blockIdx.x * nb;
+    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) { carry_s = 0; carry64_s = 0; }
+    __syncthreads();
+    for (u32 start = 0; start < nb; start += 1024u) {
+        const u32 i = start + threadIdx.x;
+        const u32 v = i < nb ? b[i] : 0u;
+        u32 x = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const u32 y = __shfl_up(x, off, 64);
+            if (lane >= (u32)off) x += y;
+        }
+        if (lane == 63u) wtot[wave] = x;
+        u64 v64 = v;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v64 += __shfl_down(v64, off, 64);
+        if (lane == 0u) wtot64[wave] = v64;
+        __syncthreads();
+        u32 before = carry_s + x - v;
+        for (u32 w = 0; w < wave; w++) before += wtot[w];
+        if (i < nb) b[i] = before;
+        __syncthreads();
+        if (threadIdx.x == 1023u) {
+            carry_s = before + v;
+            u64 t = 0;
+            for (int w = 0; w < 16; w++) t += wtot64[w];
+            carry64_s += t;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) view_total[blockIdx.x] = carry64_s;
+}
+
+// vstart / bglob / xprefix from the views' instance totals, and the call's status: the total of all views (64 bits: a wrapped 32-bit
+// total must not pass for a small one, later kernels index the instance arrays with it) against the capacity. All tables zero --
+// no chunks -- on overflow.
 __global__ void __launch_bounds__(512)
-view_segments_kernel(int V, int P, const u32* __restrict__ offsets_sorted, const F3dgHeader* __restrict__ hdr, u32* __restrict__ vstart,
+view_segments_kernel(int V, const u64* __restrict__ view_total, F3dgHeader* __restrict__ hdr, u32* __restrict__ vstart,
                      u32* __restrict__ bglob, u32* __restrict__ xprefix, u32 xstride)
 {
     __shared__ u32 carry;
     __shared__ u32 wtot[8];
+    __shared__ u64 carry64, wtot64[8];
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const bool dead = hdr->overflow != 0;
-    auto start_of = [&](u32 v) -> u32 {
-        const u64 i = (u64)v * (u64)P;
-        return (dead || i == 0) ? 0u : offsets_sorted[i - 1];
-    };
+    // first instance of every view (its low 32 bits are the whole of it unless the call overflows)
+    if (threadIdx.x == 0) carry64 = 0;
+    __syncthreads();
+    for (u32 v0 = 0; v0 < (u32)V; v0 += 512) {
+        const u32 v = v0 + threadIdx.x;
+        const u64 t = v < (u32)V ? view_total[v] : 0ull;
+        u64 x = t;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const u64 y = __shfl_up(x, off, 64);
+            if (lane >= (u32)off) x += y;
+        }
+        if (lane == 63) wtot64[wave] = x;
+        __syncthreads();
+        u64 woff = carry64;
+        for (u32 w = 0; w < wave; w++) woff += wtot64[w];
+        if (v < (u32)V) vstart[v] = (u32)(woff + x - t);
+        __syncthreads();
+        if (threadIdx.x == 511) carry64 = woff + x;
+        __syncthreads();
+    }
+    const u64 total = carry64;
+    const bool dead = total > (u64)hdr->capacity;
+    if (threadIdx.x == 0) {
+        hdr->num_rendered = total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)total;
+        hdr->overflow = dead ? 1u : 0u;
+        vstart[V] = dead ? 0u : (u32)total;
+    }
+    if (dead)
+        for (u32 v = threadIdx.x; v < (u32)V; v += 512) vstart[v] = 0u;
+    __syncthreads();
     auto chunks_of = [&](u32 v) -> u32 {
-        const u32 n = start_of(v + 1) - start_of(v);
+        const u32 n = vstart[v + 1] - vstart[v];
         return (n + F3DG_SORT_CHUNK - 1) / F3DG_SORT_CHUNK;
     };
     // global chunk prefix, view order
@@ -493,12 +569,12 @@ view_segments_kernel(int V, int P, const u32* __restrict__ offsets_sorted, const
         __syncthreads();
         u32 woff = carry;
         for (u32 w = 0; w < wave; w++) woff += wtot[w];
-        if (v < (u32)V) { vstart[v] = start_of(v); bglob[v] = woff + x - c; }
+        if (v < (u32)V) bglob[v] = woff + x - c;
         __syncthreads();
         if (threadIdx.x == 511) carry = woff + x;
         __syncthreads();
     }
-    if (threadIdx.x == 0) { vstart[V] = start_of((u32)V); bglob[V] = carry; }
+    if (threadIdx.x == 0) bglob[V] = carry;
     // per-XCD prefix: wave x scans the chunks of the views x, x + 8, ...
     const u32 nk = ((u32)V > wave) ? ((u32)V - wave + 7u) / 8u : 0u;
     u32 run = 0;
@@ -515,6 +591,58 @@ view_segments_kernel(int V, int P, const u32* __restrict__ offsets_sorted, const
         run += __shfl(x, 63, 64);
     }
     if (lane == 0) xprefix[wave * xstride + nk] = run;
+}
+
+// exclusive scan of one view's [256][chunks of the view] histogram block of a tile pass in place, starting from the view's first
+// instance (as gsort_scan_kernel: the views' output ranges are known, vstart). radix2_hist_var_kernel writes every entry of a live
+// block, so nothing is cleared beforehand and nothing outside the live blocks is touched -- but ranges_from_offsets_kernel reads the
+// entry after a view's block as the end of its digit 255: the first entry of the next view's block (= vstart of that view, and of
+// any view without instances in between), and behind the last block a sentinel that holds the total.
+__global__ void __launch_bounds__(1024)
+tile_scan_kernel(u32 V, const u32* __restrict__ vstart, const u32* __restrict__ bglob, u32* __restrict__ hist)
+{
+    constexpr u32 ITEMS = 16;                 // consecutive entries per thread: four 16-byte loads
+    __shared__ u32 wtot[16];
+    __shared__ u32 carry_s;
+    const u32 b0 = bglob[blockIdx.x], n = 256u * (bglob[blockIdx.x + 1] - b0);
+    u32* h = hist + 256ull * b0;
+    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (blockIdx.x == 0 && threadIdx.x == 0) hist[256ull * bglob[V]] = vstart[V];
+    if (threadIdx.x == 0) carry_s = vstart[blockIdx.x];
+    __syncthreads();
+    for (u32 base = 0; base < n; base += 1024u * ITEMS) {
+        const u32 i = base + ITEMS * threadIdx.x;             // n is a multiple of 256: whole groups of ITEMS
+        u32 v[ITEMS];
+#pragma unroll
+        for (u32 q = 0; q < ITEMS / 4; q++) {
+            const uint4 w = i < n ? reinterpret_cast<const uint4*>(h + i)[q] : make_uint4(0u, 0u, 0u, 0u);
+            v[4 * q] = w.x; v[4 * q + 1] = w.y; v[4 * q + 2] = w.z; v[4 * q + 3] = w.w;
+        }
+        u32 tot = 0;
+#pragma unroll
+        for (u32 q = 0; q < ITEMS; q++) tot += v[q];
+        u32 x = tot;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const u32 y = __shfl_up(x, off, 64);
+            if (lane >= (u32)off) x += y;
+        }
+        if (lane == 63u) wtot[wave] = x;
+        __syncthreads();
+        u32 run = carry_s + x - tot;
+        for (u32 w = 0; w < wave; w++) run += wtot[w];
+        if (i < n) {
+#pragma unroll
+            for (u32 q = 0; q < ITEMS / 4; q++) {
+                uint4 o;
+                o.x = run; run += v[4 * q]; o.y = run; run += v[4 * q + 1]; o.z = run; run += v[4 * q + 2]; o.w = run; run += v[4 * q + 3];
+                reinterpret_cast<uint4*>(h + i)[q] = o;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 1023u) carry_s = run;          // (the last thread's entries are live or all zero)
+        __syncthreads();
+    }
 }
 
 // identifyTileRanges when ONE pass sorted the tile bits: the scanned histogram already holds the first position of every
@@ -576,13 +704,23 @@ radix2_scatter_var_kernel(const K* __restrict__ keys_in, const u32* __restrict__
     }
 }
 
-// tile rectangles (written by the projection kernel: x = rminx | rmaxx << 16, y = rminy | rmaxy << 16) gathered into sorted order,
-// with their areas = tiles_touched as the input of the prefix sum that places the instances: the one random gather of the path
+// instances of a tile rectangle (written by the projection kernel: x = rminx | rmaxx << 16, y = rminy | rmaxy << 16) = its
+// tiles_touched. ONE definition: gsort_gather_rects_kernel reserves the output range that duplicate_sorted_kernel fills.
+__device__ __forceinline__ u32 rect_instances(u32 x, u32 y)
+{
+    const u32 rminx = x & F3DG_RECT_COORD, rmaxx = (x >> 16) & F3DG_RECT_COORD, rminy = y & F3DG_RECT_COORD, rmaxy = (y >> 16) & F3DG_RECT_COORD;
+    return (rmaxx > rminx && rmaxy > rminy) ? (rmaxx - rminx) * (rmaxy - rminy) : 0u;
+}
+
+// tile rectangles gathered into sorted order: the one random gather of the path. The instances are placed from the sums of their
+// counts over every F3DG_BLOCK consecutive depth positions of a view -- the 256 Gaussians of one duplicate_sorted_kernel workgroup --,
+// block_sums[view][nb]: the per-position counts never reach memory, duplicate_sorted_kernel rebuilds them from the rectangles.
 __global__ void __launch_bounds__(F3DG_BLOCK)
 gsort_gather_rects_kernel(int P, u32* __restrict__ gv0, u32* __restrict__ gv1, const u32* __restrict__ minmax,
-                          const uint2* __restrict__ rects, u32* __restrict__ tiles_sorted, u32* __restrict__ rx)
+                          const uint2* __restrict__ rects, u32* __restrict__ block_sums, u32* __restrict__ rx)
 {
     constexpr int ITEMS = 4;                  // four independent gathers in flight per thread
+    __shared__ u32 wsum[ITEMS][F3DG_BLOCK / 64];
     unsigned view, chunk;                     // a view's rectangles (8 P bytes) are gathered through one XCD's L2
     const unsigned cpv = (unsigned)((P + F3DG_BLOCK * ITEMS - 1) / (F3DG_BLOCK * ITEMS));
     f3dg_xcd_map(blockIdx.x, gridDim.x / cpv, cpv, view, chunk);
@@ -603,12 +741,20 @@ gsort_gather_rects_kernel(int P, u32* __restrict__ gv0, u32* __restrict__ gv1, c
     for (int i = 0; i < ITEMS; i++) {
         const int k = k0 + i * F3DG_BLOCK;
         if (k < P) {
-            tiles_sorted[vb + k] = (((r[i].x >> 16) & F3DG_RECT_COORD) - (r[i].x & F3DG_RECT_COORD)) *
-                                   (((r[i].y >> 16) & F3DG_RECT_COORD) - (r[i].y & F3DG_RECT_COORD));
             rx[vb + k] = r[i].x;
             ry[vb + k] = r[i].y;
         }
+        // item i of all threads is block ITEMS * chunk + i of the view (positions past P hold the empty rectangle)
+        u32 sum = rect_instances(r[i].x, r[i].y);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+        if ((threadIdx.x & 63) == 0) wsum[i][threadIdx.x >> 6] = sum;
     }
+    __syncthreads();
+    const unsigned nb = (unsigned)((P + F3DG_BLOCK - 1) / F3DG_BLOCK);
+    const unsigned blk = chunk * ITEMS + threadIdx.x;
+    if (threadIdx.x < ITEMS && blk < nb)
+        block_sums[(size_t)view * nb + blk] = wsum[threadIdx.x][0] + wsum[threadIdx.x][1] + wsum[threadIdx.x][2] + wsum[threadIdx.x][3];
 }
 
 // duplicateWithKeys in (view, depth, id) order: sorted position k of view v emits the tiles of Gaussian perm[v][k]. The runs of a
@@ -619,11 +765,12 @@ template <typename G>
 __global__ void __launch_bounds__(F3DG_BLOCK)
 duplicate_sorted_kernel(int P, int tile_bits, int grid_x, const u32* __restrict__ gv0, const u32* __restrict__ gv1,
                         const u32* __restrict__ minmax, const u32* __restrict__ rx,
-                        const u32* __restrict__ offsets_sorted,
+                        const u32* __restrict__ block_base /* [V][gridDim.x], view-local */, const u32* __restrict__ vstart /* or null */,
                         const F3dgHeader* __restrict__ hdr, G* __restrict__ kgrp, u32* __restrict__ vals)
 {
     __shared__ G sk[F3DG_DUP_CAP];
     __shared__ u32 sv[F3DG_DUP_CAP];
+    __shared__ u32 wtot[F3DG_BLOCK / 64];
     if (hdr->overflow) return;
     const int k = blockIdx.x * F3DG_BLOCK + threadIdx.x;
     const int v = blockIdx.y;
@@ -631,25 +778,35 @@ duplicate_sorted_kernel(int P, int tile_bits, int grid_x, const u32* __restrict_
     const bool pass2 = gsort_compact(minmax, (u32)v, kbase);      // as in gsort_gather_rects_kernel
     const u32* perm = pass2 ? gv1 : gv0;
     const u32* ry = pass2 ? gv0 : gv1;                             // the view's spare order buffer
-    // output range of the workgroup
-    const size_t first = (size_t)v * P + (size_t)blockIdx.x * F3DG_BLOCK;
-    const int in_block = min(F3DG_BLOCK, P - (int)(blockIdx.x * F3DG_BLOCK));
-    const u32 base = first == 0 ? 0u : offsets_sorted[first - 1];
-    const u32 n = offsets_sorted[first + in_block - 1] - base;
+    // output range of the workgroup: it starts at the view's first instance plus the instances of the view's earlier workgroups
+    // (vstart null: the bases are global already, binning_tail)
+    const u32 base = (vstart ? vstart[v] : 0u) + block_base[(size_t)v * gridDim.x + blockIdx.x];
     // the workgroup's output range [base, base + n) is assembled in LDS one window of F3DG_DUP_CAP instances at a time and written out
     // as whole lines: a thread emits the part of its Gaussian's run that falls into the window. (Until round 3 a workgroup whose
     // Gaussians cover more than one window wrote its runs directly -- a few bytes per lane, lines apart: with large splats, 24 tiles
     // per Gaussian at sigma0 = 0.05, that was every workgroup and the kernel ran at 1 TB/s.)
-    u32 off0 = 0, cnt = 0, x = 0, y = 0, g = 0;
+    u32 cnt = 0, x = 0, y = 0, g = 0;
     if (k < P) {
         const size_t pos = (size_t)v * P + k;
         x = rx[pos]; y = ry[pos];
-        const u32 rminx = x & F3DG_RECT_COORD, rmaxx = (x >> 16) & F3DG_RECT_COORD, rminy = y & F3DG_RECT_COORD, rmaxy = (y >> 16) & F3DG_RECT_COORD;
-        if (rmaxx > rminx && rmaxy > rminy) {
-            g = perm[pos];
-            off0 = ((pos == 0) ? 0 : offsets_sorted[pos - 1]) - base;
-            cnt = (rmaxx - rminx) * (rmaxy - rminy);
+        cnt = rect_instances(x, y);
+        if (cnt) g = perm[pos];
+    }
+    // a thread's run starts off0 instances into the range, which holds n: exclusive prefix and total of cnt over the workgroup
+    u32 off0, n;
+    {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        u32 incl = cnt;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const u32 t = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += t;
         }
+        if (lane == 63) wtot[wave] = incl;
+        __syncthreads();
+        off0 = incl - cnt;
+        for (int w = 0; w < wave; w++) off0 += wtot[w];
+        n = wtot[0] + wtot[1] + wtot[2] + wtot[3];
     }
     const u32 rminx = x & F3DG_RECT_COORD, rmaxx = (x >> 16) & F3DG_RECT_COORD, rminy = y & F3DG_RECT_COORD, rmaxy = (y >> 16) & F3DG_RECT_COORD;
     const u32 view_base = (u32)v << tile_bits;
@@ -790,9 +947,9 @@ static int binning_tail(hipStream_t s, int V, int P, int grid_x, int T, int tile
     u32* chunk_minmax = minmax + 2 * (size_t)V;
     const bool view_scan = cps <= 64;      // one workgroup per view (<= 4 rounds of 4096 entries) or the general three-kernel scan
 #define F3DG_GSORT_PASS(PASS, IN, OUT)                                                                                                     \
-    F3DG_KLAUNCH((gsort_hist_kernel<PASS>), dim3(gblocks), dim3(F3DG_BLOCK), 0, s, gk[IN], (u32)P, cps, hist, minmax, chunk_minmax); \
+    F3DG_KLAUNCH((gsort_hist_kernel<PASS>), dim3(gblocks), dim3(F3DG_BLOCK), 0, s, gk[IN], (u32)P, cps, hist, minmax, chunk_minmax, view_scan ? 0 : 1); \
     if (view_scan)                                                                                                                         \
-        F3DG_KLAUNCH(gsort_scan_kernel, dim3(V), dim3(1024), 0, s, 256u * cps, (u32)P, hist);                                       \
+        F3DG_KLAUNCH(gsort_scan_kernel, dim3(V), dim3(1024), 0, s, 256u * cps, (u32)P, hist, PASS == 3 ? minmax : (const u32*)nullptr); \
     else {                                                                                                                                 \
         rc = f3dg_launch_scan_inclusive(s, hist, hist, (unsigned long long)256 * gblocks, scan_tmp, L.scan_tmp_elems, 1, nullptr);        \
         if (rc != F3DG_OK) return rc;                                                                                                      \
@@ -805,30 +962,42 @@ static int binning_tail(hipStream_t s, int V, int P, int grid_x, int T, int tile
     F3DG_GSORT_PASS(3, 1, 0);
 #undef F3DG_GSORT_PASS
     // a view's order (perm) is gv[1] after pass 2 if its key range is compact, gv[0] after pass 3 otherwise; the other one takes ry
-    u32* offsets_sorted = gk[1];          // tiles_touched in sorted order, then its inclusive prefix sum (in place)
+    u32* block_sums = gk[1];              // [V][nb]: instances of every 256 consecutive depth positions, then their view-local exclusive prefix
     u32* rx = gk[0];
+    u64* view_total = reinterpret_cast<u64*>(chunk_minmax);      // (the chunks' key ranges are spent: gsort_range_kernel reduced them)
+    const u32 nb = (u32)((P + F3DG_BLOCK - 1) / F3DG_BLOCK);
+    SegTable st;
+    u32* segtab = reinterpret_cast<u32*>(ws + L.segtab);
+    const u32 xstride = (u32)V / 8u + 2u;
+    st.vstart = segtab; st.bglob = segtab + (V + 1); st.xprefix = segtab + 2 * (V + 1); st.xstride = xstride; st.V = (u32)V;
 
-    // 2. instances in (view, depth, id) order
+    // 2. instances in (view, depth, id) order: every workgroup of 256 depth positions gets its output range from the view's start
+    //    (view_segments_kernel, which also settles the call's total and overflow status) and the view-local prefix of the block sums
     F3DG_KLAUNCH(gsort_gather_rects_kernel, dim3((unsigned)V * (unsigned)((P + 4 * F3DG_BLOCK - 1) / (4 * F3DG_BLOCK))), dim3(F3DG_BLOCK), 0, s, P, gv[0], gv[1], minmax,
-                           reinterpret_cast<const uint2*>(ws + L.rects), offsets_sorted, rx);
-    rc = f3dg_launch_scan_inclusive(s, offsets_sorted, offsets_sorted, (unsigned long long)VP, scan_tmp, L.scan_tmp_elems, 0, hdr);
-    if (rc != F3DG_OK) return rc;
+                           reinterpret_cast<const uint2*>(ws + L.rects), block_sums, rx);
     const int passes = f3dg_sort_passes(V, T);
+    if (passes > 0) {
+        F3DG_KLAUNCH(block_sums_scan_kernel, dim3(V), dim3(1024), 0, s, nb, block_sums, view_total);
+        F3DG_KLAUNCH(view_segments_kernel, dim3(1), dim3(512), 0, s, V, view_total, hdr, segtab, segtab + (V + 1), segtab + 2 * (V + 1), xstride);
+    } else {
+        // a one-tile image has no tile pass and no use for the segment tables: the general scan over the (short) array of block sums
+        // makes the bases global and settles the status
+        rc = f3dg_launch_scan_inclusive(s, block_sums, block_sums, (unsigned long long)V * nb, scan_tmp, L.scan_tmp_elems, 1, hdr);
+        if (rc != F3DG_OK) return rc;
+    }
     int src = passes & 1;                                                      // so that the tile pass(es) end in half 0
-    F3DG_KLAUNCH((duplicate_sorted_kernel<G>), pgrid, dim3(F3DG_BLOCK), 0, s, P, tile_bits, grid_x, gv[0], gv[1], minmax, rx, offsets_sorted, hdr,
-                       kgrp[src], vals[src]);
+    F3DG_KLAUNCH((duplicate_sorted_kernel<G>), pgrid, dim3(F3DG_BLOCK), 0, s, P, tile_bits, grid_x, gv[0], gv[1], minmax, rx, block_sums,
+                       passes > 0 ? segtab : (const u32*)nullptr, hdr, kgrp[src], vals[src]);
 
     // 3. stable pass(es) over the tile bits inside every view's segment of the instance arrays: (view, tile, depth, id) order
     if (passes > 0) {
-        SegTable st;
-        u32* segtab = reinterpret_cast<u32*>(ws + L.segtab);
-        const u32 xstride = (u32)V / 8u + 2u;
-        st.vstart = segtab; st.bglob = segtab + (V + 1); st.xprefix = segtab + 2 * (V + 1); st.xstride = xstride; st.V = (u32)V;
-        F3DG_KLAUNCH(view_segments_kernel, dim3(1), dim3(512), 0, s, V, P, offsets_sorted, hdr, segtab, segtab + (V + 1),
-                           segtab + 2 * (V + 1), xstride);
         const size_t nbmax = (size_t)L.sort_blocks + (size_t)V;                // >= sum over the views of ceil(instances / chunk)
         const u32 per_xcd = (u32)((nbmax + 7) / 8 < 160 ? (nbmax + 7) / 8 : 160);   // 5 workgroups per CU of the scatter's LDS
         const u32 per_xcd_h = (u32)((nbmax + 7) / 8 < 512 ? (nbmax + 7) / 8 : 512);
+        // the scan of a pass's histogram: one workgroup per view over the view's live block (16,384 entries = 64 chunks a round) while
+        // a view of average size -- by the capacity, which is all the host knows -- takes at most 8 rounds; otherwise (few views of
+        // very many instances) the general scan over the whole cleared table, whose zero tail also yields the end of the last digit
+        const bool tile_view_scan = nbmax <= (size_t)512 * (size_t)V;
         // two passes (257..65,536 tiles: 512^2 images have 1,024): the tile bits are split EVENLY, 5 + 5 instead of 8 + 2 -- a pass costs
         // the same whatever its digit width, and a chunk's runs of equal digits, which leave LDS as coalesced stores, are 8 x longer
         // with 32 digits than with 256
@@ -836,10 +1005,14 @@ static int binning_tail(hipStream_t s, int V, int P, int grid_x, int T, int tile
         for (int p = 0; p < passes; p++) {
             const int shift = split * p;
             const u32 mask = passes == 2 ? (1u << (p == 0 ? split : tile_bits - split)) - 1u : 255u;
-            F3DG_HIP_CHECK(hipMemsetAsync(hist, 0, sizeof(u32) * 256 * nbmax, s));
+            if (!tile_view_scan) F3DG_HIP_CHECK(hipMemsetAsync(hist, 0, sizeof(u32) * 256 * nbmax, s));
             F3DG_KLAUNCH((radix2_hist_var_kernel<G>), dim3(8 * per_xcd_h), dim3(F3DG_BLOCK), 0, s, kgrp[src], st, shift, mask, hist);
-            rc = f3dg_launch_scan_inclusive(s, hist, hist, (unsigned long long)256 * nbmax, scan_tmp, L.scan_tmp_elems, 1, nullptr);
-            if (rc != F3DG_OK) return rc;
+            if (tile_view_scan)
+                F3DG_KLAUNCH(tile_scan_kernel, dim3(V), dim3(1024), 0, s, (u32)V, st.vstart, st.bglob, hist);
+            else {
+                rc = f3dg_launch_scan_inclusive(s, hist, hist, (unsigned long long)256 * nbmax, scan_tmp, L.scan_tmp_elems, 1, nullptr);
+                if (rc != F3DG_OK) return rc;
+            }
             // (a single pass: the group stream is not needed again, the ranges come from the scanned histogram)
             F3DG_KLAUNCH((radix2_scatter_var_kernel<G>), dim3(8 * per_xcd), dim3(F3DG_BLOCK), 0, s, kgrp[src], vals[src],
                                passes == 1 ? (G*)nullptr : kgrp[src ^ 1], vals[src ^ 1], st, shift, mask, hist);
