@@ -82,13 +82,16 @@ SIGNATURES = {
     "f3dg_compose_frames_size": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_sz)]),
     # the backbone between the convolutions: stream dtype nhwc N C HW (groups) | ...
     "f3dg_group_norm_silu_forward": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _f, _i, _p, _p, _p, _sz]),
+    "f3dg_group_norm_silu_forward_stats": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _f, _i, _p, _p, _p, _sz]),
     "f3dg_residual_join_forward": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _f, _p]),
     "f3dg_group_norm_nhwc_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
     # training through the backbone: the adjoints (stream N C HW groups nhwc | ...)
     "f3dg_group_norm_silu_backward_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "f3dg_group_norm_silu_backward": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _sz]),
+    "f3dg_group_norm_silu_backward_dtype": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _sz]),
     "f3dg_residual_join_backward_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "f3dg_residual_join_backward": (_i, [_p, _i, _i, _i, _i, _p, _f, _p, _p, _p, _sz]),
+    "f3dg_residual_join_backward_dtype": (_i, [_p, _i, _i, _i, _i, _i, _p, _f, _p, _p, _p, _sz]),
     # n_planes W H  /  stream | n_planes W H | img1 img2 | map dm_dmu1 dm_dsigma1_sq dm_dsigma12 | partials partials_bytes plane_sums
     "f3dg_ssim_partials_bytes": (_sz, [_i, _i, _i]),
     "f3dg_ssim_forward": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),

@@ -358,14 +358,31 @@ extern "C" size_t f3dg_group_norm_nhwc_scratch_bytes(int N, int HW, int groups)
 }
 
 // 16-bit activations travel as unsigned short (bfloat16) or _Float16
+static int gn_forward(void* stream, int dtype, int nhwc, int N, int C, int HW, int groups, const void* x, const float* pre_bias, const float* weight,
+                      const float* bias, float eps, int apply_silu, void* y, float* stats, void* scratch, size_t scratch_bytes)
+{
+    if (dtype < F3DG_F32 || dtype > F3DG_F16 || ((uintptr_t)stats & 7u)) return F3DG_ERR_BAD_ARG;
+    const auto launch = dtype == F3DG_F32 ? launch_gn<float> : dtype == F3DG_BF16 ? launch_gn<unsigned short> : launch_gn<_Float16>;
+    return launch(stream, nhwc, N, C, HW, groups, x, pre_bias, weight, bias, eps, apply_silu, y, reinterpret_cast<float2*>(stats), scratch, scratch_bytes);
+}
+
 extern "C" int f3dg_group_norm_silu_forward(void* stream, int dtype, int nhwc, int N, int C, int HW, int groups, const void* x, const float* pre_bias,
                                             const float* weight, const float* bias, float eps, int apply_silu, void* y, float* stats, void* scratch,
                                             size_t scratch_bytes)
 {
-    // the statistics are kept for the backward, which is float32 only
-    if (dtype < F3DG_F32 || dtype > F3DG_F16 || (stats && (dtype != F3DG_F32 || ((uintptr_t)stats & 7u)))) return F3DG_ERR_BAD_ARG;
-    const auto launch = dtype == F3DG_F32 ? launch_gn<float> : dtype == F3DG_BF16 ? launch_gn<unsigned short> : launch_gn<_Float16>;
-    return launch(stream, nhwc, N, C, HW, groups, x, pre_bias, weight, bias, eps, apply_silu, y, reinterpret_cast<float2*>(stats), scratch, scratch_bytes);
+    // this entry point keeps the statistics of a float32 call only, as it always has; f3dg_group_norm_silu_forward_stats keeps them in every type
+    if (stats && dtype != F3DG_F32) return F3DG_ERR_BAD_ARG;
+    return gn_forward(stream, dtype, nhwc, N, C, HW, groups, x, pre_bias, weight, bias, eps, apply_silu, y, stats, scratch, scratch_bytes);
+}
+
+// the same launch with the (mean, rstd) pairs kept for f3dg_group_norm_silu_backward_dtype, in every type: the templated kernels hand
+// stats_out through, y is the plain forward's to the bit
+extern "C" int f3dg_group_norm_silu_forward_stats(void* stream, int dtype, int nhwc, int N, int C, int HW, int groups, const void* x, const float* pre_bias,
+                                                  const float* weight, const float* bias, float eps, int apply_silu, void* y, float* stats, void* scratch,
+                                                  size_t scratch_bytes)
+{
+    if (!stats) return F3DG_ERR_BAD_ARG;
+    return gn_forward(stream, dtype, nhwc, N, C, HW, groups, x, pre_bias, weight, bias, eps, apply_silu, y, stats, scratch, scratch_bytes);
 }
 
 extern "C" int f3dg_residual_join_forward(void* stream, int dtype, int nhwc, int N, int C, int HW, const void* a, const float* bias_a, const void* b,

@@ -1,5 +1,5 @@
-// f3dg_groupnorm_bwd.hip -- the adjoints of f3dg_groupnorm.hip, float32 activations, both layouts: what training through the backbone
-// needs between MIOpen's convolutions (f3dg_group_norm_silu_backward, f3dg_residual_join_backward).
+// f3dg_groupnorm_bwd.hip -- the adjoints of f3dg_groupnorm.hip, float32, bfloat16 and float16 activations, both layouts: what training
+// through the backbone needs between MIOpen's convolutions (f3dg_group_norm_silu_backward[_dtype], f3dg_residual_join_backward[_dtype]).
 //
 // GroupNorm (+ SiLU), recomputed from x: with v = x + pre_bias, xh = (v - mean) * rstd, z = weight * xh + bias, m = Cg * HW,
 //   dz = dy * s * (1 + z * (1 - s)), s = sigmoid(z)                 (dz = dy without SiLU)
@@ -12,6 +12,11 @@
 // float32 over short runs (a packet in NCHW, a thread's pixels of a run channels-last, as the forward's moments) and combined in float64
 // in a fixed order: no floating-point atomics anywhere, the gradients are bit-identical from run to run.
 // Nothing but x is needed from the forward: neither its output nor the normalised pre-activation is kept.
+//
+// T = float, unsigned short holding bfloat16, or _Float16, as in the forward: x, dy and dx are T (16-byte packets of 4 or 8 values), the
+// parameters, the statistics and every parameter gradient float32. A 16-bit value is widened exactly on the way in, all arithmetic and
+// all sums are those of the float32 kernel, and dx is rounded to T once on the way out (from_f32: to nearest even, an fp16 result
+// beyond the type's range becomes +-Inf, which is how a loss scaler sees an overflow). Nothing is rounded before it enters a sum.
 #include "f3dg_common.h"
 #include "f3dg_groupnorm.h"
 
@@ -41,12 +46,13 @@ struct GnBwdScratch {
 // butterfly per wave, the 16 waves added in order by thread 0, which also carries s1 and s2. Stage 2 re-reads x and dy and writes dx. The
 // re-read comes from L2 only where the two slabs fit beside those of the XCD's other workgroups: at 256^2 (2 x 1 MiB per slab) a counter
 // pass shows both reads leaving the L2, 20 B per element in all, as the channels-last kernels move (profiles/backbone_train.md).
+template <typename T>
 __global__ void __launch_bounds__(GN_THREADS)
-gn_bwd_nchw_kernel(int C, int HW, int groups, const float* __restrict__ x, const float* __restrict__ pre_bias, const float* __restrict__ weight,
-                   const float* __restrict__ bias, const float2* __restrict__ stats, int apply_silu, const float* __restrict__ dy,
-                   float* __restrict__ dx, double* __restrict__ nc, double* __restrict__ sg)
+gn_bwd_nchw_kernel(int C, int HW, int groups, const T* __restrict__ x, const float* __restrict__ pre_bias, const float* __restrict__ weight,
+                   const float* __restrict__ bias, const float2* __restrict__ stats, int apply_silu, const T* __restrict__ dy,
+                   T* __restrict__ dx, double* __restrict__ nc, double* __restrict__ sg)
 {
-    constexpr int PN = 4, NW = GN_THREADS / 64;
+    constexpr int PN = Packet<T>::N, NW = GN_THREADS / 64;
     const int g = blockIdx.x % groups;
     const int n = blockIdx.x / groups;
     const int Cg = C / groups;
@@ -63,12 +69,12 @@ gn_bwd_nchw_kernel(int C, int HW, int groups, const float* __restrict__ x, const
         const int c = g * Cg + j;
         const GnChan ch = gn_chan(c, st, pre_bias, weight, bias);
         const float wc = weight[c];
-        const float* xs = x + base + (size_t)j * HW;
-        const float* ds = dy + base + (size_t)j * HW;
+        const T* xs = x + base + (size_t)j * HW;
+        const T* ds = dy + base + (size_t)j * HW;
         double a = 0.0, b = 0.0, xx = 0.0;
         if (vec) {
             for (int i = threadIdx.x; i < hwp; i += GN_THREADS) {
-                Packet<float> px, pd;
+                Packet<T> px, pd;
                 px.load(xs + (size_t)i * PN);
                 pd.load(ds + (size_t)i * PN);
                 float fa = 0.0f, fb = 0.0f, fx = 0.0f;
@@ -83,7 +89,7 @@ gn_bwd_nchw_kernel(int C, int HW, int groups, const float* __restrict__ x, const
         } else {
             for (int i = threadIdx.x; i < HW; i += GN_THREADS) {
                 float dz, xh;
-                gn_bwd_elem(xs[i], ds[i], ch, apply_silu, dz, xh);
+                gn_bwd_elem(to_f32(xs[i]), to_f32(ds[i]), ch, apply_silu, dz, xh);
                 a += (double)dz; b += (double)(dz * xh); xx += (double)xh;
             }
         }
@@ -118,7 +124,7 @@ gn_bwd_nchw_kernel(int C, int HW, int groups, const float* __restrict__ x, const
             const int c = g * Cg + gn_nchw_chan(i, hwp, idx32);
             const GnChan ch = gn_chan(c, st, pre_bias, weight, bias);
             const float wc = weight[c];
-            Packet<float> px, pd;
+            Packet<T> px, pd;
             px.load(x + base + i * PN);
             pd.load(dy + base + i * PN);
 #pragma unroll
@@ -134,8 +140,8 @@ gn_bwd_nchw_kernel(int C, int HW, int groups, const float* __restrict__ x, const
             const int c = g * Cg + gn_nchw_chan(i, HW, idx32);
             const float wc = weight[c];
             float dz, xh;
-            gn_bwd_elem(x[base + i], dy[base + i], gn_chan(c, st, pre_bias, weight, bias), apply_silu, dz, xh);
-            dx[base + i] = rstd * ((dz * wc - s1) - xh * s2);
+            gn_bwd_elem(to_f32(x[base + i]), to_f32(dy[base + i]), gn_chan(c, st, pre_bias, weight, bias), apply_silu, dz, xh);
+            from_f32(dx[base + i], rstd * ((dz * wc - s1) - xh * s2));
         }
     }
 }
@@ -147,12 +153,13 @@ gn_bwd_nchw_kernel(int C, int HW, int groups, const float* __restrict__ x, const
 // gn_bwd_nhwc_finish_kernel: ONE WAVE per (sample, group) adds the blocks of each of its channels -- lane l takes blocks l, l + 64, ...
 //     in order, then a fixed butterfly -- and leaves (A, B, X) per (n, c) and (s1, s2) per (n, g);
 // gn_bwd_nhwc_apply_kernel: the same mapping as the first, one pass: dx.
+template <typename T>
 __global__ void __launch_bounds__(256)
-gn_bwd_nhwc_partial_kernel(int C, int HW, int groups, int rows, const float* __restrict__ x, const float* __restrict__ pre_bias,
+gn_bwd_nhwc_partial_kernel(int C, int HW, int groups, int rows, const T* __restrict__ x, const float* __restrict__ pre_bias,
                            const float* __restrict__ weight, const float* __restrict__ bias, const float2* __restrict__ stats, int apply_silu,
-                           const float* __restrict__ dy, double* __restrict__ part)
+                           const T* __restrict__ dy, double* __restrict__ part)
 {
-    constexpr int PN = 4;
+    constexpr int PN = Packet<T>::N;
     const GnNhwcRun r = gn_nhwc_run<PN>(C, HW);
     float a[PN], b[PN], xx[PN];
 #pragma unroll
@@ -161,8 +168,8 @@ gn_bwd_nhwc_partial_kernel(int C, int HW, int groups, int rows, const float* __r
         GnChan ch[PN];
         gn_nhwc_chan(ch, r, C / groups, groups, pre_bias, weight, bias, stats);
         const size_t base = ((size_t)r.n * HW) * C + (size_t)r.col * PN;
-        const float* const in[2] = { x + base, dy + base };
-        gn_nhwc_walk(r, rows, C, in, [&](const Packet<float> (&q)[2], size_t) {
+        const T* const in[2] = { x + base, dy + base };
+        gn_nhwc_walk(r, rows, C, in, [&](const Packet<T> (&q)[2], size_t) {
 #pragma unroll
             for (int k = 0; k < PN; k++) {
                 float dz, xh;
@@ -208,12 +215,13 @@ gn_bwd_nhwc_finish_kernel(int N, int C, int HW, int groups, int nb, const float*
     }
 }
 
+template <typename T>
 __global__ void __launch_bounds__(256)
-gn_bwd_nhwc_apply_kernel(int C, int HW, int groups, int rows, const float* __restrict__ x, const float* __restrict__ pre_bias,
+gn_bwd_nhwc_apply_kernel(int C, int HW, int groups, int rows, const T* __restrict__ x, const float* __restrict__ pre_bias,
                          const float* __restrict__ weight, const float* __restrict__ bias, const float2* __restrict__ stats, int apply_silu,
-                         const float* __restrict__ dy, const double* __restrict__ sg, float* __restrict__ dx)
+                         const T* __restrict__ dy, const double* __restrict__ sg, T* __restrict__ dx)
 {
-    constexpr int PN = 4;
+    constexpr int PN = Packet<T>::N;
     const GnNhwcRun r = gn_nhwc_run<PN>(C, HW);
     if (r.row >= rows) return;
     const int Cg = C / groups;
@@ -229,8 +237,8 @@ gn_bwd_nhwc_apply_kernel(int C, int HW, int groups, int rows, const float* __res
         s2[k] = (float)s[1];
     }
     const size_t base = ((size_t)r.n * HW) * C + (size_t)r.col * PN;
-    const float* const in[2] = { x + base, dy + base };
-    gn_nhwc_walk(r, rows, C, in, [&](Packet<float> (&q)[2], size_t off) {
+    const T* const in[2] = { x + base, dy + base };
+    gn_nhwc_walk(r, rows, C, in, [&](Packet<T> (&q)[2], size_t off) {
 #pragma unroll
         for (int k = 0; k < PN; k++) {
             float dz, xh;
@@ -272,36 +280,38 @@ size_t gn_bwd_scratch_doubles(int N, int C, int HW, int groups, int nhwc)
 
 // ---- the residual join's adjoint --------------------------------------------------------------------------------------------------
 // y = ((a + bias_a) + (b + bias_b)) * scale: da = db = grad_y * scale, written ONCE; dbias_a = dbias_b = its per-channel sum. One pass over
-// grad_y: a workgroup writes its piece of grad_y * scale and the float64 sum of what it wrote per channel (part[segment][C]); a wave per
-// channel then adds the segments in a fixed order.
+// grad_y: a workgroup writes its piece of grad_y * scale, rounded to T once, and the float64 sum per channel of the float32 products
+// themselves -- for T = float what it wrote -- (part[segment][C]); a wave per channel then adds the segments in a fixed order.
 //   NCHW: a segment is up to JOIN_BWD_CHUNK consecutive values of one (n, c) plane;
 //   channels-last: a segment is a run of JOIN_BWD_PIX pixels of the N * HW, all channels, thread (row, col) as in the GroupNorm kernels.
 constexpr int JOIN_BWD_CHUNK = 4096;
 constexpr int JOIN_BWD_PIX = 256;
 
+template <typename T>
 __global__ void __launch_bounds__(256)
-join_bwd_nchw_kernel(int C, int HW, int cpp, int vec, const float* gy, float scale, float* gab, double* __restrict__ part)
+join_bwd_nchw_kernel(int C, int HW, int cpp, int vec, const T* gy, float scale, T* gab, double* __restrict__ part)
 {
+    constexpr int PN = Packet<T>::N;
     const int c = blockIdx.x % C;
     const int seg = blockIdx.x / C;
     const int n = seg / cpp, k0 = (seg % cpp) * JOIN_BWD_CHUNK;
     const int k1 = min(k0 + JOIN_BWD_CHUNK, HW);
     const size_t base = ((size_t)n * C + c) * HW;
     double s = 0.0;
-    if (vec) {                                                    // HW a multiple of 4: planes and chunks start on 16-byte boundaries
-        for (int i = k0 + threadIdx.x * 4; i < k1; i += 256 * 4) {
-            Packet<float> p;
+    if (vec) {                                                    // HW a multiple of the packet: planes and chunks start on 16-byte boundaries
+        for (int i = k0 + threadIdx.x * PN; i < k1; i += 256 * PN) {
+            Packet<T> p;
             p.load(gy + base + i);
             float f = 0.0f;
 #pragma unroll
-            for (int k = 0; k < 4; k++) { p.v[k] = p.v[k] * scale; f += p.v[k]; }
+            for (int k = 0; k < PN; k++) { p.v[k] = p.v[k] * scale; f += p.v[k]; }
             p.store(gab + base + i);
             s += (double)f;
         }
     } else {
         for (int i = k0 + threadIdx.x; i < k1; i += 256) {
-            const float v = gy[base + i] * scale;
-            gab[base + i] = v;
+            const float v = to_f32(gy[base + i]) * scale;
+            from_f32(gab[base + i], v);
             s += (double)v;
         }
     }
@@ -313,18 +323,21 @@ join_bwd_nchw_kernel(int C, int HW, int cpp, int vec, const float* gy, float sca
     if (threadIdx.x == 0) part[(size_t)seg * C + c] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
 }
 
+template <typename T>
 __global__ void __launch_bounds__(256)
-join_bwd_nhwc_kernel(int C, size_t P, int rows, const float* gy, float scale, float* gab, double* __restrict__ part)
+join_bwd_nhwc_kernel(int C, size_t P, int rows, const T* gy, float scale, T* gab, double* __restrict__ part)
 {
-    constexpr int PN = 4;
+    constexpr int PN = Packet<T>::N;
     const int ppp = C / PN;
     const int col = threadIdx.x % ppp, row = threadIdx.x / ppp;
     const size_t p0 = (size_t)blockIdx.x * JOIN_BWD_PIX;
     const size_t p1 = p0 + JOIN_BWD_PIX < P ? p0 + JOIN_BWD_PIX : P;
-    double s[PN] = { 0.0, 0.0, 0.0, 0.0 };
+    double s[PN];
+#pragma unroll
+    for (int k = 0; k < PN; k++) s[k] = 0.0;
     if (row < rows) {
         for (size_t p = p0 + row; p < p1; p += rows) {
-            Packet<float> q;
+            Packet<T> q;
             q.load(gy + p * C + (size_t)col * PN);
 #pragma unroll
             for (int k = 0; k < PN; k++) { q.v[k] = q.v[k] * scale; s[k] += (double)q.v[k]; }
@@ -353,22 +366,18 @@ size_t join_bwd_segments(int N, int HW, int nhwc)
     return (size_t)N * ((HW + JOIN_BWD_CHUNK - 1) / JOIN_BWD_CHUNK);
 }
 
-} // namespace
-
-extern "C" size_t f3dg_group_norm_silu_backward_scratch_bytes(int N, int C, int HW, int groups, int nhwc)
+template <typename T>
+int launch_gn_bwd(void* stream, int N, int C, int HW, int groups, int nhwc, const void* x_, const float* pre_bias, const float* weight, const float* bias,
+                  const float* stats, int apply_silu, const void* grad_y_, void* grad_x_, float* grad_weight, float* grad_bias, float* grad_pre_bias,
+                  void* scratch, size_t scratch_bytes)
 {
-    if (N <= 0 || C <= 0 || HW <= 0 || groups <= 0) return 0;
-    return sizeof(double) * gn_bwd_scratch_doubles(N, C, HW, groups, nhwc);
-}
-
-extern "C" int f3dg_group_norm_silu_backward(void* stream, int N, int C, int HW, int groups, int nhwc, const float* x, const float* pre_bias,
-                                             const float* weight, const float* bias, const float* stats, int apply_silu, const float* grad_y,
-                                             float* grad_x, float* grad_weight, float* grad_bias, float* grad_pre_bias, void* scratch,
-                                             size_t scratch_bytes)
-{
-    const int rc = gn_check_args(N, C, HW, groups, nhwc, 4, x && weight && bias && stats && grad_y && scratch, scratch_bytes,
-                                 f3dg_group_norm_silu_backward_scratch_bytes(N, C, HW, groups, nhwc), (uintptr_t)x | (uintptr_t)grad_y | (uintptr_t)grad_x,
-                                 (uintptr_t)stats | (uintptr_t)scratch);
+    constexpr int PN = Packet<T>::N;
+    const T* x = static_cast<const T*>(x_);
+    const T* grad_y = static_cast<const T*>(grad_y_);
+    T* grad_x = static_cast<T*>(grad_x_);
+    const size_t need = (N > 0 && C > 0 && HW > 0 && groups > 0) ? sizeof(double) * gn_bwd_scratch_doubles(N, C, HW, groups, nhwc) : 0;
+    const int rc = gn_check_args(N, C, HW, groups, nhwc, PN, x && weight && bias && stats && grad_y && scratch, scratch_bytes, need,
+                                 (uintptr_t)x | (uintptr_t)grad_y | (uintptr_t)grad_x, (uintptr_t)stats | (uintptr_t)scratch);
     if (rc != F3DG_OK || N == 0) return rc;
     if ((long long)N * groups > 0x7FFFFFFFll || (nhwc && N > 65535)) return F3DG_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -378,16 +387,16 @@ extern "C" int f3dg_group_norm_silu_backward(void* stream, int N, int C, int HW,
     w.sg = w.nc + 3 * (size_t)N * C;
     w.part = w.sg + 2 * (size_t)N * groups;
     if (!nhwc) {
-        F3DG_KLAUNCH(gn_bwd_nchw_kernel, dim3((unsigned)(N * groups)), dim3(GN_THREADS), 0, s, C, HW, groups, x, pre_bias, weight, bias, st, apply_silu,
+        F3DG_KLAUNCH(gn_bwd_nchw_kernel<T>, dim3((unsigned)(N * groups)), dim3(GN_THREADS), 0, s, C, HW, groups, x, pre_bias, weight, bias, st, apply_silu,
                      grad_y, grad_x, w.nc, w.sg);
     } else {
-        const int ppp = C / 4, rows = 256 / ppp;
+        const int ppp = C / PN, rows = 256 / ppp;
         const int nb = (HW + gn_nhwc_pix(HW) - 1) / gn_nhwc_pix(HW);
         const dim3 grid((unsigned)nb, (unsigned)N);
-        F3DG_KLAUNCH(gn_bwd_nhwc_partial_kernel, grid, dim3(256), 0, s, C, HW, groups, rows, x, pre_bias, weight, bias, st, apply_silu, grad_y, w.part);
+        F3DG_KLAUNCH(gn_bwd_nhwc_partial_kernel<T>, grid, dim3(256), 0, s, C, HW, groups, rows, x, pre_bias, weight, bias, st, apply_silu, grad_y, w.part);
         F3DG_KLAUNCH(gn_bwd_nhwc_finish_kernel, dim3((unsigned)((N * groups + 3) / 4)), dim3(256), 0, s, N, C, HW, groups, nb, weight, w.part, w.nc, w.sg);
         if (grad_x)
-            F3DG_KLAUNCH(gn_bwd_nhwc_apply_kernel, grid, dim3(256), 0, s, C, HW, groups, rows, x, pre_bias, weight, bias, st, apply_silu, grad_y, w.sg, grad_x);
+            F3DG_KLAUNCH(gn_bwd_nhwc_apply_kernel<T>, grid, dim3(256), 0, s, C, HW, groups, rows, x, pre_bias, weight, bias, st, apply_silu, grad_y, w.sg, grad_x);
     }
     if (grad_weight || grad_bias || grad_pre_bias)
         F3DG_KLAUNCH(gn_bwd_params_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, N, C, HW, groups, weight, st, w.nc, w.sg, grad_weight,
@@ -396,35 +405,82 @@ extern "C" int f3dg_group_norm_silu_backward(void* stream, int N, int C, int HW,
     return F3DG_OK;
 }
 
+template <typename T>
+int launch_join_bwd(void* stream, int N, int C, int HW, int nhwc, const void* grad_y_, float scale, void* grad_ab_, float* grad_bias, void* scratch,
+                    size_t scratch_bytes)
+{
+    constexpr int PN = Packet<T>::N;
+    const T* grad_y = static_cast<const T*>(grad_y_);
+    T* grad_ab = static_cast<T*>(grad_ab_);
+    if (N < 0 || C <= 0 || HW <= 0 || !grad_y || !grad_ab) return F3DG_ERR_BAD_ARG;
+    const size_t total = (size_t)N * C * HW;
+    if (total == 0) return F3DG_OK;
+    if (total % PN != 0 || (((uintptr_t)grad_y | (uintptr_t)grad_ab) & 15u)) return F3DG_ERR_BAD_ARG;
+    if (nhwc && (C % PN != 0 || C / PN > 256 || C > GN_NHWC_MAXC)) return F3DG_ERR_BAD_ARG;
+    const size_t nseg = join_bwd_segments(N, HW, nhwc);
+    if (grad_bias) {
+        if (!scratch || ((uintptr_t)scratch & 7u)) return F3DG_ERR_BAD_ARG;
+        if (scratch_bytes < sizeof(double) * nseg * (size_t)C) return F3DG_ERR_WORKSPACE;
+    }
+    if (nseg * (nhwc ? 1 : (size_t)C) > 0x7FFFFFFFull) return F3DG_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    double* part = grad_bias ? static_cast<double*>(scratch) : nullptr;
+    if (nhwc)
+        F3DG_KLAUNCH(join_bwd_nhwc_kernel<T>, dim3((unsigned)nseg), dim3(256), 0, s, C, (size_t)N * HW, 256 / (C / PN), grad_y, scale, grad_ab, part);
+    else
+        F3DG_KLAUNCH(join_bwd_nchw_kernel<T>, dim3((unsigned)(nseg * C)), dim3(256), 0, s, C, HW, (HW + JOIN_BWD_CHUNK - 1) / JOIN_BWD_CHUNK, HW % PN == 0 ? 1 : 0,
+                     grad_y, scale, grad_ab, part);
+    if (grad_bias)
+        F3DG_KLAUNCH(join_bwd_finish_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, C, nseg, part, grad_bias);
+    F3DG_HIP_CHECK(hipGetLastError());
+    return F3DG_OK;
+}
+
+} // namespace
+
+// (neither scratch depends on the activation type: the partial sums are float64 per channel whatever the packets hold)
+extern "C" size_t f3dg_group_norm_silu_backward_scratch_bytes(int N, int C, int HW, int groups, int nhwc)
+{
+    if (N <= 0 || C <= 0 || HW <= 0 || groups <= 0) return 0;
+    return sizeof(double) * gn_bwd_scratch_doubles(N, C, HW, groups, nhwc);
+}
+
+extern "C" int f3dg_group_norm_silu_backward_dtype(void* stream, int dtype, int N, int C, int HW, int groups, int nhwc, const void* x, const float* pre_bias,
+                                                   const float* weight, const float* bias, const float* stats, int apply_silu, const void* grad_y,
+                                                   void* grad_x, float* grad_weight, float* grad_bias, float* grad_pre_bias, void* scratch,
+                                                   size_t scratch_bytes)
+{
+    if (dtype < F3DG_F32 || dtype > F3DG_F16) return F3DG_ERR_BAD_ARG;
+    const auto launch = dtype == F3DG_F32 ? launch_gn_bwd<float> : dtype == F3DG_BF16 ? launch_gn_bwd<unsigned short> : launch_gn_bwd<_Float16>;
+    return launch(stream, N, C, HW, groups, nhwc, x, pre_bias, weight, bias, stats, apply_silu, grad_y, grad_x, grad_weight, grad_bias, grad_pre_bias, scratch,
+                  scratch_bytes);
+}
+
+extern "C" int f3dg_group_norm_silu_backward(void* stream, int N, int C, int HW, int groups, int nhwc, const float* x, const float* pre_bias,
+                                             const float* weight, const float* bias, const float* stats, int apply_silu, const float* grad_y,
+                                             float* grad_x, float* grad_weight, float* grad_bias, float* grad_pre_bias, void* scratch,
+                                             size_t scratch_bytes)
+{
+    return f3dg_group_norm_silu_backward_dtype(stream, F3DG_F32, N, C, HW, groups, nhwc, x, pre_bias, weight, bias, stats, apply_silu, grad_y, grad_x,
+                                               grad_weight, grad_bias, grad_pre_bias, scratch, scratch_bytes);
+}
+
 extern "C" size_t f3dg_residual_join_backward_scratch_bytes(int N, int C, int HW, int nhwc)
 {
     if (N <= 0 || C <= 0 || HW <= 0) return 0;
     return sizeof(double) * join_bwd_segments(N, HW, nhwc) * (size_t)C;
 }
 
+extern "C" int f3dg_residual_join_backward_dtype(void* stream, int dtype, int N, int C, int HW, int nhwc, const void* grad_y, float scale, void* grad_ab,
+                                                 float* grad_bias, void* scratch, size_t scratch_bytes)
+{
+    if (dtype < F3DG_F32 || dtype > F3DG_F16) return F3DG_ERR_BAD_ARG;
+    const auto launch = dtype == F3DG_F32 ? launch_join_bwd<float> : dtype == F3DG_BF16 ? launch_join_bwd<unsigned short> : launch_join_bwd<_Float16>;
+    return launch(stream, N, C, HW, nhwc, grad_y, scale, grad_ab, grad_bias, scratch, scratch_bytes);
+}
+
 extern "C" int f3dg_residual_join_backward(void* stream, int N, int C, int HW, int nhwc, const float* grad_y, float scale, float* grad_ab,
                                            float* grad_bias, void* scratch, size_t scratch_bytes)
 {
-    if (N < 0 || C <= 0 || HW <= 0 || !grad_y || !grad_ab) return F3DG_ERR_BAD_ARG;
-    const size_t total = (size_t)N * C * HW;
-    if (total == 0) return F3DG_OK;
-    if (total % 4 != 0 || (((uintptr_t)grad_y | (uintptr_t)grad_ab) & 15u)) return F3DG_ERR_BAD_ARG;
-    if (nhwc && (C % 4 != 0 || C / 4 > 256)) return F3DG_ERR_BAD_ARG;
-    if (grad_bias) {
-        if (!scratch || ((uintptr_t)scratch & 7u)) return F3DG_ERR_BAD_ARG;
-        if (scratch_bytes < f3dg_residual_join_backward_scratch_bytes(N, C, HW, nhwc)) return F3DG_ERR_WORKSPACE;
-    }
-    const size_t nseg = join_bwd_segments(N, HW, nhwc);
-    if (nseg * (nhwc ? 1 : (size_t)C) > 0x7FFFFFFFull) return F3DG_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    double* part = grad_bias ? static_cast<double*>(scratch) : nullptr;
-    if (nhwc)
-        F3DG_KLAUNCH(join_bwd_nhwc_kernel, dim3((unsigned)nseg), dim3(256), 0, s, C, (size_t)N * HW, 256 / (C / 4), grad_y, scale, grad_ab, part);
-    else
-        F3DG_KLAUNCH(join_bwd_nchw_kernel, dim3((unsigned)(nseg * C)), dim3(256), 0, s, C, HW, (HW + JOIN_BWD_CHUNK - 1) / JOIN_BWD_CHUNK, HW % 4 == 0 ? 1 : 0,
-                     grad_y, scale, grad_ab, part);
-    if (grad_bias)
-        F3DG_KLAUNCH(join_bwd_finish_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, C, nseg, part, grad_bias);
-    F3DG_HIP_CHECK(hipGetLastError());
-    return F3DG_OK;
+    return f3dg_residual_join_backward_dtype(stream, F3DG_F32, N, C, HW, nhwc, grad_y, scale, grad_ab, grad_bias, scratch, scratch_bytes);
 }

@@ -139,17 +139,18 @@ def _gn_nhwc_ok(x):
     return _is_nhwc(x) and x.shape[1] % (4 if x.dtype == torch.float32 else 8) == 0 and x.shape[1] <= 1024 and x.data_ptr() % 16 == 0
 
 
-def _dense_like(g, nhwc):
-    """The cotangent in the layout the kernels read, float32, 16-byte aligned."""
-    g = g.float()
+def _dense_like(g, nhwc, dtype):
+    """The cotangent in the type and layout the kernels read (``dtype``: the activations' own), 16-byte aligned."""
+    g = g.to(dtype)
     g = g.contiguous(memory_format=torch.channels_last) if nhwc else g.contiguous()
     return g.clone() if g.data_ptr() % 16 else g
 
 
 def _gn_forward(x, pre_bias, weight, bias, groups, eps, silu, keep_stats=False):
     """``f3dg_group_norm_silu_forward`` on ``x`` as it lies where the channels-last kernels take it (channels-last out), on a dense
-    16-byte aligned NCHW copy otherwise. Returns ``(x as the kernel read it, y, nhwc, stats)``; ``keep_stats`` (float32 only) keeps the
-    (mean, rstd) pair per (sample, group) that the backward normalises with."""
+    16-byte aligned NCHW copy otherwise. Returns ``(x as the kernel read it, y, nhwc, stats)``; ``keep_stats``
+    (``f3dg_group_norm_silu_forward_stats``: the same launch and the same ``y`` in every dtype) keeps the float32 (mean, rstd) pair per
+    (sample, group) that the backward normalises with."""
     L = _lib.lib()
     nhwc = _gn_nhwc_ok(x)
     if not nhwc:
@@ -164,16 +165,18 @@ def _gn_forward(x, pre_bias, weight, bias, groups, eps, silu, keep_stats=False):
     if nhwc:
         scratch = torch.empty(L.f3dg_group_norm_nhwc_scratch_bytes(N, HW, groups) // 8 + 1, dtype=torch.float64, device=x.device)
         nbytes = scratch.numel() * 8
-    rc = L.f3dg_group_norm_silu_forward(_stream(), _KERNEL_DTYPE[x.dtype], 1 if nhwc else 0, N, Cc, HW, groups, _lib.ptr(x), _lib.ptr(pre_bias),
-                                        _lib.ptr(weight), _lib.ptr(bias), float(eps), 1 if silu else 0, _lib.ptr(y), _lib.ptr(stats), _lib.ptr(scratch), nbytes)
-    _lib.check(rc, "f3dg_group_norm_silu_forward")
+    name = "f3dg_group_norm_silu_forward_stats" if keep_stats else "f3dg_group_norm_silu_forward"
+    rc = getattr(L, name)(_stream(), _KERNEL_DTYPE[x.dtype], 1 if nhwc else 0, N, Cc, HW, groups, _lib.ptr(x), _lib.ptr(pre_bias),
+                          _lib.ptr(weight), _lib.ptr(bias), float(eps), 1 if silu else 0, _lib.ptr(y), _lib.ptr(stats), _lib.ptr(scratch), nbytes)
+    _lib.check(rc, name)
     return x, y, nhwc, stats
 
 
 class _GroupNormSiLU(torch.autograd.Function):
-    """``f3dg_group_norm_silu_forward`` keeping its statistics, with ``f3dg_group_norm_silu_backward`` behind it (float32, NCHW or
-    channels-last). Saved: ``x``, the parameters and the (mean, rstd) pair per (sample, group) -- not the output and not the normalised
-    pre-activation, which the backward kernel recomputes from ``x``."""
+    """``f3dg_group_norm_silu_forward_stats`` with ``f3dg_group_norm_silu_backward_dtype`` behind it (float32, bfloat16 or float16
+    activations, NCHW or channels-last). Saved: ``x`` in its own dtype, the float32 parameters and the float32 (mean, rstd) pair per
+    (sample, group) -- not the output and not the normalised pre-activation, which the backward kernel recomputes from ``x``. The
+    cotangent is brought to ``x``'s dtype, ``grad_x`` has it, the three parameter gradients are float32."""
 
     @staticmethod
     def forward(ctx, x, pre_bias, weight, bias, groups, eps, silu):
@@ -189,7 +192,7 @@ class _GroupNormSiLU(torch.autograd.Function):
         L = _lib.lib()
         N, Cc = x.shape[0], x.shape[1]
         HW = x.numel() // (N * Cc)
-        gy = _dense_like(gy, ctx.nhwc)
+        gy = _dense_like(gy, ctx.nhwc, x.dtype)
         need = ctx.needs_input_grad
         new = lambda: torch.empty(Cc, dtype=torch.float32, device=x.device)
         dx = torch.empty_like(x) if need[0] else None
@@ -198,10 +201,11 @@ class _GroupNormSiLU(torch.autograd.Function):
         db = new() if need[3] else None
         nbytes = L.f3dg_group_norm_silu_backward_scratch_bytes(N, Cc, HW, ctx.groups, 1 if ctx.nhwc else 0)
         scratch = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=x.device)
-        rc = L.f3dg_group_norm_silu_backward(_stream(), N, Cc, HW, ctx.groups, 1 if ctx.nhwc else 0, _lib.ptr(x), _lib.ptr(pre_bias), _lib.ptr(weight),
-                                             _lib.ptr(bias), _lib.ptr(stats), 1 if ctx.silu else 0, _lib.ptr(gy), _lib.ptr(dx), _lib.ptr(dw),
-                                             _lib.ptr(db), _lib.ptr(dpb), _lib.ptr(scratch), scratch.numel() * 8)
-        _lib.check(rc, "f3dg_group_norm_silu_backward")
+        rc = L.f3dg_group_norm_silu_backward_dtype(_stream(), _KERNEL_DTYPE[x.dtype], N, Cc, HW, ctx.groups, 1 if ctx.nhwc else 0, _lib.ptr(x),
+                                                   _lib.ptr(pre_bias), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(stats), 1 if ctx.silu else 0,
+                                                   _lib.ptr(gy), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(dpb), _lib.ptr(scratch),
+                                                   scratch.numel() * 8)
+        _lib.check(rc, "f3dg_group_norm_silu_backward_dtype")
         return dx, dpb, dw, db, None, None, None
 
 
@@ -213,22 +217,23 @@ def _join_forward(a, bias_a, b, bias_b, scale, y, nhwc):
 
 
 class _ResidualJoin(torch.autograd.Function):
-    """``f3dg_residual_join_forward`` out of place with ``f3dg_residual_join_backward`` behind it: nothing is saved, the backward is one pass over
-    the cotangent whose result is the gradient of ``a`` and of ``b`` alike, and whose per-channel sum is the gradient of either bias."""
+    """``f3dg_residual_join_forward`` out of place with ``f3dg_residual_join_backward_dtype`` behind it: nothing is saved, the backward is one
+    pass over the cotangent (in the activations' dtype) whose result is the gradient of ``a`` and of ``b`` alike, and whose per-channel
+    float32 sum is the gradient of either bias."""
 
     @staticmethod
     def forward(ctx, a, bias_a, b, bias_b, scale):
         nhwc = _is_nhwc(a)
         y = torch.empty_like(a)
         _join_forward(a, bias_a, b, bias_b, scale, y, nhwc)
-        ctx.nhwc, ctx.scale = nhwc, float(scale)
+        ctx.nhwc, ctx.scale, ctx.dtype = nhwc, float(scale), a.dtype
         return y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         L = _lib.lib()
-        gy = _dense_like(gy, ctx.nhwc)
+        gy = _dense_like(gy, ctx.nhwc, ctx.dtype)
         N, Cc, H, W = gy.shape
         need = ctx.needs_input_grad
         g = torch.empty_like(gy)
@@ -237,9 +242,9 @@ class _ResidualJoin(torch.autograd.Function):
             gb = torch.empty(Cc, dtype=torch.float32, device=gy.device)
             nbytes = L.f3dg_residual_join_backward_scratch_bytes(N, Cc, H * W, 1 if ctx.nhwc else 0)
             scratch = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=gy.device)
-        rc = L.f3dg_residual_join_backward(_stream(), N, Cc, H * W, 1 if ctx.nhwc else 0, _lib.ptr(gy), ctx.scale, _lib.ptr(g), _lib.ptr(gb),
-                                           _lib.ptr(scratch), scratch.numel() * 8 if scratch is not None else 0)
-        _lib.check(rc, "f3dg_residual_join_backward")
+        rc = L.f3dg_residual_join_backward_dtype(_stream(), _KERNEL_DTYPE[ctx.dtype], N, Cc, H * W, 1 if ctx.nhwc else 0, _lib.ptr(gy), ctx.scale,
+                                                 _lib.ptr(g), _lib.ptr(gb), _lib.ptr(scratch), scratch.numel() * 8 if scratch is not None else 0)
+        _lib.check(rc, "f3dg_residual_join_backward_dtype")
         # (each bias parameter gets a tensor of its own to keep as .grad)
         return (g if need[0] else None), (gb if need[1] else None), (g if need[2] else None), ((gb.clone() if need[1] else gb) if need[3] else None), None
 
@@ -254,23 +259,23 @@ class GroupNorm(nn.Module):
         self.bias = nn.Parameter(torch.zeros(num_channels))
 
     def _fusable(self, x):
-        """A HIP device and a dtype the kernels take: the fused HIP kernels run -- in inference always; under autograd only with the
-        ``fused_autograd`` switch on and in float32 (16-bit backbones are inference-only)."""
+        """A HIP device and a dtype the kernels take (float32, bfloat16, float16): the fused HIP kernels run -- in inference always; under
+        autograd only with the ``fused_autograd`` switch on."""
         if not (x.is_cuda and x.dtype in _KERNEL_DTYPE and x.dim() >= 3 and x.numel() > 0 and self.weight.dtype == torch.float32):
             return False
         if not (torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad)):
             return True
-        return self.fused_autograd and x.dtype == torch.float32
+        return self.fused_autograd
 
     def forward(self, x, N_views_xa=1, silu=False, pre_bias=None):
         """``silu=True`` returns ``F.silu(group_norm(x))``: the pair the residual blocks always apply together. In
         inference on a HIP device the pair is ONE fused kernel (``f3dg_group_norm_silu_forward``); with autograd
         or on the host (the CPU fixtures of the backbone) it is the two PyTorch ops -- unless ``fused_autograd`` is set
-        (``set_fused_autograd``), when float32 tensors on a HIP device take the kernels under autograd too, with
-        ``f3dg_group_norm_silu_backward`` behind them. ``pre_bias`` ([C] float32): the result is
+        (``set_fused_autograd``), when float32, bfloat16 and float16 tensors on a HIP device take the kernels under autograd too, with
+        ``f3dg_group_norm_silu_backward_dtype`` behind them (``grad_x`` in ``x``'s dtype, float32 parameter gradients). ``pre_bias`` ([C] float32): the result is
         that of ``x + pre_bias[None, :, None, None]`` -- the bias of the convolution that produced ``x`` (``Conv2d.forward(bias=False)``)."""
         if self._fusable(x) and (pre_bias is None or pre_bias.dtype == torch.float32):
-            if self.fused_autograd and x.dtype == torch.float32 and self.bias.dtype == torch.float32 and torch.is_grad_enabled() and any(
+            if self.fused_autograd and self.bias.dtype == torch.float32 and torch.is_grad_enabled() and any(
                     t is not None and t.requires_grad for t in (x, pre_bias, self.weight, self.bias)):
                 return _GroupNormSiLU.apply(x, pre_bias, self.weight, self.bias, self.num_groups, float(self.eps), bool(silu))
             return _gn_forward(x, pre_bias, self.weight, self.bias, self.num_groups, self.eps, silu)[1]
@@ -283,13 +288,13 @@ class GroupNorm(nn.Module):
 def residual_join(a, bias_a, b, bias_b, scale, fused_autograd=False):
     """((a + bias_a) + (b + bias_b)) * scale with per-channel biases (either may be None): the tail of a residual block. One HIP
     kernel (``f3dg_residual_join_forward``) for inference tensors on a HIP device that share a dense layout (NCHW or channels-last); the
-    PyTorch ops otherwise. Writes into ``a``'s storage when it can. ``fused_autograd=True``: under autograd float32 tensors take the
-    kernel as well, out of place, with ``f3dg_residual_join_backward`` behind it."""
+    PyTorch ops otherwise. Writes into ``a``'s storage when it can. ``fused_autograd=True``: under autograd tensors of the kernels' three
+    dtypes take the kernel as well, out of place, with ``f3dg_residual_join_backward_dtype`` behind it."""
     def tb(t, bias):
         return t if bias is None else t + bias.to(t.dtype).reshape(1, -1, 1, 1)
     grad = fused_autograd and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (a, b, bias_a, bias_b))
     ok = (a.is_cuda and a.dim() == 4 and a.dtype in _KERNEL_DTYPE and b.dtype == a.dtype and a.shape == b.shape
-          and (a.dtype == torch.float32 if grad else not (torch.is_grad_enabled() and (a.requires_grad or b.requires_grad)))
+          and (grad or not (torch.is_grad_enabled() and (a.requires_grad or b.requires_grad)))
           and all(t is None or (t.dtype == torch.float32 and t.is_contiguous()) for t in (bias_a, bias_b))
           and a.numel() % (4 if a.dtype == torch.float32 else 8) == 0)
     if ok:
@@ -334,7 +339,7 @@ class UNetBlock(nn.Module):
             # inference on a HIP device: the three convolutions run without their biases, which go to the kernels that read the results
             # (norm1 takes conv0's; the residual join takes conv1's and the skip convolution's, adds, and scales): same float32
             # operations in the same order as the lines below, five elementwise passes fewer. With the fused_autograd switch the same
-            # route under autograd (float32): the biases get their gradients from those kernels' adjoints
+            # route under autograd (float32 or 16-bit activations): the biases get their gradients from those kernels' adjoints
             x = self.conv0(self.norm0(x, silu=True), bias=False)
             x = self.norm1(x, silu=True, pre_bias=self.conv0.bias)
             if self.training:
@@ -357,7 +362,13 @@ class UNetBlock(nn.Module):
             b, c = x.shape[0], x.shape[1]
             qkv = self.qkv(self.norm2(x)).reshape(b, c, 3, -1)          # channel index = c*3 + {q,k,v}
             q, k, v = (t.transpose(1, 2).unsqueeze(1).float() for t in qkv.unbind(2))      # [b,1,L,c]
-            a = F.scaled_dot_product_attention(q, k, v)                  # softmax(q k^T / sqrt(c)) v, fp32
+            # softmax(q k^T / sqrt(c)) v, fp32. Training through the fused route with 16-bit activations runs under torch.autocast, which
+            # would cast q, k, v back to 16 bits inside the operator: attention stays float32 there, so autocast is off around it
+            if x.is_cuda and self.fused_autograd and torch.is_grad_enabled() and x.dtype in _HALF_DTYPES:
+                with torch.autocast("cuda", enabled=False):
+                    a = F.scaled_dot_product_attention(q, k, v)
+            else:
+                a = F.scaled_dot_product_attention(q, k, v)
             a = a.squeeze(1).transpose(1, 2).to(x.dtype).reshape(*x.shape)
             if _is_nhwc(x):
                 a = a.contiguous(memory_format=torch.channels_last)
@@ -371,7 +382,7 @@ class UNetBlock(nn.Module):
 def set_fused_autograd(module, on=True):
     """Switches every ``GroupNorm`` and ``UNetBlock`` below ``module`` (itself included) between the two backbone routes under autograd:
     ``on`` = GroupNorm (+ SiLU) and the residual join as HIP kernels forward and backward, the convolutions without their bias passes
-    (float32 on a HIP device; anything else still takes the torch operators); off (the default of a new module) = torch's operators
+    (float32, bfloat16 or float16 activations on a HIP device; anything else still takes the torch operators); off (the default of a new module) = torch's operators
     whenever a gradient is wanted. Inference is the fused kernels either way. Returns ``module``."""
     for mod in module.modules():
         if isinstance(mod, (GroupNorm, UNetBlock)):
@@ -690,13 +701,25 @@ class GaussianSplatPredictor_gtunet(nn.Module):
         if self.backbone_layout not in ("auto", "nchw", "nhwc"):
             raise ValueError("backbone_layout must be 'auto', 'nchw' or 'nhwc'")
         # extension: what the backbone's GroupNorm (+ SiLU), bias and residual-join passes run as UNDER AUTOGRAD: "torch" (default) =
-        # torch's operators, as ever; "fused" = the HIP kernels forward and backward (set_fused_autograd: float32 only -- the 16-bit
-        # options stay inference-only), and an explicit backbone_layout "nhwc" is then honoured under autograd too ("auto" stays NCHW)
+        # torch's operators, as ever; "fused" = the HIP kernels forward and backward (set_fused_autograd), and an explicit
+        # backbone_layout "nhwc" is then honoured under autograd too ("auto" stays NCHW)
         self.backbone_autograd = str(m.get('backbone_autograd', 'torch'))
         if self.backbone_autograd not in ("torch", "fused"):
             raise ValueError("backbone_autograd must be 'torch' or 'fused'")
         if self.backbone_autograd == "fused":
             set_fused_autograd(self.network_with_offset, True)
+        # extension: the precision of the backbone UNDER AUTOGRAD on a HIP device (backbone_dtype above is the inference option and keeps
+        # its meaning): "fp32" (default) as ever; "bf16" / "fp16" = mixed-precision training through the fused route -- the backbone under
+        # torch.autocast with 16-bit activations between the layers, GroupNorm+SiLU and the residual join as the 16-bit HIP kernels
+        # forward and backward, the result cast to float32 before the splat head. GroupNorm statistics, attention and the splat head
+        # stay float32; the parameters stay float32 master weights and receive float32 gradients. fp16 leaves loss scaling to the caller:
+        # a gradient beyond float16's range leaves the kernels as +-Inf, never clamped, which is what torch.amp.GradScaler looks for
+        self.backbone_train_dtype = str(m.get('backbone_train_dtype', 'fp32'))
+        if self.backbone_train_dtype not in ("fp32", "bf16", "fp16"):
+            raise ValueError("backbone_train_dtype must be 'fp32', 'bf16' or 'fp16'")
+        if self.backbone_train_dtype != "fp32" and self.backbone_autograd != "fused":
+            raise ValueError("backbone_train_dtype = '%s' needs backbone_autograd = 'fused' (it is '%s'): the 16-bit training route is "
+                             "the fused kernels'" % (self.backbone_train_dtype, self.backbone_autograd))
         self.init_ray_dirs()
         self.init_sh_transform_matrices()
 
@@ -737,7 +760,11 @@ class GaussianSplatPredictor_gtunet(nn.Module):
         ``out`` / ``n_offset`` (extension): write into preallocated aggregated buffers [B, n_total, ...];
         requires Nv == 1 so that image b's Gaussians stay contiguous.
         ``head=False`` (extension): stop before the splat head and return ``(net_out [B*Nv,23,H,W], depth [B*Nv,1,H,W])``, what
-        ``splat_head`` / ``splat_head_merge`` take -- the training form of the cycle aggregation merges several passes in one node."""
+        ``splat_head`` / ``splat_head_merge`` take -- the training form of the cycle aggregation merges several passes in one node.
+        Under autograd on a HIP device ``cfg['model']['backbone_train_dtype']`` = ``'bf16'`` / ``'fp16'`` (with ``backbone_autograd =
+        'fused'``) runs the backbone under ``torch.autocast`` with 16-bit activations through the fused kernels forward and backward;
+        ``net_out`` is float32 either way and every parameter receives a float32 gradient. fp16 leaves loss scaling to the caller: scale
+        the loss (``torch.amp.GradScaler`` works), an overflowing gradient shows as +-Inf, never as a clamped value."""
         assert focals_pixels is None, "Unexpected argument for srn dataset"
         assert source_cv2wT_quat is not None
         assert unet_depth is not None, "F3D-Gaus feeds the (monocular or rendered) depth map as unet_depth"
@@ -747,7 +774,9 @@ class GaussianSplatPredictor_gtunet(nn.Module):
         v2w = source_cameras_view_to_world.reshape(B * Nv, 4, 4)
         quat = source_cv2wT_quat.reshape(B * Nv, 4)
         inference = x.is_cuda and not torch.is_grad_enabled()
-        half = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(self.backbone_dtype) if inference else None
+        # 16-bit activations: the inference option without autograd, the training option (fused route only) under it
+        half = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(
+            self.backbone_dtype if inference else self.backbone_train_dtype if x.is_cuda else "fp32")
 
         def backbone(xc):
             # ("auto": measured crossover -- fp32 25.9 against 26.4 ms at two images, bf16 11.5 against 10.8 at two and 24.2 against 25.4 at eight)

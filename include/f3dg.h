@@ -476,7 +476,7 @@ enum { F3DG_F32 = 0, F3DG_BF16 = 1, F3DG_F16 = 2 };
  * Both layouts sum (v - K) and (v - K)^2, K the first value of the (sample, group), so that the variance keeps torch's float32 accuracy
  * when a group's mean is far from zero (measured up to |mean| / std = 100 and on constant groups: tests/test_backbone_kernels_gpu.py).
  * `stats` (may be NULL; F3DG_F32 only, 8-byte aligned): [N, groups, 2] float32 = (mean, 1 / sqrt(var + eps)) per (sample, group), kept
- * for f3dg_group_norm_silu_backward; y is the same with and without it.
+ * for f3dg_group_norm_silu_backward; y is the same with and without it. (f3dg_group_norm_silu_forward_stats keeps them in every dtype.)
  * `scratch` / `scratch_bytes`: channels-last only (NULL / 0 with nhwc = 0), f3dg_group_norm_nhwc_scratch_bytes(N, HW, groups) bytes: one
  * (sum, sum of squares) pair per workgroup, sample and group, added up in workgroup order by a second-stage kernel -- no atomics, the
  * statistics are bit-reproducible from run to run. `scratch_bytes` is the size of the buffer behind `scratch`: the scratch has grown with
@@ -488,13 +488,23 @@ size_t f3dg_group_norm_nhwc_scratch_bytes(int N, int HW, int groups);
 int f3dg_group_norm_silu_forward(void* stream, int dtype, int nhwc, int N, int C, int HW, int groups,
                                  const void* x, const float* pre_bias, const float* weight, const float* bias,
                                  float eps, int apply_silu, void* y, float* stats, void* scratch, size_t scratch_bytes);
+/* f3dg_group_norm_silu_forward keeping its statistics in EVERY dtype, for f3dg_group_norm_silu_backward_dtype: the same launch, y the same
+ * bit for bit as f3dg_group_norm_silu_forward writes with the same arguments, and `stats` ([N, groups, 2] float32, 8-byte aligned,
+ * REQUIRED) = (mean, 1 / sqrt(var + eps)) per (sample, group) -- float32 whatever the activations are. Refused as the call above refuses
+ * (F3DG_ERR_BAD_ARG / F3DG_ERR_WORKSPACE before any HIP call, nothing written), and with F3DG_ERR_BAD_ARG for a NULL stats; a 16-bit dtype
+ * is no refusal here. N == 0: F3DG_OK and no work. */
+int f3dg_group_norm_silu_forward_stats(void* stream, int dtype, int nhwc, int N, int C, int HW, int groups,
+                                       const void* x, const float* pre_bias, const float* weight, const float* bias,
+                                       float eps, int apply_silu, void* y, float* stats, void* scratch, size_t scratch_bytes);
 /* The residual join of a backbone block (src/gaussian_predictor.py:325-327: the second convolution's bias, `x = x + skip(orig)` with the
  * skip convolution's bias, `x = x * skip_scale`) as ONE elementwise pass: y = ((a + bias_a[c]) + (b + bias_b[c])) * scale in float32,
  * the reference's order. a, b, y as `dtype` and `nhwc` say, 16-byte aligned, N*C*HW a multiple of 4 (float32) / 8 (16-bit) -- and C as
  * well when nhwc = 1; either bias may be null; y may alias a or b. Anything else, and a dtype outside 0..2, is F3DG_ERR_BAD_ARG. */
 int f3dg_residual_join_forward(void* stream, int dtype, int nhwc, int N, int C, int HW,
                                const void* a, const float* bias_a, const void* b, const float* bias_b, float scale, void* y);
-/* Training through the backbone: the adjoints of the float32 kernels above, both layouts (nhwc = 0: [N,C,HW]; nhwc = 1: [N,HW,C]).
+/* Training through the backbone: the adjoints of the kernels above, both layouts (nhwc = 0: [N,C,HW]; nhwc = 1: [N,HW,C]). The two
+ * float32 entry points came first; the *_dtype forms behind them take every activation type, and the float32 ones are calls of those
+ * with F3DG_F32.
  *
  * f3dg_group_norm_silu_backward takes `stats` from f3dg_group_norm_silu_forward and recomputes everything else from x. With v = x + pre_bias, xh = (v - mean) * rstd, z = weight * xh + bias
  * (formed as the forward forms it: the mean taken off before the scale), m = (C / groups) * HW:
@@ -514,6 +524,18 @@ int f3dg_group_norm_silu_backward(void* stream, int N, int C, int HW, int groups
                                   const float* weight, const float* bias, const float* stats, int apply_silu, const float* grad_y,
                                   float* grad_x, float* grad_weight, float* grad_bias, float* grad_pre_bias, void* scratch,
                                   size_t scratch_bytes);
+/* The same in the activation type `dtype` names: x, grad_y and grad_x are float32, bfloat16 or float16 (16-byte packets of 4 / 8 values);
+ * pre_bias, weight, bias, `stats` (from f3dg_group_norm_silu_forward_stats) and the three parameter gradients stay float32. A 16-bit
+ * value is widened exactly, all arithmetic and every sum is the float32 call's (nothing is rounded before it enters a sum), and grad_x is
+ * rounded to the type ONCE, to nearest even; a float16 grad_x beyond the type's range is +-Inf, never a clamped value (a loss scaler
+ * detects overflow by that). No atomics: bit-identical from run to run; a non-finite grad_y stays inside its (sample, group). The scratch
+ * is f3dg_group_norm_silu_backward_scratch_bytes whatever the dtype. NCHW takes whole packets where HW is a multiple of 4 / 8 and single
+ * values otherwise. Refused as above, and with F3DG_ERR_BAD_ARG for a dtype outside 0..2 and for a channels-last C that is no multiple
+ * of 4 (float32) / 8 (16-bit) or above 1024. N == 0: F3DG_OK and no work. */
+int f3dg_group_norm_silu_backward_dtype(void* stream, int dtype, int N, int C, int HW, int groups, int nhwc, const void* x,
+                                        const float* pre_bias, const float* weight, const float* bias, const float* stats, int apply_silu,
+                                        const void* grad_y, void* grad_x, float* grad_weight, float* grad_bias, float* grad_pre_bias,
+                                        void* scratch, size_t scratch_bytes);
 /* The adjoint of f3dg_residual_join_forward in ONE pass over grad_y: grad_ab = grad_y * scale [as grad_y], which is the gradient of a and of b
  * alike, and grad_bias[c] = the sum of grad_ab over channel c ([C], the gradient of either bias; NULL = not wanted), summed in float64 in
  * a fixed order without atomics. grad_ab may be grad_y. `scratch` (needed only with grad_bias): f3dg_residual_join_backward_scratch_bytes
@@ -522,6 +544,13 @@ int f3dg_group_norm_silu_backward(void* stream, int N, int C, int HW, int groups
 size_t f3dg_residual_join_backward_scratch_bytes(int N, int C, int HW, int nhwc);
 int f3dg_residual_join_backward(void* stream, int N, int C, int HW, int nhwc, const float* grad_y, float scale, float* grad_ab,
                                 float* grad_bias, void* scratch, size_t scratch_bytes);
+/* The same in the activation type `dtype` names: grad_y and grad_ab are float32, bfloat16 or float16, grad_bias float32. grad_ab is the
+ * float32 product grad_y * scale rounded to the type once (to nearest even; float16 overflow is +-Inf); grad_bias sums the float32
+ * products themselves, not their rounded copies. The scratch is f3dg_residual_join_backward_scratch_bytes whatever the dtype.
+ * F3DG_ERR_BAD_ARG as above with the packet of the type -- N*C*HW, and channels-last C, a multiple of 4 (float32) / 8 (16-bit) -- and for a
+ * dtype outside 0..2. N == 0: F3DG_OK and no work. */
+int f3dg_residual_join_backward_dtype(void* stream, int dtype, int N, int C, int HW, int nhwc, const void* grad_y, float scale,
+                                      void* grad_ab, float* grad_bias, void* scratch, size_t scratch_bytes);
 
 /* Fused differentiable image loss: SSIM (+ L1, L2) of n_planes pairs of H x W planes -- a plane is one channel of one frame; img1, img2
  * and every plane set below are float32, planar and contiguous, [n_planes, H, W].
