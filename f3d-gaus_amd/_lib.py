@@ -11,6 +11,7 @@ OK, ERR_BAD_ARG, ERR_WORKSPACE, ERR_OVERFLOW, ERR_HIP, ERR_UNSUPPORTED, ERR_STAT
 FLAG_SAVE_AUX, FLAG_BG_PER_VIEW, FLAG_SKIP_NORMAL, FLAG_SKIP_DISTORTION = 1, 2, 4, 8
 FLAG_EXACT, FLAG_FAST, FLAG_NO_TILE_CULL, FLAG_NO_SMALL_PATH, FLAG_SCAN, FLAG_SETS_AUX = 16, 32, 64, 128, 256, 512
 PENDING = 1
+GEOM_ALPHA_WEIGHT = 1
 MAX_PANELS, PANEL_RGB, PANEL_SIGNED, PANEL_COLORMAP = 8, 0, 1, 2
 
 
@@ -97,6 +98,10 @@ SIGNATURES = {
     "f3dg_ssim_forward": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     # stream | n_planes W H | img1 img2 | dL_dmap plane_weights | dm_dmu1 dm_dsigma1_sq dm_dsigma12 | dL_dimg1
     "f3dg_ssim_backward": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    # n_frames W H  /  stream | n_frames H W | raster world_view fx fy flags | depth_target normal_target alpha_target mask | ...
+    "f3dg_geometry_loss_partials_bytes": (_sz, [_i, _i, _i]),
+    "f3dg_geometry_loss_forward": (_i, [_p, _i, _i, _i, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _sz, _p]),      # partials partials_bytes frame_sums
+    "f3dg_geometry_loss_backward": (_i, [_p, _i, _i, _i, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _p]),          # frame_weights dL_draster
     "f3dg_set_option": (_i, [C.c_char_p, _i]),
     "f3dg_profile_enable": (_i, [_i]),
     "f3dg_debug_launch_count": (C.c_longlong, [_i]),

@@ -11,13 +11,23 @@ hands their gradient back as the kernel's per-plane weights, so a mean never mat
 
 Inputs are float32 ``[..., C, H, W]`` on one HIP device (no CPU fallback); only ``img1`` (the prediction) receives a gradient -- SSIM is
 symmetric, swap the arguments for the other side. The outputs of ``render_views(..., differentiable=True)["render"]`` go in as they are.
-No double backward. Everything is enqueued on the current stream."""
+No double backward. Everything is enqueued on the current stream.
+
+The geometry terms the reference's settings file weighs besides RGB (config/imagenetgs_256x256_v1.yaml:50-66: ``w_depth_normal``,
+``w_distortion``, ``w_depth``, ``w_normal``, ``w_alpha``) read the nine raster planes themselves: ``geometry_sums`` is ONE forward kernel
+(``f3dg_geometry_loss_forward``: the five per-frame sums, the world normal and the depth normal of a pixel formed in registers with the
+epilogue's own arithmetic and never written) and ONE backward kernel (``f3dg_geometry_loss_backward``: dL/draster directly, the cotangent
+of the sums as its per-frame weights). ``geometry_loss`` blends them; ``normal_consistency``, ``distortion_loss`` and ``depth_loss`` are
+single-term wrappers. ``out["raster"]`` of ``render_views(..., differentiable=True)`` goes in as it is."""
+import math
+
 import torch
 
 from . import _lib
 from .diff_gof_rasterization import _stream
 
-__all__ = ["ssim", "ssim_map", "l1_loss", "l2_loss", "psnr", "image_metrics", "photometric_loss"]
+__all__ = ["ssim", "ssim_map", "l1_loss", "l2_loss", "psnr", "image_metrics", "photometric_loss",
+           "geometry_sums", "geometry_loss", "normal_consistency", "distortion_loss", "depth_loss"]
 
 
 def _forward_call(img1, img2, n_planes, H, W, want_map, want_planes):
@@ -161,3 +171,185 @@ def photometric_loss(render, target, lambda_dssim=0.2, reduction="mean"):
         n = float(render.numel())
         return (1.0 - lam) * (sums[:, 1].sum() / n) + lam * (1.0 - sums[:, 0].sum() / n)
     return (1.0 - lam) * _per_leading(sums[:, 1], render.shape) + lam * (1.0 - _per_leading(sums[:, 0], render.shape))
+
+
+# ------------------------------------------------------------------------------------------------ geometry terms
+class _GeometryLoss(torch.autograd.Function):
+    """``f3dg_geometry_loss_forward`` with ``f3dg_geometry_loss_backward`` behind it: frame_sums [F, 5] of a contiguous float32
+    [F, 9, H, W] raster. Saves its inputs only; the cotangent of the sums goes to the backward kernel as its per-frame weights."""
+
+    @staticmethod
+    def forward(ctx, raster, world_view, depth_target, normal_target, alpha_target, mask, fx, fy, flags):
+        F, _, H, W = raster.shape
+        L = _lib.lib()
+        nbytes = L.f3dg_geometry_loss_partials_bytes(F, W, H)
+        if nbytes == 0:
+            raise ValueError(f"geometry loss: bad frame count / size ({F} frames of {H} x {W})")
+        partials = torch.empty(nbytes // 4, dtype=torch.float32, device=raster.device)
+        sums = torch.empty((F, 5), dtype=torch.float32, device=raster.device)
+        rc = L.f3dg_geometry_loss_forward(_stream(), F, H, W, _lib.ptr(raster), _lib.ptr(world_view), fx, fy, flags, _lib.ptr(depth_target),
+                                          _lib.ptr(normal_target), _lib.ptr(alpha_target), _lib.ptr(mask), _lib.ptr(partials), nbytes,
+                                          _lib.ptr(sums))
+        _lib.check(rc, "f3dg_geometry_loss_forward")
+        ctx.set_materialize_grads(False)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(raster, world_view, depth_target, normal_target, alpha_target, mask)
+            ctx.scalars = (fx, fy, flags)
+        return sums
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_sums):
+        if g_sums is None:
+            return (None,) * 9
+        raster, world_view, depth_target, normal_target, alpha_target, mask = ctx.saved_tensors
+        fx, fy, flags = ctx.scalars
+        F, _, H, W = raster.shape
+        g_sums = g_sums.to(device=raster.device, dtype=torch.float32).contiguous()
+        d_raster = torch.empty_like(raster)
+        rc = _lib.lib().f3dg_geometry_loss_backward(_stream(), F, H, W, _lib.ptr(raster), _lib.ptr(world_view), fx, fy, flags,
+                                                    _lib.ptr(depth_target), _lib.ptr(normal_target), _lib.ptr(alpha_target), _lib.ptr(mask),
+                                                    _lib.ptr(g_sums), _lib.ptr(d_raster))
+        _lib.check(rc, "f3dg_geometry_loss_backward")
+        return (d_raster,) + (None,) * 8
+
+
+def _geometry_data(t, name, who, lead, planes, H, W, dev, allow_bool=False):
+    """A target or the mask as a contiguous float32 [F, planes, H, W] device tensor (None stays None). ``planes`` = 1 also takes
+    [..., H, W] without the plane axis."""
+    if t is None:
+        return None
+    if torch.is_grad_enabled() and t.requires_grad:
+        raise NotImplementedError(f"{who} produces no gradient for `{name}`: detach it (only `raster` receives a gradient)")
+    if allow_bool and t.dtype == torch.bool:
+        t = t.to(torch.float32)
+    if t.dtype != torch.float32:
+        raise TypeError(f"{who}: `{name}` must be float32 (got {t.dtype})")
+    want = tuple(lead) + (planes, H, W)
+    if tuple(t.shape) != want and not (planes == 1 and tuple(t.shape) == tuple(lead) + (H, W)):
+        raise ValueError(f"{who}: `{name}` is {tuple(t.shape)}; the raster {tuple(lead) + (9, H, W)} needs {want}")
+    if t.device != dev:
+        raise RuntimeError(f"f3dgaus_amd.losses.{who} needs `{name}` on the raster's HIP device (no CPU fallback)")
+    return t.detach().contiguous().reshape(-1, planes, H, W)
+
+
+def _geometry_sums(raster, world_views, cfg, who, alpha_weight=False, depth_target=None, normal_target=None, alpha_target=None, mask=None):
+    """Boundary checks in this package's manner, then the autograd function: ([F, 5] sums, the raster's leading shape, H, W)."""
+    if raster.dim() < 3 or raster.shape[-3] != 9:
+        raise ValueError(f"{who}: the raster is [..., 9, H, W]; got {tuple(raster.shape)}")
+    if raster.numel() == 0:
+        raise ValueError(f"{who}: empty raster {tuple(raster.shape)}")
+    if raster.dtype != torch.float32:
+        raise TypeError(f"{who}: the raster must be float32 (got {raster.dtype})")
+    lead, (H, W) = tuple(raster.shape[:-3]), raster.shape[-2:]
+    F = raster.numel() // (9 * H * W)
+    if world_views is None:                    # no term that reads a camera was asked for
+        wv = torch.eye(4, dtype=torch.float32, device=raster.device).reshape(1, 16)
+        fx = fy = 1.0
+    else:
+        if torch.is_grad_enabled() and world_views.requires_grad:
+            raise NotImplementedError(f"{who} produces no gradient for the cameras (`world_views`): detach them")
+        if world_views.dtype != torch.float32:
+            raise TypeError(f"{who}: `world_views` must be float32 (got {world_views.dtype})")
+        if world_views.numel() == 0 or world_views.numel() % 16:
+            raise ValueError(f"{who}: `world_views` is [F, 4, 4] or [F, 16]; got {tuple(world_views.shape)}")
+        wv = world_views.detach().reshape(-1, 16)
+        FoV = cfg['model']['fov'] * math.pi / 180
+        fx, fy = W / (2 * math.tan(FoV / 2.)), H / (2 * math.tan(FoV / 2.))          # as render_views forms them for its epilogue
+    V = wv.shape[0]
+    if F % V:
+        raise ValueError(f"{who}: {V} cameras for {F} frames: one per frame, or V with F = n * V (frame b * V + v, as render_views(bs=None))")
+    dev = raster.device
+    data = [_geometry_data(depth_target, "depth_target", who, lead, 1, H, W, dev), _geometry_data(normal_target, "normal_target", who, lead, 3, H, W, dev),
+            _geometry_data(alpha_target, "alpha_target", who, lead, 1, H, W, dev), _geometry_data(mask, "mask", who, lead, 1, H, W, dev, allow_bool=True)]
+    if dev.type != "cuda" or wv.device != dev:
+        raise RuntimeError(f"f3dgaus_amd.losses.{who} needs the raster and `world_views` on one HIP device (no CPU fallback)")
+    if V != F:
+        wv = wv.repeat(F // V, 1)              # image-major
+    sums = _GeometryLoss.apply(raster.contiguous().reshape(F, 9, H, W), wv.contiguous(), *data, float(fx), float(fy),
+                               _lib.GEOM_ALPHA_WEIGHT if alpha_weight else 0)
+    return sums, lead, H, W
+
+
+def geometry_sums(raster, world_views, cfg, *, alpha_weight=False, depth_target=None, normal_target=None, alpha_target=None, mask=None):
+    """The per-frame sums [F, 5] of the five geometry terms over a raster [..., 9, H, W] (F = the product of the leading dims), from ONE
+    forward kernel; differentiable in ``raster`` through ONE backward kernel. With N = ``rendered_normal`` and D = ``depth_normal`` exactly
+    as ``render_views`` returns them, n^ = normalize(raster[3:6]), d = raster[6], alpha = raster[7] and m = ``mask`` (1 without one):
+
+        [:, 0]  depth-normal consistency  w (1 - <N, D>),   w = 1, or alpha with ``alpha_weight`` (as data: no gradient through w)
+        [:, 1]  distortion                raster[8]
+        [:, 2]  depth                     m |d - depth_target|
+        [:, 3]  normal                    m (1 - <n^, normal_target>)   (camera frame; the target is used as given)
+        [:, 4]  alpha                     |alpha - alpha_target|
+
+    A term whose target is None is 0 and contributes no gradient. ``world_views`` is [F, 4, 4] or [F, 16], one per frame, or [V, ...] with
+    F = n * V (frame b * V + v, as ``render_views(bs=None)`` lays frames out); the focal lengths come from ``cfg['model']['fov']`` and the
+    raster's own W, H. Targets are float32 [..., H, W] or [..., 1, H, W] ([..., 3, H, W] for the normals) with the raster's leading dims;
+    the mask may also be bool. Only ``raster`` receives a gradient."""
+    return _geometry_sums(raster, world_views, cfg, "geometry_sums", alpha_weight, depth_target, normal_target, alpha_target, mask)[0]
+
+
+_BLEND = {}
+
+
+def _blend_weights(weights, device):
+    """(columns of the non-zero weights or None for all five, their float32 values) as device tensors, built once per (device, weights):
+    the blend of a training step then costs no host-to-device copy."""
+    key = (device, tuple(weights))
+    hit = _BLEND.get(key)
+    if hit is None:
+        cols = [k for k, w in enumerate(weights) if w != 0.0]
+        hit = (None if len(cols) == len(weights) else torch.tensor(cols, dtype=torch.long, device=device),
+               torch.tensor([weights[k] for k in cols], dtype=torch.float32, device=device))
+        if len(_BLEND) >= 64:           # (weights on a schedule: keep the table small)
+            _BLEND.clear()
+        _BLEND[key] = hit
+    return hit
+
+
+def _geometry_loss(who, raster, world_views, cfg, weights, alpha_weight=False, depth_target=None, normal_target=None, alpha_target=None,
+                   mask=None, reduction="mean"):
+    """``geometry_loss`` with the weights in the order of the sums' columns; a term with weight 0 is not handed to the kernel."""
+    if reduction not in ("mean", "none"):
+        raise ValueError(f"{who}: reduction must be 'mean' or 'none' (got {reduction!r})")
+    weights = [float(w) for w in weights]
+    targets = [depth_target, normal_target, alpha_target]
+    for w, t, name in zip(weights[2:], targets, ("depth", "normal", "alpha")):
+        if w != 0.0 and t is None:
+            raise ValueError(f"{who}: w_{name} = {w} needs `{name}_target`")
+    depth_target, normal_target, alpha_target = (t if w != 0.0 else None for w, t in zip(weights[2:], targets))
+    sums, lead, H, W = _geometry_sums(raster, world_views, cfg, who, alpha_weight, depth_target, normal_target, alpha_target,
+                                      mask if (weights[2] != 0.0 or weights[3] != 0.0) else None)
+    cols, w = _blend_weights(weights, sums.device)
+    if w.numel() == 0:
+        per_frame = torch.zeros(sums.shape[0], dtype=torch.float32, device=sums.device)
+    else:           # (a column with weight 0 is left out, not multiplied by 0: whatever it holds cannot reach the loss)
+        per_frame = ((sums if cols is None else sums.index_select(1, cols)) * w).sum(1)
+    if reduction == "mean":
+        return per_frame.sum() / float(sums.shape[0] * H * W)
+    return per_frame.reshape(lead) / float(H * W)
+
+
+def geometry_loss(raster, world_views, cfg, *, w_depth_normal=0., w_distortion=0., w_depth=0., w_normal=0., w_alpha=0., alpha_weight=False,
+                  depth_target=None, normal_target=None, alpha_target=None, mask=None, reduction="mean"):
+    """The weighted sum of the geometry terms of ``geometry_sums``, the weights named as the reference's settings file names them
+    (config/imagenetgs_256x256_v1.yaml:50-66). Every term is its mean over ALL pixels (masked terms too: their sum over F * H * W).
+    ``reduction="mean"``: a scalar; ``"none"``: the loss of every frame (the raster's leading shape), each term divided by H * W.
+    A term with weight 0 is not evaluated; a non-zero weight whose target is missing raises ``ValueError``."""
+    return _geometry_loss("geometry_loss", raster, world_views, cfg, (w_depth_normal, w_distortion, w_depth, w_normal, w_alpha), alpha_weight,
+                          depth_target, normal_target, alpha_target, mask, reduction)
+
+
+def normal_consistency(raster, world_views, cfg, alpha_weight=False):
+    """mean(w (1 - <rendered_normal, depth_normal>)) over all pixels of all frames, w = 1 or the rendered alpha (``alpha_weight``)."""
+    return _geometry_loss("normal_consistency", raster, world_views, cfg, (1.0, 0.0, 0.0, 0.0, 0.0), alpha_weight)
+
+
+def distortion_loss(raster):
+    """The mean of the distortion map (raster[..., 8, :, :])."""
+    return _geometry_loss("distortion_loss", raster, None, None, (0.0, 1.0, 0.0, 0.0, 0.0))
+
+
+def depth_loss(raster, depth_target, mask=None):
+    """mean(mask |rendered_depth - depth_target|) over all pixels of all frames."""
+    return _geometry_loss("depth_loss", raster, None, None, (0.0, 0.0, 1.0, 0.0, 0.0), depth_target=depth_target, mask=mask)

@@ -42,6 +42,9 @@
  *   f3dg_ssim_forward / f3dg_ssim_backward
  *       ssim / _ssim, l1_loss, l2_loss and what torch.autograd derives from them   src/gaussian-splatting/utils/loss_utils.py:17-63
  *       (the objective of src/gaussian-splatting/train.py:92) and psnr's mean squared error, utils/image_utils.py:17-19
+ *   f3dg_geometry_loss_forward / f3dg_geometry_loss_backward
+ *       the terms the settings file weighs besides RGB   config/imagenetgs_256x256_v1.yaml:50-66 (the reference ships the weights, not
+ *       the trainer: the terms are defined below, on the maps of src/gaussian_renderer/__init__.py:881-909, 1043-1053)
  *
  * Memory ownership mirrors the reference: outputs and the workspace are allocated and owned by the caller
  * (torch tensors on the Python side). Instead of growing buffers through callbacks in the middle of the call
@@ -588,6 +591,44 @@ int f3dg_ssim_forward(void* stream, int n_planes, int W, int H, const float* img
 int f3dg_ssim_backward(void* stream, int n_planes, int W, int H, const float* img1, const float* img2, const float* dL_dmap,
                        const float* plane_weights, const float* dm_dmu1, const float* dm_dsigma1_sq, const float* dm_dsigma12,
                        float* dL_dimg1);
+
+/* Fused geometry losses: the terms the reference's trainer weighs besides RGB (config/imagenetgs_256x256_v1.yaml:50-66: w_depth_normal,
+ * w_distortion, w_depth, w_normal, w_alpha) on raster [n_frames,9,H,W], summed per frame -- one forward kernel that never writes the
+ * two derived maps, one backward kernel that writes dL/draster directly. Everything is float32, planar and contiguous.
+ * Per pixel: N = normal_world and D = depth_normal EXACTLY as f3dg_render_epilogue_view defines them (world_view [n_frames,16] in the
+ * row-vector convention, c2w = inverse(world_view^T) by float64 cofactors per frame, the same fx, fy, D = 0 on the border, F.normalize's
+ * 1e-12 clamp on both normalisations); n^ = normalize(raster[3:6]) in the camera frame; d = raster[6], alpha = raster[7]; m = mask
+ * ([n_frames,H,W]; NULL = 1).
+ *   term 0  depth-normal consistency  w (1 - <N, D>),  w = 1, or alpha with F3DG_GEOM_ALPHA_WEIGHT (w is data: it gets no gradient)
+ *   term 1  distortion                raster[8]
+ *   term 2  depth                     m |d - depth_target|                 depth_target [n_frames,H,W]
+ *   term 3  normal                    m (1 - <n^, normal_target>)          normal_target [n_frames,3,H,W], used as given
+ *   term 4  alpha                     |alpha - alpha_target|               alpha_target [n_frames,H,W]
+ * f3dg_geometry_loss_forward writes frame_sums [n_frames,5]: the sum of every term over the frame's pixels. A NULL target skips its term:
+ * the sum is written as 0. `partials` is a scratch buffer of f3dg_geometry_loss_partials_bytes(n_frames, W, H) bytes (partials_bytes =
+ * its size): every 32 x 16 tile writes its own slot, a second kernel adds one frame's slots in a fixed order. No float atomics: the sums
+ * are bit-reproducible, and the sums of one frame depend on no other frame's data.
+ * f3dg_geometry_loss_backward ASSIGNS every element of dL_draster [n_frames,9,H,W] for L = sum_f sum_k frame_weights[f,k] frame_sums[f,k]
+ * (frame_weights [n_frames,5] = W0..W4 of a frame), one thread per (frame, pixel), no atomics:
+ *   channels 0..2  0
+ *   channels 3..5  F.normalize's backward (g / 1e-12 where its clamp is active) of  -W0 w c2w[:3,:3]^T D - W3 m normal_target
+ *   channel 6      W2 m sign(d - depth_target) + the gather of term 0 over the up to four interior axial neighbours q whose depth normal
+ *                  reads this pixel, in the order of f3dg_render_epilogue_backward, each with the cotangent -W0 w(q) N(q) on D(q)
+ *   channel 7      W4 sign(alpha - alpha_target)
+ *   channel 8      W1
+ * sign(0) = 0. A term with a NULL target contributes nothing, and neither does a term whose weight is exactly 0: it is not evaluated.
+ * F3DG_ERR_BAD_ARG: NULL raster, world_view, frame_sums or partials (forward), frame_weights or dL_draster (backward); non-positive
+ * sizes; flag bits other than F3DG_GEOM_ALPHA_WEIGHT. F3DG_ERR_WORKSPACE: partials_bytes too small. F3DG_ERR_UNSUPPORTED: 9 H W or the
+ * number of tiles beyond 2^31 - 1. f3dg_geometry_loss_partials_bytes returns 0 for non-positive sizes. All checks happen before any
+ * HIP call. */
+#define F3DG_GEOM_ALPHA_WEIGHT 1
+size_t f3dg_geometry_loss_partials_bytes(int n_frames, int W, int H);
+int f3dg_geometry_loss_forward(void* stream, int n_frames, int H, int W, const float* raster, const float* world_view, float fx, float fy,
+                               int flags, const float* depth_target, const float* normal_target, const float* alpha_target,
+                               const float* mask, float* partials, size_t partials_bytes, float* frame_sums);
+int f3dg_geometry_loss_backward(void* stream, int n_frames, int H, int W, const float* raster, const float* world_view, float fx, float fy,
+                                int flags, const float* depth_target, const float* normal_target, const float* alpha_target,
+                                const float* mask, const float* frame_weights, float* dL_draster);
 
 /* Runtime switches: process-wide DEFAULTS for what a call's own flags do not say (every arithmetic / list / path choice of a call has a
  * flag, above). The library knows sixteen names and one diagnostic pair; everything else returns F3DG_ERR_BAD_ARG.
