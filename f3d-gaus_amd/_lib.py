@@ -102,6 +102,14 @@ SIGNATURES = {
     "f3dg_geometry_loss_partials_bytes": (_sz, [_i, _i, _i]),
     "f3dg_geometry_loss_forward": (_i, [_p, _i, _i, _i, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _sz, _p]),      # partials partials_bytes frame_sums
     "f3dg_geometry_loss_backward": (_i, [_p, _i, _i, _i, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _p]),          # frame_weights dL_draster
+    # n_src n_views C W H  /  stream | n_src n_views C H W | image depth valid rel | fx fy z_near depth_tolerance occlusion_min_weight threshold
+    # | erode | workspace workspace_bytes | warped mask warped_depth weight
+    "f3dg_forward_warp_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "f3dg_forward_warp": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _f, _f, _f, _f, _f, _f, _i, _p, _sz, _p, _p, _p, _p]),
+    # n_frames C W H  /  stream | n_frames C H W | a b mask | partials partials_bytes frame_sums  /  ... | frame_weights dL_da
+    "f3dg_masked_l1_partials_bytes": (_sz, [_i, _i, _i, _i]),
+    "f3dg_masked_l1_forward": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "f3dg_masked_l1_backward": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "f3dg_set_option": (_i, [C.c_char_p, _i]),
     "f3dg_profile_enable": (_i, [_i]),
     "f3dg_debug_launch_count": (C.c_longlong, [_i]),

@@ -9,7 +9,7 @@
 // formed with the epilogue's own expressions (f3dg_epilogue.h), so the terms are those of the maps f3dg_render_epilogue_view writes.
 //
 // forward   a workgroup of 256 threads owns a 32 x 16 pixel tile of one frame, two pixels per thread (rows ty and ty + 8); its five
-//           sums go through a pairwise tree in LDS (fixed order) into the tile's own slot of `partials`; geom_frame_sums_kernel adds
+//           sums go through a pairwise tree in LDS (fixed order) into the tile's own slot of `partials`; f3dg_frame_sums_kernel<5> adds
 //           one frame's slots in a fixed order. No float atomics, bit-reproducible, and no frame's sums see another frame's data.
 // backward  one thread per (frame, pixel), 256 consecutive pixels of a frame per workgroup, as epilogue_backward_kernel: channels 3..5
 //           from this pixel's own N, D and target; channel 6 as the gather over the up to four interior axial neighbours whose depth
@@ -17,6 +17,7 @@
 //           the forward, no atomics, every element of dL_draster is assigned.
 #include "f3dg_common.h"
 #include "f3dg_epilogue.h"
+#include "f3dg_frame_sums.h"
 
 #define F3DG_GEOM_TW 32
 #define F3DG_GEOM_TH 16
@@ -136,26 +137,7 @@ geom_fwd_kernel(GeomGrid grid, GeomArgs a, float* __restrict__ partials)
     }
 }
 
-// Second stage: one wave per frame adds that frame's tile slots -- lane l takes tiles l, l + 64, ... in ascending order, then a
-// pairwise tree over the 64 lanes in LDS (ssim_plane_sums_kernel with five columns).
-__global__ void __launch_bounds__(64)
-geom_frame_sums_kernel(unsigned tiles_per_frame, const float* __restrict__ partials, float* __restrict__ frame_sums)
-{
-    __shared__ float s[F3DG_GEOM_TERMS * 64];
-    const unsigned lane = threadIdx.x, f = blockIdx.x;
-    const float* p = partials + F3DG_GEOM_TERMS * (size_t)f * tiles_per_frame;
-    float acc[F3DG_GEOM_TERMS] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
-    for (unsigned i = lane; i < tiles_per_frame; i += 64u)
-        for (int q = 0; q < F3DG_GEOM_TERMS; q++) acc[q] = acc[q] + p[F3DG_GEOM_TERMS * (size_t)i + q];
-    for (int q = 0; q < F3DG_GEOM_TERMS; q++) s[q * 64 + lane] = acc[q];
-    for (unsigned half = 32u; half >= 1u; half >>= 1) {
-        __syncthreads();
-        if (lane < half)
-            for (int q = 0; q < F3DG_GEOM_TERMS; q++) s[q * 64 + lane] = s[q * 64 + lane] + s[q * 64 + lane + half];
-    }
-    if (lane == 0)
-        for (int q = 0; q < F3DG_GEOM_TERMS; q++) frame_sums[F3DG_GEOM_TERMS * (size_t)f + q] = s[q * 64];
-}
+// Second stage: f3dg_frame_sums_kernel<5> (f3dg_frame_sums.h), one wave per frame over that frame's tile slots in a fixed order.
 
 // dL/draster for L = sum_f sum_k frame_weights[f,k] frame_sums[f,k]. A term whose weight is exactly 0 is not evaluated (its data
 // cannot reach the gradient, whatever it holds), as a term whose target is null.
@@ -268,7 +250,7 @@ extern "C" int f3dg_geometry_loss_forward(void* stream, int n_frames, int H, int
     const GeomArgs a = { H, W, raster, world_view, fx, fy, flags, depth_target, normal_target, alpha_target, mask };
     F3DG_KLAUNCH(geom_fwd_kernel, dim3((unsigned)blocks), dim3(F3DG_GEOM_THREADS), 0, (hipStream_t)stream, g, a, partials);
     F3DG_HIP_CHECK(hipGetLastError());
-    F3DG_KLAUNCH(geom_frame_sums_kernel, dim3((unsigned)n_frames), dim3(64), 0, (hipStream_t)stream, g.tiles_x * g.tiles_y, partials,
+    F3DG_KLAUNCH(f3dg_frame_sums_kernel<F3DG_GEOM_TERMS>, dim3((unsigned)n_frames), dim3(64), 0, (hipStream_t)stream, g.tiles_x * g.tiles_y, partials,
                  frame_sums);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;

@@ -18,7 +18,11 @@ The geometry terms the reference's settings file weighs besides RGB (config/imag
 (``f3dg_geometry_loss_forward``: the five per-frame sums, the world normal and the depth normal of a pixel formed in registers with the
 epilogue's own arithmetic and never written) and ONE backward kernel (``f3dg_geometry_loss_backward``: dL/draster directly, the cotangent
 of the sums as its per-frame weights). ``geometry_loss`` blends them; ``normal_consistency``, ``distortion_loss`` and ``depth_loss`` are
-single-term wrappers. ``out["raster"]`` of ``render_views(..., differentiable=True)`` goes in as it is."""
+single-term wrappers. ``out["raster"]`` of ``render_views(..., differentiable=True)`` goes in as it is.
+
+The settings' ``w_warping`` term compares a novel render with the forward-warped input view (``warp.forward_warp``) under the warp's
+mask: ``warping_sums`` is ONE forward kernel plus the same fixed-order second stage (``f3dg_masked_l1_forward``) and ONE backward kernel
+(``f3dg_masked_l1_backward``); ``warping_loss`` is its mean. Only the render receives a gradient: the warp is data."""
 import math
 
 import torch
@@ -27,7 +31,7 @@ from . import _lib
 from .diff_gof_rasterization import _stream
 
 __all__ = ["ssim", "ssim_map", "l1_loss", "l2_loss", "psnr", "image_metrics", "photometric_loss",
-           "geometry_sums", "geometry_loss", "normal_consistency", "distortion_loss", "depth_loss"]
+           "geometry_sums", "geometry_loss", "normal_consistency", "distortion_loss", "depth_loss", "warping_sums", "warping_loss"]
 
 
 def _forward_call(img1, img2, n_planes, H, W, want_map, want_planes):
@@ -353,3 +357,97 @@ def distortion_loss(raster):
 def depth_loss(raster, depth_target, mask=None):
     """mean(mask |rendered_depth - depth_target|) over all pixels of all frames."""
     return _geometry_loss("depth_loss", raster, None, None, (0.0, 0.0, 1.0, 0.0, 0.0), depth_target=depth_target, mask=mask)
+
+
+# ------------------------------------------------------------------------------------------------ warping term
+class _MaskedL1(torch.autograd.Function):
+    """``f3dg_masked_l1_forward`` with ``f3dg_masked_l1_backward`` behind it: frame_sums [F, 2] of contiguous float32 a, b [F, C, H, W]
+    and m [F, 1, H, W]. Saves its inputs only; the cotangent of the sums goes to the backward kernel as its per-frame weights."""
+
+    @staticmethod
+    def forward(ctx, a, b, m):
+        F, C, H, W = a.shape
+        L = _lib.lib()
+        nbytes = L.f3dg_masked_l1_partials_bytes(F, C, W, H)
+        if nbytes == 0:
+            raise ValueError(f"warping loss: bad frame count / size ({F} frames of {C} x {H} x {W})")
+        partials = torch.empty(nbytes // 4, dtype=torch.float32, device=a.device)
+        sums = torch.empty((F, 2), dtype=torch.float32, device=a.device)
+        rc = L.f3dg_masked_l1_forward(_stream(), F, C, H, W, _lib.ptr(a), _lib.ptr(b), _lib.ptr(m), _lib.ptr(partials), nbytes, _lib.ptr(sums))
+        _lib.check(rc, "f3dg_masked_l1_forward")
+        ctx.set_materialize_grads(False)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(a, b, m)
+        return sums
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_sums):
+        if g_sums is None:
+            return None, None, None
+        a, b, m = ctx.saved_tensors
+        F, C, H, W = a.shape
+        g_sums = g_sums.to(device=a.device, dtype=torch.float32).contiguous()
+        d_a = torch.empty_like(a)
+        rc = _lib.lib().f3dg_masked_l1_backward(_stream(), F, C, H, W, _lib.ptr(a), _lib.ptr(b), _lib.ptr(m), _lib.ptr(g_sums), _lib.ptr(d_a))
+        _lib.check(rc, "f3dg_masked_l1_backward")
+        return d_a, None, None
+
+
+def _warping_sums(render, warped, mask, who):
+    """Boundary checks in this package's manner, then the autograd function: ([F, 2] sums, (C, H, W))."""
+    if render.dim() < 3:
+        raise ValueError(f"{who}: the render is [..., C, H, W]; got {tuple(render.shape)}")
+    if render.numel() == 0:
+        raise ValueError(f"{who}: empty render {tuple(render.shape)}")
+    if warped.dim() < 3 or warped.shape[-3:] != render.shape[-3:] or warped.numel() != render.numel():
+        raise ValueError(f"{who}: `render` and `warped` differ in shape: {tuple(render.shape)} vs {tuple(warped.shape)} (the same [C, H, W] and "
+                         "the same number of frames: [B * V, ...] against [B, V, ...] is fine)")
+    if render.dtype != torch.float32 or warped.dtype != torch.float32:
+        raise TypeError(f"{who}: `render` and `warped` must be float32 (got {render.dtype} and {warped.dtype})")
+    if torch.is_grad_enabled() and warped.requires_grad:
+        raise NotImplementedError(f"{who} produces no gradient for `warped` (the warp is data): detach it")
+    lead, (C, H, W) = tuple(render.shape[:-3]), render.shape[-3:]
+    dev = render.device
+    if torch.is_grad_enabled() and mask.requires_grad:
+        raise NotImplementedError(f"{who} produces no gradient for `mask`: detach it (only `render` receives a gradient)")
+    if mask.dtype == torch.bool:
+        mask = mask.to(torch.float32)
+    if mask.dtype != torch.float32:
+        raise TypeError(f"{who}: `mask` must be float32 or bool (got {mask.dtype})")
+    if mask.dim() < 2 or tuple(mask.shape[-2:]) != (H, W) or mask.numel() * C != render.numel():
+        raise ValueError(f"{who}: `mask` is {tuple(mask.shape)}; the render {tuple(render.shape)} needs {lead + (1, H, W)} (or its frames "
+                         "under other leading dims)")
+    if dev.type != "cuda" or warped.device != dev or mask.device != dev:
+        raise RuntimeError(f"f3dgaus_amd.losses.{who} needs `render`, `warped` and `mask` on one HIP device (no CPU fallback)")
+    sums = _MaskedL1.apply(render.contiguous().reshape(-1, C, H, W), warped.detach().contiguous().reshape(-1, C, H, W),
+                           mask.detach().contiguous().reshape(-1, 1, H, W))
+    return sums, (C, H, W)
+
+
+def warping_sums(render, warped, mask):
+    """The per-frame sums [F, 2] of the warping term over ``render`` and ``warped`` [..., C, H, W] and ``mask`` [..., 1, H, W] (or
+    [..., H, W]; float32 or bool), F the product of the leading dims, which may be split differently -- ``render_views(...,
+    differentiable=True)["render"]`` [B * V, 3, H, W] (image-major) and ``warp.forward_warp``'s [B, V, 3, H, W] go in as they are:
+
+        [:, 0]  sum over channels and pixels of  m |render - warped|
+        [:, 1]  sum over pixels of  m
+
+    ONE forward kernel and a fixed-order second stage (bit-reproducible); differentiable in ``render`` only, through ONE backward kernel:
+    ``m sign(render - warped)`` times the cotangent of column 0."""
+    return _warping_sums(render, warped, mask, "warping_sums")[0]
+
+
+def warping_loss(render, warped, mask, reduction="mean"):
+    """``sum(m |render - warped|) / (F C H W)``: the masked L1 against the warped frame as a mean over ALL pixels, the convention
+    ``geometry_loss`` uses for its masked terms. ``reduction="none"``: the loss of every frame (the leading shape), each divided by
+    C H W. To normalise by the covered pixels instead::
+
+        s = warping_sums(render, warped, mask)
+        loss = s[:, 0].sum() / (C * s[:, 1].sum()).clamp_min(1.0)"""
+    if reduction not in ("mean", "none"):
+        raise ValueError(f"warping_loss: reduction must be 'mean' or 'none' (got {reduction!r})")
+    sums, (C, H, W) = _warping_sums(render, warped, mask, "warping_loss")
+    if reduction == "mean":
+        return sums[:, 0].sum() / float(sums.shape[0] * C * H * W)
+    return sums[:, 0].reshape(tuple(render.shape[:-3])) / float(C * H * W)

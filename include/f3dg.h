@@ -45,6 +45,10 @@
  *   f3dg_geometry_loss_forward / f3dg_geometry_loss_backward
  *       the terms the settings file weighs besides RGB   config/imagenetgs_256x256_v1.yaml:50-66 (the reference ships the weights, not
  *       the trainer: the terms are defined below, on the maps of src/gaussian_renderer/__init__.py:881-909, 1043-1053)
+ *   f3dg_forward_warp / f3dg_masked_l1_forward / f3dg_masked_l1_backward
+ *       the depth-based forward warp behind the settings' w_warping / w_prop (threshold, erode_kernel_size, erode_pad_size:
+ *       config/imagenetgs_256x256_v1.yaml:50-66) and the masked L1 against it. The reference ships the settings, no trainer and no
+ *       warp: the semantics are this build's, defined below
  *
  * Memory ownership mirrors the reference: outputs and the workspace are allocated and owned by the caller
  * (torch tensors on the Python side). Instead of growing buffers through callbacks in the middle of the call
@@ -629,6 +633,58 @@ int f3dg_geometry_loss_forward(void* stream, int n_frames, int H, int W, const f
 int f3dg_geometry_loss_backward(void* stream, int n_frames, int H, int W, const float* raster, const float* world_view, float fx, float fy,
                                 int flags, const float* depth_target, const float* normal_target, const float* alpha_target,
                                 const float* mask, const float* frame_weights, float* dL_draster);
+
+/* Forward warp: source frames splatted into new cameras by their depth, with a z-buffer -- the masked pseudo-target of the settings'
+ * w_warping / w_prop. THE SEMANTICS ARE THIS PROJECT'S (the reference holds no warp); tests/warp_truth.py restates them in float64.
+ * Everything is float32, planar and contiguous. n_src source frames, n_views target cameras each: pair p = b * n_views + v.
+ *   image [n_src,C,H,W], 1 <= C <= 16; depth [n_src,H,W] z-depth; valid [n_src,H,W] or NULL (a source pixel takes part iff valid > 0);
+ *   rel [n_src,n_views,16]: row-major 4 x 4, rel[b,v] = inverse(src_world_view[b]) dst_world_view[b,v] in the row-vector convention.
+ * Projection. Source pixel (column i, row j) with d = depth[b,j,i] is live iff it is valid, d is finite and d > 0. Its camera point is
+ *   X = (i + 0.5 - W/2) / fx * d, Y = (j + 0.5 - H/2) / fy * d, Z = d (the rasterizer's pixel centre), in the target camera
+ *   (x,y,z) = X rel[0,:3] + Y rel[1,:3] + Z rel[2,:3] + rel[3,:3]; it stays live iff z > z_near. u = fx x / z + W/2 - 0.5,
+ *   v = fy y / z + H/2 - 0.5. The library evaluates this in float64 on the float32 arguments.
+ * Footprint. x0 = floor(u), y0 = floor(v), a = u - x0, b = v - y0; the four neighbours (x0 + dx, y0 + dy) have the bilinear weights
+ *   w = (dx ? a : 1 - a)(dy ? b : 1 - b); a neighbour is a candidate iff it lies inside the image and w > 0. u and v are range-checked
+ *   as floating-point numbers before any conversion to int: +-huge, +-Inf and NaN coordinates touch nothing.
+ * Pass 1. zmin[t] = the least z (rounded to float32) over the candidates of target pixel t with w >= occlusion_min_weight; +inf
+ *   without one. The floor keeps a point whose u lies 1e-7 past an integer from claiming the neighbouring pixel's z-buffer.
+ * Pass 2. A candidate (any w > 0) contributes iff z <= zmin[t] + depth_tolerance: Wsum[t] += w, Csum[t,c] += w image[c], Zsum[t] += w z.
+ *   The sums are 64-bit integers in units of q = 2^-24, each term rounded to nearest once: they do not depend on the order of arrival,
+ *   and the outputs are bit-identical from run to run. Range: a term |w v| saturates at 2^15 = 32768 (|image| and depth up to there
+ *   are exact; a non-finite colour of a live pixel saturates too), and H W <= 2^23 keeps every sum inside 63 bits.
+ * Resolve. weight = Wsum; where Wsum > 0 (at least q / 2): warped = Csum / Wsum and warped_depth = Zsum / Wsum, elsewhere both 0;
+ *   mask = (Wsum >= threshold) as 0.0 / 1.0.
+ * Erode. erode = k odd, 3..15 (0 and 1: off): mask[t] = the minimum of the mask over the k x k window around t, neighbours outside
+ *   the image ignored (-max_pool2d(-mask, k, 1, k / 2)).
+ * EVERY element of warped [n_src,n_views,C,H,W], mask [n_src,n_views,1,H,W] and, when not NULL, warped_depth and weight
+ * [n_src,n_views,1,H,W] is assigned. The colour and depth of a source pixel that is not live never enter arithmetic: a NaN there
+ * reaches no output. `workspace` (8-byte aligned, f3dg_forward_warp_workspace_bytes(...) bytes, caller-owned) holds the accumulators
+ * [pair][C + 2][H W], the z-buffer and the mask before erosion; the call initialises it. Five launches (four without erosion) for all
+ * pairs.
+ * F3DG_ERR_BAD_ARG: NULL image, depth, rel, workspace, warped or mask; a workspace off the 8-byte grid; non-positive n_src, n_views, C,
+ * H or W; fx or fy not positive and finite; z_near negative or not finite; depth_tolerance negative or NaN; occlusion_min_weight outside
+ * [0, 1]; a NaN threshold; erode negative, even or above 15. F3DG_ERR_UNSUPPORTED: C > 16, H W > 2^23, or more than 2^31 - 1 workgroups.
+ * F3DG_ERR_WORKSPACE: workspace_bytes too small. f3dg_forward_warp_workspace_bytes returns 0 for every size the call refuses. All checks
+ * happen before any HIP call. */
+size_t f3dg_forward_warp_workspace_bytes(int n_src, int n_views, int C, int W, int H);
+int f3dg_forward_warp(void* stream, int n_src, int n_views, int C, int H, int W, const float* image, const float* depth,
+                      const float* valid, const float* rel, float fx, float fy, float z_near, float depth_tolerance,
+                      float occlusion_min_weight, float threshold, int erode, void* workspace, size_t workspace_bytes,
+                      float* warped, float* mask, float* warped_depth, float* weight);
+
+/* Masked L1 of a [n_frames,C,H,W] against b (the warped frame) under m = mask [n_frames,1,H,W], in the mould of the geometry losses.
+ * f3dg_masked_l1_forward writes frame_sums [n_frames,2] = (sum_c sum_pixels m |a - b|, sum_pixels m): a 32 x 16 tile per workgroup
+ * writes its own slot of `partials` (f3dg_masked_l1_partials_bytes(n_frames, C, W, H) bytes), a second kernel adds one frame's slots in
+ * a fixed order. No atomics: bit-reproducible, and a frame's sums read no other frame's data.
+ * f3dg_masked_l1_backward ASSIGNS every element of dL_da = (g[f] m) sign(a - b), g[f] = frame_weights[f,0] (frame_weights [n_frames,2],
+ * the cotangent of frame_sums; column 1 is not read: the mask gets no gradient), sign(0) = 0 as torch.abs's gradient.
+ * F3DG_ERR_BAD_ARG: a NULL pointer, non-positive sizes. F3DG_ERR_WORKSPACE: partials_bytes too small. F3DG_ERR_UNSUPPORTED: C H W or the
+ * number of tiles beyond 2^31 - 1. f3dg_masked_l1_partials_bytes returns 0 for those sizes. All checks happen before any HIP call. */
+size_t f3dg_masked_l1_partials_bytes(int n_frames, int C, int W, int H);
+int f3dg_masked_l1_forward(void* stream, int n_frames, int C, int H, int W, const float* a, const float* b, const float* mask,
+                           float* partials, size_t partials_bytes, float* frame_sums);
+int f3dg_masked_l1_backward(void* stream, int n_frames, int C, int H, int W, const float* a, const float* b, const float* mask,
+                            const float* frame_weights, float* dL_da);
 
 /* Runtime switches: process-wide DEFAULTS for what a call's own flags do not say (every arithmetic / list / path choice of a call has a
  * flag, above). The library knows sixteen names and one diagnostic pair; everything else returns F3DG_ERR_BAD_ARG.
