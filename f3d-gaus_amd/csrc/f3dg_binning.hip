@@ -2,7 +2,8 @@
 //
 // Replaces, for ALL views of a call at once (reference RAST/cuda_rasterizer/rasterizer_impl.cu):
 //   cub::DeviceScan::InclusiveSum      :332      -> sums per 256 depth positions + block_sums_scan_kernel / view_segments_kernel (placing the
-//                                                    instances); scan_* kernels (hand-written reduce / scan / propagate: the general scan)
+//                                                    instances); scan_* kernels (reduce / scan / propagate: the general scan). Every
+//                                                    prefix sum here is one of the three of f3dg_scan.h: wave, workgroup, array in place
 //   the blocking D2H of num_rendered   :336      -> count stays on the device (workspace header)
 //   duplicateWithKeys                  :70-111   -> duplicate_sorted_kernel
 //   cub::DeviceRadixSort::SortPairs    :358-363  -> gsort_* (depth, per Gaussian) and radix2_*_var (tile, per instance) passes of 8 bits
@@ -17,6 +18,7 @@
 // lane, the set of lanes holding the same digit; ranks are popcounts of that 64-bit mask below the lane. Keys
 // are consumed in (wave, round, lane) order which IS memory order, so stability needs no extra bookkeeping.
 #include "f3dg_common.h"
+#include "f3dg_scan.h"
 
 namespace {
 
@@ -43,50 +45,14 @@ scan_reduce_kernel(const u32* __restrict__ in, u64 n, u32* __restrict__ block_su
     if (threadIdx.x == 0) block_sums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-// Exclusive scan of the block sums in place, by one workgroup looping over them; also publishes the total.
+// Exclusive scan of the block sums in place, by one workgroup looping over them; also publishes the total (the call's status).
 __global__ void __launch_bounds__(1024)
 scan_blocksums_kernel(u32* __restrict__ block_sums, u32 nblocks, F3dgHeader* __restrict__ hdr)
 {
-    __shared__ u32 wtot[16];
-    __shared__ u32 carry_s;
-    __shared__ u64 carry64_s, wtot64[16];   // the same sum without wrap-around: a batch can hold more than 2^32 instances (V * P * tiles)
-    if (threadIdx.x == 0) { carry_s = 0; carry64_s = 0; }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (u32 start = 0; start < nblocks; start += 1024) {
-        const u32 i = start + threadIdx.x;
-        const u32 v = i < nblocks ? block_sums[i] : 0;
-        u32 x = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const u32 y = __shfl_up(x, off, 64);
-            if (lane >= off) x += y;
-        }
-        if (lane == 63) wtot[wave] = x;
-        unsigned long long v64 = v;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v64 += __shfl_down(v64, off, 64);
-        if (lane == 0) wtot64[wave] = v64;
-        __syncthreads();
-        u32 wave_off = 0;
-        for (int w = 0; w < wave; w++) wave_off += wtot[w];
-        const u32 carry = carry_s;
-        if (i < nblocks) block_sums[i] = carry + wave_off + x - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) {
-            carry_s = carry + wave_off + x;
-            u64 t = 0;
-            for (int w = 0; w < 16; w++) t += wtot64[w];
-            carry64_s += t;
-        }
-        __syncthreads();
-    }
-    if (hdr && threadIdx.x == 0) {
-        // a wrapped 32-bit total must not pass for a small one: later kernels index the instance arrays with it
-        const u64 total = carry64_s;
-        hdr->num_rendered = total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)total;
-        hdr->overflow = total > (u64)hdr->capacity ? 1u : 0u;
-    }
+    __shared__ u64 wtot[16];
+    // (64 bits: a batch can hold more than 2^32 instances, V * P * tiles)
+    const u64 total = scan_array_in_place<16, 1, u64>(block_sums, nblocks, 0u, wtot);
+    if (hdr) set_status(hdr, total);
 }
 
 __global__ void __launch_bounds__(F3DG_BLOCK)
@@ -110,17 +76,7 @@ scan_apply_kernel(const u32* in, u32* out /* may alias in */, u64 n, const u32* 
     }
 #pragma unroll
     for (int i = 0; i < F3DG_SCAN_ITEMS; i++) s += v[i];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u32 x = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const u32 y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) wtot[wave] = x;
-    __syncthreads();
-    u32 run = block_sums[blockIdx.x] + x - s;
-    for (int w = 0; w < wave; w++) run += wtot[w];
+    u32 run = block_sums[blockIdx.x] + block_scan_exclusive<F3DG_BLOCK / 64>(s, wtot);
     u32 o[F3DG_SCAN_ITEMS];
 #pragma unroll
     for (int i = 0; i < F3DG_SCAN_ITEMS; i++) {
@@ -298,16 +254,7 @@ __device__ __forceinline__ void scatter_chunk(const K* __restrict__ keys_in, con
         const u32 d = threadIdx.x;
         const u32 c0 = sh.cnt[0][d], c1 = sh.cnt[1][d], c2 = sh.cnt[2][d], c3 = sh.cnt[3][d];
         const u32 tot = c0 + c1 + c2 + c3;
-        u32 x = tot;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const u32 y = __shfl_up(x, off, 64);
-            if (lane >= off) x += y;
-        }
-        if (lane == 63) sh.wtot[wave] = x;
-        __syncthreads();
-        u32 excl = x - tot;
-        for (int w = 0; w < wave; w++) excl += sh.wtot[w];
+        const u32 excl = block_scan_exclusive<F3DG_BLOCK / 64>(tot, sh.wtot);
         sh.lbase[d] = excl;
         sh.gdelta[d] = offsets[ck.obase + (u64)d * ck.cps + ck.c] - excl;
         sh.cnt[0][d] = excl;
@@ -392,34 +339,10 @@ __global__ void __launch_bounds__(1024)
 gsort_scan_kernel(u32 n_per_seg /* 256 cps */, u32 seg_len, u32* __restrict__ hist, const u32* __restrict__ skip_compact /* pass 3: minmax */)
 {
     __shared__ u32 wtot[16];
-    __shared__ u32 carry_s;
     u32 kbase;
     if (skip_compact && gsort_compact(skip_compact, blockIdx.x, kbase)) return;      // nothing reads the table of a compact view's pass 3
-    u32* h = hist + (size_t)blockIdx.x * n_per_seg;
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = blockIdx.x * seg_len;
-    __syncthreads();
-    for (u32 base = 0; base < n_per_seg; base += 4096u) {
-        const u32 i = base + 4u * threadIdx.x;                 // n_per_seg is a multiple of 256: whole uint4s
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (i < n_per_seg) v = *reinterpret_cast<const uint4*>(h + i);
-        const u32 tot = v.x + v.y + v.z + v.w;
-        u32 x = tot;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const u32 y = __shfl_up(x, off, 64);
-            if (lane >= (u32)off) x += y;
-        }
-        if (lane == 63u) wtot[wave] = x;
-        __syncthreads();
-        u32 before = carry_s + x - tot;
-        for (u32 w = 0; w < wave; w++) before += wtot[w];
-        if (i < n_per_seg)
-            *reinterpret_cast<uint4*>(h + i) = make_uint4(before, before + v.x, before + v.x + v.y, before + v.x + v.y + v.z);
-        __syncthreads();
-        if (threadIdx.x == 1023u) carry_s = before + tot;
-        __syncthreads();
-    }
+    // (n_per_seg is a multiple of 256: whole uint4s)
+    scan_array_in_place<16, 4, u32>(hist + (size_t)blockIdx.x * n_per_seg, n_per_seg, blockIdx.x * seg_len, wtot);
 }
 
 // key range of every view from the ranges of its chunks (one wave per view)
@@ -470,41 +393,9 @@ gsort_scatter_kernel(const u32* __restrict__ keys_in, const u32* __restrict__ va
 __global__ void __launch_bounds__(1024)
 block_sums_scan_kernel(u32 nb, u32* __restrict__ block_sums, u64* __restrict__ view_total)
 {
-    __shared__ u32 wtot[16];
-    __shared__ u32 carry_s;
-    __shared__ u64 carry64_s, wtot64[16];
-    u32* b = block_sums + (size_t)blockIdx.x * nb;
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) { carry_s = 0; carry64_s = 0; }
-    __syncthreads();
-    for (u32 start = 0; start < nb; start += 1024u) {
-        const u32 i = start + threadIdx.x;
-        const u32 v = i < nb ? b[i] : 0u;
-        u32 x = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const u32 y = __shfl_up(x, off, 64);
-            if (lane >= (u32)off) x += y;
-        }
-        if (lane == 63u) wtot[wave] = x;
-        u64 v64 = v;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v64 += __shfl_down(v64, off, 64);
-        if (lane == 0u) wtot64[wave] = v64;
-        __syncthreads();
-        u32 before = carry_s + x - v;
-        for (u32 w = 0; w < wave; w++) before += wtot[w];
-        if (i < nb) b[i] = before;
-        __syncthreads();
-        if (threadIdx.x == 1023u) {
-            carry_s = before + v;
-            u64 t = 0;
-            for (int w = 0; w < 16; w++) t += wtot64[w];
-            carry64_s += t;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) view_total[blockIdx.x] = carry64_s;
+    __shared__ u64 wtot[16];
+    const u64 total = scan_array_in_place<16, 1, u64>(block_sums + (size_t)blockIdx.x * nb, nb, 0u, wtot);
+    if (threadIdx.x == 0) view_total[blockIdx.x] = total;
 }
 
 // vstart / bglob / xprefix from the views' instance totals, and the call's status: the total of all views (64 bits: a wrapped 32-bit
@@ -514,38 +405,21 @@ __global__ void __launch_bounds__(512)
 view_segments_kernel(int V, const u64* __restrict__ view_total, F3dgHeader* __restrict__ hdr, u32* __restrict__ vstart,
                      u32* __restrict__ bglob, u32* __restrict__ xprefix, u32 xstride)
 {
-    __shared__ u32 carry;
-    __shared__ u32 wtot[8];
-    __shared__ u64 carry64, wtot64[8];
+    __shared__ u64 wtot_v[8];
+    __shared__ u32 wtot_c[8];
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     // first instance of every view (its low 32 bits are the whole of it unless the call overflows)
-    if (threadIdx.x == 0) carry64 = 0;
-    __syncthreads();
+    u64 total = 0;
     for (u32 v0 = 0; v0 < (u32)V; v0 += 512) {
         const u32 v = v0 + threadIdx.x;
-        const u64 t = v < (u32)V ? view_total[v] : 0ull;
-        u64 x = t;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const u64 y = __shfl_up(x, off, 64);
-            if (lane >= (u32)off) x += y;
-        }
-        if (lane == 63) wtot64[wave] = x;
-        __syncthreads();
-        u64 woff = carry64;
-        for (u32 w = 0; w < wave; w++) woff += wtot64[w];
-        if (v < (u32)V) vstart[v] = (u32)(woff + x - t);
-        __syncthreads();
-        if (threadIdx.x == 511) carry64 = woff + x;
+        u64 round;
+        const u64 before = block_scan_exclusive<8>(v < (u32)V ? view_total[v] : 0ull, wtot_v, round);
+        if (v < (u32)V) vstart[v] = (u32)(total + before);
+        total += round;
         __syncthreads();
     }
-    const u64 total = carry64;
-    const bool dead = total > (u64)hdr->capacity;
-    if (threadIdx.x == 0) {
-        hdr->num_rendered = total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)total;
-        hdr->overflow = dead ? 1u : 0u;
-        vstart[V] = dead ? 0u : (u32)total;
-    }
+    const bool dead = set_status(hdr, total);
+    if (threadIdx.x == 0) vstart[V] = dead ? 0u : (u32)total;
     if (dead)
         for (u32 v = threadIdx.x; v < (u32)V; v += 512) vstart[v] = 0u;
     __syncthreads();
@@ -554,39 +428,23 @@ view_segments_kernel(int V, const u64* __restrict__ view_total, F3dgHeader* __re
         return (n + F3DG_SORT_CHUNK - 1) / F3DG_SORT_CHUNK;
     };
     // global chunk prefix, view order
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
+    u32 chunks = 0;
     for (u32 v0 = 0; v0 < (u32)V; v0 += 512) {
         const u32 v = v0 + threadIdx.x;
-        const u32 c = v < (u32)V ? chunks_of(v) : 0u;
-        u32 x = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const u32 y = __shfl_up(x, off, 64);
-            if (lane >= (u32)off) x += y;
-        }
-        if (lane == 63) wtot[wave] = x;
-        __syncthreads();
-        u32 woff = carry;
-        for (u32 w = 0; w < wave; w++) woff += wtot[w];
-        if (v < (u32)V) bglob[v] = woff + x - c;
-        __syncthreads();
-        if (threadIdx.x == 511) carry = woff + x;
+        u32 round;
+        const u32 before = block_scan_exclusive<8>(v < (u32)V ? chunks_of(v) : 0u, wtot_c, round);
+        if (v < (u32)V) bglob[v] = chunks + before;
+        chunks += round;
         __syncthreads();
     }
-    if (threadIdx.x == 0) bglob[V] = carry;
+    if (threadIdx.x == 0) bglob[V] = chunks;
     // per-XCD prefix: wave x scans the chunks of the views x, x + 8, ...
     const u32 nk = ((u32)V > wave) ? ((u32)V - wave + 7u) / 8u : 0u;
     u32 run = 0;
     for (u32 k0 = 0; k0 < nk; k0 += 64) {
         const u32 k = k0 + lane;
         const u32 c = k < nk ? chunks_of(wave + 8u * k) : 0u;
-        u32 x = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const u32 y = __shfl_up(x, off, 64);
-            if (lane >= (u32)off) x += y;
-        }
+        const u32 x = wave_scan_inclusive(c, lane);
         if (k < nk) xprefix[wave * xstride + k] = run + x - c;
         run += __shfl(x, 63, 64);
     }
@@ -601,48 +459,11 @@ view_segments_kernel(int V, const u64* __restrict__ view_total, F3dgHeader* __re
 __global__ void __launch_bounds__(1024)
 tile_scan_kernel(u32 V, const u32* __restrict__ vstart, const u32* __restrict__ bglob, u32* __restrict__ hist)
 {
-    constexpr u32 ITEMS = 16;                 // consecutive entries per thread: four 16-byte loads
     __shared__ u32 wtot[16];
-    __shared__ u32 carry_s;
     const u32 b0 = bglob[blockIdx.x], n = 256u * (bglob[blockIdx.x + 1] - b0);
-    u32* h = hist + 256ull * b0;
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     if (blockIdx.x == 0 && threadIdx.x == 0) hist[256ull * bglob[V]] = vstart[V];
-    if (threadIdx.x == 0) carry_s = vstart[blockIdx.x];
-    __syncthreads();
-    for (u32 base = 0; base < n; base += 1024u * ITEMS) {
-        const u32 i = base + ITEMS * threadIdx.x;             // n is a multiple of 256: whole groups of ITEMS
-        u32 v[ITEMS];
-#pragma unroll
-        for (u32 q = 0; q < ITEMS / 4; q++) {
-            const uint4 w = i < n ? reinterpret_cast<const uint4*>(h + i)[q] : make_uint4(0u, 0u, 0u, 0u);
-            v[4 * q] = w.x; v[4 * q + 1] = w.y; v[4 * q + 2] = w.z; v[4 * q + 3] = w.w;
-        }
-        u32 tot = 0;
-#pragma unroll
-        for (u32 q = 0; q < ITEMS; q++) tot += v[q];
-        u32 x = tot;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const u32 y = __shfl_up(x, off, 64);
-            if (lane >= (u32)off) x += y;
-        }
-        if (lane == 63u) wtot[wave] = x;
-        __syncthreads();
-        u32 run = carry_s + x - tot;
-        for (u32 w = 0; w < wave; w++) run += wtot[w];
-        if (i < n) {
-#pragma unroll
-            for (u32 q = 0; q < ITEMS / 4; q++) {
-                uint4 o;
-                o.x = run; run += v[4 * q]; o.y = run; run += v[4 * q + 1]; o.z = run; run += v[4 * q + 2]; o.w = run; run += v[4 * q + 3];
-                reinterpret_cast<uint4*>(h + i)[q] = o;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 1023u) carry_s = run;          // (the last thread's entries are live or all zero)
-        __syncthreads();
-    }
+    // (16 consecutive entries per thread: four 16-byte loads; n is a multiple of 256)
+    scan_array_in_place<16, 16, u32>(hist + 256ull * b0, n, vstart[blockIdx.x], wtot);
 }
 
 // identifyTileRanges when ONE pass sorted the tile bits: the scanned histogram already holds the first position of every
@@ -793,21 +614,8 @@ duplicate_sorted_kernel(int P, int tile_bits, int grid_x, const u32* __restrict_
         if (cnt) g = perm[pos];
     }
     // a thread's run starts off0 instances into the range, which holds n: exclusive prefix and total of cnt over the workgroup
-    u32 off0, n;
-    {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        u32 incl = cnt;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const u32 t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
-        if (lane == 63) wtot[wave] = incl;
-        __syncthreads();
-        off0 = incl - cnt;
-        for (int w = 0; w < wave; w++) off0 += wtot[w];
-        n = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    }
+    u32 n;
+    const u32 off0 = block_scan_exclusive<F3DG_BLOCK / 64>(cnt, wtot, n);
     const u32 rminx = x & F3DG_RECT_COORD, rmaxx = (x >> 16) & F3DG_RECT_COORD, rminy = y & F3DG_RECT_COORD, rmaxy = (y >> 16) & F3DG_RECT_COORD;
     const u32 view_base = (u32)v << tile_bits;
     // quadrant mask of an instance (f3dg_common.h: F3DG_ID_BITS): the halves of the first / last tile column and row that the

@@ -21,6 +21,7 @@
 // that scan its image rows); a longer list sets the overflow flags and the caller re-runs the call on the general path (f3dg_read_status remembers the shape).
 // Forwards with auxiliary planes take it too (round 5, option small_path_aux): f3dg_backward reads the header and walks the slots.
 #include "f3dg_common.h"
+#include "f3dg_scan.h"
 
 namespace {
 
@@ -40,7 +41,7 @@ struct SmallShared {
     u32 wave_n[SMALL_WAVES];
     u32 wave_min[SMALL_WAVES], wave_max[SMALL_WAVES];
     u64 chit[SMALL_WAVES][SMALL_STEPS / 64];    // which chunks of every wave's share hold the tile
-    u32 wsum[4];
+    u32 wsum[SMALL_WAVES];
     u32 skip;
 };
 static_assert(sizeof(u64) * SMALL_STEPS * SMALL_WAVES <= 2 * sizeof(u32) * F3DG_SMALL_CAP, "the hit masks must fit buffer 0");
@@ -183,13 +184,8 @@ small_bin_kernel(u32 P, u32 T, u32 grid_x, F3dgHeader* __restrict__ hdr, const u
         u32 run = off;
         for (u32 s0 = 0; s0 < nsteps; s0 += 64u) {
             u64 m = s0 + lane < nsteps ? wbal[s0 + lane] : 0ull;
-            u32 x = (u32)__popcll(m);
-            const u32 mine = x;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const u32 y = (u32)__shfl_up((int)x, o, 64);
-                if (lane >= (u32)o) x += y;
-            }
+            const u32 mine = (u32)__popcll(m);
+            const u32 x = wave_scan_inclusive(mine, lane);
             u32 at = run + x - mine;
             const u32 gbase = g0 + 64u * (s0 + lane);
             while (m != 0ull) {
@@ -259,24 +255,15 @@ small_bin_kernel(u32 P, u32 T, u32 grid_x, F3dgHeader* __restrict__ hdr, const u
         for (u32 i = e0 + lane; i < e1; i += 64u)
             atomicAdd(&sh.hist[wave][(sh.buf[2u * cur][i] >> shift) & 255u], 1u);
         __syncthreads();
-        // thread d < 256: total of digit d, exclusive scan over the digits, per-wave offsets
-        u32 tot = 0, x = 0;
+        // thread d < 256: total of digit d, exclusive scan over the digits (by the whole workgroup: the other threads add 0), per-wave offsets
+        u32 tot = 0;
         if (threadIdx.x < 256u) {
 #pragma unroll
             for (u32 w = 0; w < SMALL_WAVES; w++) tot += sh.hist[w][threadIdx.x];
             if (tot == n) sh.skip = 1;                      // every entry has this digit: the pass is the identity
-            x = tot;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const u32 y = __shfl_up(x, o, 64);
-                if (lane >= (u32)o) x += y;
-            }
-            if (lane == 63) sh.wsum[wave] = x;
         }
-        __syncthreads();
+        u32 run = block_scan_exclusive<SMALL_WAVES>(tot, sh.wsum);
         if (threadIdx.x < 256u) {
-            u32 run = x - tot;
-            for (u32 w = 0; w < wave; w++) run += sh.wsum[w];
 #pragma unroll
             for (u32 w = 0; w < SMALL_WAVES; w++) {
                 const u32 h = sh.hist[w][threadIdx.x];

@@ -3,6 +3,14 @@ a view-local scan of them plus the views' totals (block_sums_scan_kernel, view_s
 from the rectangles (duplicate_sorted_kernel), and a per-view scan of the tile pass's histogram (tile_scan_kernel). The shapes here
 are the ones at which that can go wrong. Every case holds the final list, the ranges and the count to the oracle's exactly (lists
 without tile culling), and the images of the default, culled call to the plain transcription's (option reference_kernels) bit for bit.
+
+The one-workgroup scans loop over their array in rounds and carry the sum of the earlier rounds (f3dg_scan.h: scan_array_in_place,
+block_scan_exclusive). The last cases pin a second round of each, and each asserts first, from the oracle, that something the later
+kernels READ lies in that round -- a round of zeros that nothing reads would pass with a wrong carry: gsort_scan_kernel (more than
+4,096 entries = 16 chunks per view, Gaussians with a low key byte of 241 and up), block_sums_scan_kernel (more than 1,024 block sums
+per view with instances in the blocks from 1,024 on, together with the general three-kernel scan of the depth sort, more than 64
+chunks per view), tile_scan_kernel (more than 16,384 entries = 64 chunks of instances in a view of 256 tiles, instances in tiles
+whose entries lie past the first round) and both scans of view_segments_kernel (more than 512 views, the 513th with instances).
 """
 import ctypes as C
 import functools
@@ -307,3 +315,83 @@ def test_capacity_far_above_the_count_takes_the_general_tile_scan(gpu_device):
     assert (cap + SORT_CHUNK - 1) // SORT_CHUNK + 3 > 512 * 3
     h, _ = _check(scene, gpu_device, max_rendered=cap)
     assert h["workspace"].max_rendered == cap
+
+
+# ------------------------------------------------------------------------------------------------ later rounds of the one-workgroup scans
+def test_depth_sort_scan_second_round(gpu_device):
+    """17 chunks per view: a view's [256][17] histogram block is 4,352 entries, more than the 4,096 (1,024 threads x 4) of one round of
+    gsort_scan_kernel -- the second round starts from the first one's carry. Two views: the second one's scan starts at P."""
+    P = 65537
+    cps = (P + SORT_CHUNK - 1) // SORT_CHUNK
+    assert cps == 17 and 256 * cps > 1024 * 4 and cps <= 64
+    scene = make_scene(P=P, res=(72, 40), s0=0.01, seed=31, view=[0, 3])
+    ora = _oracle_views(scene)
+    for o in ora["per"]:        # digit d's entries are [17 d, 17 d + 17): the first pass reads the second round's for d >= 241
+        low = np.array(o["depths"], dtype=np.float32).view(np.uint32)[np.array(o["tiles_touched"]) > 0] & 255
+        assert o["num_rendered"] > 0 and int((low >= -(-4096 // cps)).sum()) > 0
+    _check(scene, gpu_device, ora)
+
+
+@pytest.mark.parametrize("P", [262400, 266240])
+def test_general_depth_sort_scan_and_block_sums_second_round(P, gpu_device):
+    """65 chunks per view: the depth sort's histograms take the general three-kernel scan (and a compact view's fourth pass its stand-in
+    histogram); more than 1,024 block sums per view: block_sums_scan_kernel takes a second round. At P = 262,400 that round is the one
+    block 1,024, which holds Gaussians that touch no tile only (they sort last): the round runs, but its carry reaches no instance. At
+    P = 266,240 (1,040 blocks) blocks of the second round hold instances: their workgroups' bases and the view's total need the carry."""
+    nb = (P + 255) // 256
+    assert (P + SORT_CHUNK - 1) // SORT_CHUNK == 65 > 64 and nb > 1024
+    scene = make_scene(P=P, res=(72, 40), s0=0.004, seed=37, view=[3])
+    ora = _oracle_views(scene)
+    c = _depth_order_counts(ora["per"][0])
+    assert int(c[:1024 * 256].sum()) > 0
+    if P == 266240:
+        assert int(c[1024 * 256:].sum()) > 0
+    _check(scene, gpu_device, ora)
+
+
+def _tile_scan_rounds(ora):
+    """Of one view: entries of its block of the tile pass's histogram, and the instances in tiles whose entries -- digit d's are
+    [d chunks, (d + 1) chunks) -- start past the first round of tile_scan_kernel (1,024 threads x 16)."""
+    chunks = (ora["num_rendered"] + SORT_CHUNK - 1) // SORT_CHUNK
+    r = ora["ranges"][0].astype(np.int64)
+    n = r[:, 1] - r[:, 0]
+    return 256 * chunks, int(n[np.arange(len(n)) * chunks >= 1024 * 16].sum())
+
+
+def test_tile_scan_second_round(gpu_device):
+    """One view of more than 64 chunks of instances: its [256][chunks] block of the tile pass's histogram is more than the 16,384
+    entries of one round of tile_scan_kernel, in a workspace that still takes the per-view scan. 15 tiles: the digits in use end at
+    entry 15 x 79, so the second round runs over zeros that nothing reads -- it must end, no more (the next case reads it)."""
+    scene = make_scene(P=30000, res=(72, 40), s0=0.2, seed=43, view=[3])
+    ora = _oracle_views(scene)
+    assert _tile_scan_rounds(ora)[0] > 1024 * 16
+    h, _ = _check(scene, gpu_device, ora)
+    assert (h["workspace"].max_rendered + SORT_CHUNK - 1) // SORT_CHUNK + 1 <= 512 * 1
+
+
+def test_tile_scan_second_round_is_read(gpu_device):
+    """256 tiles (one 8-bit pass, every digit a tile) and 118 chunks of instances in the one view: the entries of the tiles from 139 on
+    lie in the second round of tile_scan_kernel, and the scatter and the ranges read them."""
+    scene = make_scene(P=20000, res=(256, 256), s0=0.05, seed=53, view=[3])
+    ora = _oracle_views(scene)
+    entries, read_past_first = _tile_scan_rounds(ora)
+    assert 1024 * 16 < entries <= 2 * 1024 * 16 and read_past_first > 0
+    h, _ = _check(scene, gpu_device, ora)
+    assert (h["workspace"].max_rendered + SORT_CHUNK - 1) // SORT_CHUNK + 1 <= 512 * 1
+
+
+@functools.lru_cache(maxsize=None)
+def _tiny_scene():
+    return make_scene(P=40, res=(32, 16), s0=0.05, seed=47, view=range(9))
+
+
+def test_view_segment_scans_second_round(gpu_device):
+    """513 views of two tiles: view_segments_kernel's scans of the views' totals and of their chunk counts take a second round of
+    512 views, whose one view -- it has instances -- starts where the 512 before it end."""
+    cams = [i % 9 for i in range(513)]
+    scene = _views(_tiny_scene(), cams)
+    V, T = len(cams), ((scene["W"] + 15) // 16) * ((scene["H"] + 15) // 16)
+    assert V > 512 and T == 2 and ((V - 1) << 1 | 1) <= 0xFFFF          # one tile pass, u16 group stream
+    per = [run_oracle(_tiny_scene(), c) for c in range(9)]
+    assert all(o["num_rendered"] > 0 for o in per), [o["num_rendered"] for o in per]
+    _check(scene, gpu_device, _joined([per[c] for c in cams]))
