@@ -16,13 +16,14 @@ _sys.modules.setdefault("diff_gof_rasterization", diff_gof_rasterization)
 from .diff_gof_rasterization import (GaussianRasterizationSettings_GOF, GaussianRasterizer_GOF,  # noqa: E402,F401
                                      rasterize_views, rasterize_views_autograd, set_deferred_status, deferred_status, flush)
 
-from . import gaussian_renderer, gaussian_predictor, unet_gs, cycle, dist, ply, mesh, losses, frames, warp  # noqa: E402,F401
+from . import gaussian_renderer, gaussian_predictor, unet_gs, cycle, dist, ply, mesh, losses, frames, warp, tsdf  # noqa: E402,F401
 from .gaussian_renderer import (render_predicted_more_v2_gof, render_predicted_more_v3_gof,  # noqa: E402,F401
                                 render_predicted_more_v2_gof_in, AlphaSweep,
                                 render_views, depth_to_normal, depths_to_points)
 from .gaussian_predictor import GaussianSplatPredictor_gtunet, splat_head, splat_head_merge  # noqa: E402,F401
 from .unet_gs import Unet_GS_gtunet  # noqa: E402,F401
-from .mesh import marching_tetrahedra, tetra_points, bisect_level_set, extract_mesh  # noqa: E402,F401
+from .mesh import marching_tetrahedra, tetra_points, bisect_level_set, extract_mesh, extract_mesh_tsdf  # noqa: E402,F401
+from .tsdf import TSDFVolume  # noqa: E402,F401
 from .frames import compose_frames, compose_orbit_frames, depth_range, colormap_lut  # noqa: E402,F401
 from .warp import forward_warp, relative_transforms  # noqa: E402,F401
 

@@ -13,6 +13,7 @@ FLAG_EXACT, FLAG_FAST, FLAG_NO_TILE_CULL, FLAG_NO_SMALL_PATH, FLAG_SCAN, FLAG_SE
 PENDING = 1
 GEOM_ALPHA_WEIGHT = 1
 MAX_PANELS, PANEL_RGB, PANEL_SIGNED, PANEL_COLORMAP = 8, 0, 1, 2
+TSDF_MAX_VIEWS = 128
 
 
 class Panel(C.Structure):
@@ -110,6 +111,14 @@ SIGNATURES = {
     "f3dg_masked_l1_partials_bytes": (_sz, [_i, _i, _i, _i]),
     "f3dg_masked_l1_forward": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "f3dg_masked_l1_backward": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    # stream | nx ny nz origin(host [3]) voxel trunc z_near | n_views H W | depth color alpha alpha_min world_view fx fy | tsdf weight color color_weight
+    "f3dg_tsdf_integrate": (_i, [_p, _i, _i, _i, C.POINTER(_f), _f, _f, _f, _i, _i, _i, _p, _p, _p, _f, _p, _f, _f, _p, _p, _p, _p]),
+    # nx ny nz  /  stream | nx ny nz | min_weight tsdf weight | workspace workspace_bytes h_n_active  /  ... | workspace workspace_bytes n_active tets
+    "f3dg_tsdf_cells_workspace_bytes": (_sz, [_i, _i, _i]),
+    "f3dg_tsdf_cells_count": (_i, [_p, _i, _i, _i, _f, _p, _p, _p, _sz, C.POINTER(_ll)]),
+    "f3dg_tsdf_cells_emit": (_i, [_p, _i, _i, _i, _p, _sz, _ll, _p]),
+    # stream | nx ny nz origin(host [3]) voxel | E interp_v | tsdf color color_weight | vertices vertex_colors
+    "f3dg_tsdf_vertices": (_i, [_p, _i, _i, _i, C.POINTER(_f), _f, _ll, _p, _p, _p, _p, _p, _p]),
     "f3dg_set_option": (_i, [C.c_char_p, _i]),
     "f3dg_profile_enable": (_i, [_i]),
     "f3dg_debug_launch_count": (C.c_longlong, [_i]),

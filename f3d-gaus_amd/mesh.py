@@ -8,6 +8,9 @@
 ``marching_tetrahedra`` has the signature and return structure of src/utils_tetmesh.py:141-190. Its integer topology (which edges cross
 the level set, their order, the triangles) is the HIP library's (f3dg_marching_tets_count / _emit, csrc/f3dg_mesh.hip); the three
 gathers are plain torch indexing, so the result stays differentiable in ``vertices`` and ``sdf`` exactly as in the reference.
+
+``extract_mesh_tsdf`` is the route that needs no ``cells`` from outside: the orbit's rendered depth fused into a TSDF volume
+(``f3dgaus_amd.tsdf``) whose surface cells the library itself turns into tetrahedra. Its semantics are this project's, not the reference's.
 No CPU fallback: tensors that are not on a HIP device raise."""
 import ctypes as C
 import math
@@ -197,6 +200,47 @@ def bisect_level_set(sweep, end_points, end_sdf, n_steps=8):
         left_points = torch.where(ind_low, mid_points, left_points)
         right_points = torch.where(ind_low, right_points, mid_points)
     return (left_points + right_points) / 2
+
+
+@torch.no_grad()
+def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, resolution=256, bounds=None, trunc=None, alpha_min=0.5):
+    """The TSDF route to a coloured mesh of image ``bs`` of the Gaussian dict ``pc`` -- no tetrahedralisation from outside, nothing but
+    this package (the semantics are this project's: ``f3dgaus_amd.tsdf``). All cameras are rendered in one
+    launch sequence (``render_views(..., channels="rgb_depth_alpha", epilogue=False)``), depth, alpha and colour are fused into a
+    volume whose longest side has ``resolution`` voxels (cubic voxels; the other sides as many as the box needs), and the zero level
+    set is triangulated. ``bounds`` = ((x0, y0, z0), (x1, y1, z1)) in world space; None takes the box of ``pc["xyz"][bs]`` padded by
+    the truncation distance (one host read). ``trunc`` defaults to four voxels. Returns ``TSDFVolume.extract``'s dict, ready for
+    ``ply.save_mesh_ply(path, m["vertices"], m["faces"], (m["vertex_colors"].clamp(0, 1) * 255).round().to(torch.uint8))``."""
+    from .gaussian_renderer import render_views
+    from .tsdf import TSDFVolume
+    xyz = pc["xyz"][bs]
+    _require_hip(xyz, world_views)
+    resolution = int(resolution)
+    if resolution < 2:
+        raise ValueError(f"extract_mesh_tsdf: resolution {resolution} must be at least 2")
+    if bounds is None:
+        box = torch.stack([xyz.detach().min(dim=0)[0], xyz.detach().max(dim=0)[0]]).double().cpu()
+        lo, hi = box[0].tolist(), box[1].tolist()
+    else:
+        lo, hi = [float(v) for v in bounds[0]], [float(v) for v in bounds[1]]
+    if not all(math.isfinite(a) and math.isfinite(b) and b > a for a, b in zip(lo, hi)):
+        raise ValueError(f"extract_mesh_tsdf: empty or non-finite bounds {lo} .. {hi}")
+    longest = max(b - a for a, b in zip(lo, hi))
+    if bounds is not None:
+        voxel = longest / (resolution - 1)
+    else:
+        # the padded box is longest + 2 trunc wide and spans resolution - 1 voxel edges; a default trunc is four of those edges
+        if trunc is None and resolution < 10:
+            raise ValueError(f"extract_mesh_tsdf: resolution {resolution} leaves no room for the default padding of four voxels a side")
+        voxel = longest / (resolution - 9) if trunc is None else (longest + 2 * float(trunc)) / (resolution - 1)
+        pad = 4 * voxel if trunc is None else float(trunc)
+        lo, hi = [a - pad for a in lo], [b + pad for b in hi]
+    dims = tuple(max(2, int(math.ceil((b - a) / voxel - 1e-9)) + 1) for a, b in zip(lo, hi))
+    vol = TSDFVolume(lo, voxel, dims, trunc=trunc, device=xyz.device)
+    out = render_views(pc, bs, world_views, full_projs, camera_centers, bg, cfg, channels="rgb_depth_alpha", epilogue=False)
+    vol.integrate(out["rendered_depth"], world_views.reshape(-1, 4, 4), cfg['model']['fov'], color=out["render"].contiguous(),
+                  alpha=out["rendered_alpha"], alpha_min=alpha_min)
+    return vol.extract()
 
 
 @torch.no_grad()

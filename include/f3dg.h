@@ -49,6 +49,10 @@
  *       the depth-based forward warp behind the settings' w_warping / w_prop (threshold, erode_kernel_size, erode_pad_size:
  *       config/imagenetgs_256x256_v1.yaml:50-66) and the masked L1 against it. The reference ships the settings, no trainer and no
  *       warp: the semantics are this build's, defined below
+ *   f3dg_tsdf_integrate / f3dg_tsdf_cells_count / f3dg_tsdf_cells_emit / f3dg_tsdf_vertices
+ *       the TSDF mesh route (depth maps fused into a volume, its surface cells as tetrahedra for f3dg_marching_tets_*): the reference
+ *       meshes through an external Delaunay tetrahedralisation (visualize.py:440-548) and holds no TSDF code: the semantics are this
+ *       build's, defined below
  *
  * Memory ownership mirrors the reference: outputs and the workspace are allocated and owned by the caller
  * (torch tensors on the Python side). Instead of growing buffers through callbacks in the middle of the call
@@ -685,6 +689,71 @@ int f3dg_masked_l1_forward(void* stream, int n_frames, int C, int H, int W, cons
                            float* partials, size_t partials_bytes, float* frame_sums);
 int f3dg_masked_l1_backward(void* stream, int n_frames, int C, int H, int W, const float* a, const float* b, const float* mask,
                             const float* frame_weights, float* dL_da);
+
+/* TSDF fusion: rendered depth maps fused into a truncated signed distance volume, the volume's surface cells as tetrahedra for
+ * f3dg_marching_tets_count / _emit, and the crossing edges as vertices and vertex colours -- a mesh route that needs no external
+ * tetrahedralisation. THE SEMANTICS ARE THIS PROJECT'S (the reference holds no TSDF code); tests/tsdf_truth.py restates them in float64.
+ *
+ * Volume. Dimensions (nx, ny, nz), `origin` [3] (a HOST array) the world position of the centre of voxel (0,0,0), `voxel` the edge
+ *   length. Voxel (x, y, z) has the linear id (z ny + y) nx + x and the centre p = origin + voxel (x, y, z). nx ny nz < 2^31
+ *   (F3DG_ERR_UNSUPPORTED beyond). Caller-owned state, float32, plane-major so that x is the fastest axis of every access:
+ *   tsdf [nz,ny,nx] a weighted mean in [-1, 1], weight [nz,ny,nx], color [3,nz,ny,nx] a weighted mean, color_weight [nz,ny,nx].
+ *   All-zero means empty.
+ * One view's sample at a voxel. The conventions are the forward warp's: row-vector world_view [n_views,16] (row-major 4 x 4, a world
+ *   point as a row times world_view is the camera point), the rasterizer's pixel centre, depth [n_views,H,W] read as z-depth.
+ *   (X, Y, Z) = p world_view[:3,:3] + world_view[3,:3]. The sample is live iff Z > z_near. Pixel i = floor(fx X / Z + W/2),
+ *   j = floor(fy Y / Z + H/2) (pixel i has its centre at i + 0.5); the two coordinates are range-checked as floating-point numbers
+ *   before any conversion to int, so +-huge, +-Inf and NaN touch nothing; the sample stays live iff 0 <= coordinate < W (H).
+ *   d = depth[v,j,i]; the sample stays live iff d is finite and d > 0 and, when `alpha` [n_views,H,W] is given, alpha[v,j,i] >= alpha_min
+ *   (a NaN alpha is not live). sdf = d - Z; the sample is dropped iff sdf < -trunc; t = min(1, sdf / trunc). The sample is also a
+ *   COLOUR sample iff |sdf| <= trunc: a free-space observation must not tint a voxel with the surface behind it. The colour
+ *   (color [n_views,3,H,W]) and depth of a pixel that is not live never enter arithmetic. The library evaluates all of this in float64
+ *   on the float32 arguments.
+ * One call, n_views views. Per voxel, over the live samples in ascending view order: S = sum t, n = their number; Cs = sum colour,
+ *   nc = the number of colour samples (float64 sums). Then, ASSIGNED once per call and rounded to float32 once:
+ *   tsdf <- (tsdf weight + S) / (weight + n), weight <- weight + n where n > 0 and weight + n > 0; the same for color / color_weight
+ *   with Cs and nc. A voxel with n = 0 (nc = 0) is not written: its tsdf and weight (color and color_weight) keep their bits. Every
+ *   voxel has one writer, the views are taken in a fixed order and there are no atomics: the outputs are bit-reproducible. A second call
+ *   accumulates further views into the same volume. Weights are float32 counts: exact up to 2^24 samples per voxel.
+ *   One launch serves up to F3DG_TSDF_MAX_VIEWS views (the camera table of the kernel); a call with more runs consecutive launches over
+ *   consecutive view ranges, which equals consecutive calls with those ranges to the bit. With color == NULL the arrays color_out and
+ *   color_weight may be NULL and are untouched.
+ * Surface cells. Cell (x, y, z), x < nx - 1, y < ny - 1, z < nz - 1, has the id (z (ny - 1) + y)(nx - 1) + x. It is ACTIVE iff all
+ *   eight corners have weight >= min_weight and a finite tsdf, and the corners do not all agree on tsdf < 0. An active cell yields the
+ *   six tetrahedra of the Kuhn split along its (0,0,0)-(1,1,1) diagonal, one per order of the axes, vertices as voxel ids: with b the
+ *   cell's (0,0,0) corner and X = 1, Y = nx, Z = nx ny, in THIS order
+ *       xyz (b, b+X+Y, b+X, b+X+Y+Z)   xzy (b, b+X, b+X+Z, b+X+Y+Z)   yxz (b, b+Y, b+X+Y, b+X+Y+Z)
+ *       yzx (b, b+Y+Z, b+Y, b+X+Y+Z)   zxy (b, b+X+Z, b+Z, b+X+Y+Z)   zyx (b, b+Z, b+Y+Z, b+X+Y+Z)
+ *   -- the path along the axes in the named order with the two middle vertices of three of the orders swapped, so that all six have
+ *   the same orientation, the signed volume (v0 - v3) . ((v1 - v3) x (v2 - v3)) / 6 > 0. That is the orientation for which the triangle
+ *   table of f3dg_marching_tets_emit turns every face's normal towards the free side (out of the surface); with the textbook volume
+ *   above it is the even orders (xyz, yzx, zxy) whose path is swapped. tets [6 n_active, 4] int32, cells in ascending id.
+ *   f3dg_tsdf_cells_count: classification, one bit per cell and the scanned counts into `workspace`
+ *   (f3dg_tsdf_cells_workspace_bytes(nx, ny, nz) bytes, 16-byte aligned, caller-owned); BLOCKING, one host read: *h_n_active.
+ *   f3dg_tsdf_cells_emit: after a count on the same workspace and volume; writes the tets, at most n_active cells of them (the capacity
+ *   of `tets`, 16-byte aligned), and reads nothing back. On a workspace that holds no completed count of this volume it writes nothing.
+ * Mesh. f3dg_marching_tets_count / _emit on sdf = -tsdf with these tets: occupied means behind the surface, tsdf == 0 is free.
+ *   f3dg_tsdf_vertices, one thread per crossing edge (lo, hi) of interp_v [E,2] int64, in float32 in exactly this order: o = the end with
+ *   tsdf < 0 (lo if both), f = the other; w = t_f / (t_f - t_o) where t_f - t_o > 0, else 0; p(id) = origin + voxel * (x, y, z);
+ *   vertex = p_f + (p_o - p_f) * w; vertex colour = c_f + (c_o - c_f) * w per channel where both ends have color_weight > 0, the
+ *   colour of the one end that has otherwise, 0 where neither has. vertices [E,3], vertex_colors [E,3] or NULL (then color and
+ *   color_weight may be NULL). An id outside [0, nx ny nz) indexes nothing: that row is zeros.
+ * F3DG_ERR_BAD_ARG, found on the host before any launch: a NULL required pointer (origin, depth, world_view, tsdf, weight; color_out or
+ *   color_weight with a color; workspace, h_n_active, tets, interp_v, vertices; color or color_weight with vertex_colors); non-positive
+ *   sizes (dimensions, n_views, H, W, E; n_active for emit); voxel, trunc, fx or fy not finite or <= 0; a non-finite origin; z_near
+ *   negative or not finite; a NaN alpha_min or min_weight; a dimension below 2 for the cell entries; a workspace or tets off the 16-byte
+ *   grid. F3DG_ERR_UNSUPPORTED: nx ny nz >= 2^31, H W >= 2^31. F3DG_ERR_WORKSPACE: workspace_bytes too small.
+ *   f3dg_tsdf_cells_workspace_bytes returns 0 for every volume the cell entries refuse. */
+#define F3DG_TSDF_MAX_VIEWS 128
+int f3dg_tsdf_integrate(void* stream, int nx, int ny, int nz, const float* origin, float voxel, float trunc, float z_near, int n_views,
+                        int H, int W, const float* depth, const float* color, const float* alpha, float alpha_min, const float* world_view,
+                        float fx, float fy, float* tsdf, float* weight, float* color_out, float* color_weight);
+size_t f3dg_tsdf_cells_workspace_bytes(int nx, int ny, int nz);
+int f3dg_tsdf_cells_count(void* stream, int nx, int ny, int nz, float min_weight, const float* tsdf, const float* weight, void* workspace,
+                          size_t workspace_bytes, long long* h_n_active);
+int f3dg_tsdf_cells_emit(void* stream, int nx, int ny, int nz, void* workspace, size_t workspace_bytes, long long n_active, int* tets);
+int f3dg_tsdf_vertices(void* stream, int nx, int ny, int nz, const float* origin, float voxel, long long E, const long long* interp_v,
+                       const float* tsdf, const float* color, const float* color_weight, float* vertices, float* vertex_colors);
 
 /* Runtime switches: process-wide DEFAULTS for what a call's own flags do not say (every arithmetic / list / path choice of a call has a
  * flag, above). The library knows sixteen names and one diagnostic pair; everything else returns F3DG_ERR_BAD_ARG.
