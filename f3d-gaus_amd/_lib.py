@@ -119,6 +119,13 @@ SIGNATURES = {
     "f3dg_tsdf_cells_emit": (_i, [_p, _i, _i, _i, _p, _sz, _ll, _p]),
     # stream | nx ny nz origin(host [3]) voxel | E interp_v | tsdf color color_weight | vertices vertex_colors
     "f3dg_tsdf_vertices": (_i, [_p, _i, _i, _i, C.POINTER(_f), _f, _ll, _p, _p, _p, _p, _p, _p]),
+    # N F  /  stream ws ws_bytes | N F faces faces_int32 | face_component component_faces h_counts[4]
+    "f3dg_mesh_components_workspace_bytes": (_sz, [_ll, _ll]),
+    "f3dg_mesh_components": (_i, [_p, _p, _sz, _ll, _ll, _p, _i, _p, _p, C.POINTER(_ll)]),
+    # N F  /  stream ws ws_bytes | N F faces faces_int32 face_component keep_root | h_counts[2]  /  ... | n_faces_kept n_vertices_kept faces_out vertex_ids
+    "f3dg_mesh_compact_workspace_bytes": (_sz, [_ll, _ll]),
+    "f3dg_mesh_compact_count": (_i, [_p, _p, _sz, _ll, _ll, _p, _i, _p, _p, C.POINTER(_ll)]),
+    "f3dg_mesh_compact_emit": (_i, [_p, _p, _sz, _ll, _ll, _p, _i, _p, _p, _ll, _ll, _p, _p]),
     "f3dg_set_option": (_i, [C.c_char_p, _i]),
     "f3dg_profile_enable": (_i, [_i]),
     "f3dg_debug_launch_count": (C.c_longlong, [_i]),

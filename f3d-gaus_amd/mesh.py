@@ -110,6 +110,125 @@ def marching_tetrahedra(vertices, tets, sdf, scales):
     return list(zip(*outs))
 
 
+def _faces_arg(faces, who):
+    _require_hip(faces)
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"{who}: faces must be [F,3] int64 or int32, got {tuple(faces.shape)} {faces.dtype}")
+    return faces.contiguous()
+
+
+def _components_raw(faces, N):
+    """f3dg_mesh_components: (face_component [F] int32 root ids or -1, component_faces [N] int32, (C, largest, degenerate, rounds))."""
+    F, dev = int(faces.shape[0]), faces.device
+    if N <= 0:
+        raise ValueError(f"mesh components: the mesh needs at least one vertex (got {N})")
+    L = _lib.lib()
+    nbytes = L.f3dg_mesh_components_workspace_bytes(N, F)
+    if nbytes == 0:
+        raise _lib.F3dgError(_lib.ERR_UNSUPPORTED, "f3dg_mesh_components_workspace_bytes")
+    counts = (C.c_longlong * 4)()
+    with torch.cuda.device(dev):
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        face_root = torch.empty((F,), dtype=torch.int32, device=dev)
+        root_faces = torch.empty((N,), dtype=torch.int32, device=dev)
+        _lib.check(L.f3dg_mesh_components(_stream(), _lib.ptr(ws), nbytes, N, F, _lib.ptr(faces), int(faces.dtype == torch.int32),
+                                          _lib.ptr(face_root), _lib.ptr(root_faces), counts), "f3dg_mesh_components")
+    return face_root, root_faces, tuple(int(c) for c in counts)
+
+
+def _rank_components(face_root, root_faces):
+    """The dense ranking, torch glue over the C roots: (roots [C], sizes [C], rank_of_root [N] (-1 where no root), face_component [F])."""
+    roots = torch.nonzero(root_faces > 0).reshape(-1)                           # ascending
+    sizes, order = torch.sort(root_faces[roots].to(torch.int64), descending=True, stable=True)       # equal sizes keep the roots' order
+    roots = roots[order]
+    rank = torch.full((root_faces.shape[0],), -1, dtype=torch.int64, device=root_faces.device)
+    rank[roots] = torch.arange(roots.shape[0], dtype=torch.int64, device=roots.device)
+    fr = face_root.to(torch.int64)
+    face_component = torch.where(fr >= 0, rank[fr.clamp(min=0)], fr)
+    return roots, sizes, rank, face_component
+
+
+@torch.no_grad()
+def mesh_components(faces, n_vertices):
+    """The connected components of the mesh ``faces`` [F,3] (int64 or int32, on a HIP device) over ``n_vertices`` vertices
+    (f3dg_mesh_components, csrc/f3dg_mesh_clean.hip; the definition is include/f3dg.h's). Two faces are connected when they share a
+    vertex ID (vertex connectivity, not edge adjacency; no welding of coincident vertices); a face with two equal ids is degenerate
+    and belongs to no component; a face with an id outside [0, n_vertices) raises. Returns a dict:
+        face_component [F] int64      the dense index of the face's component, -1 for a degenerate face
+        component_sizes [C] int64     faces per component
+        component_roots [C] int64     the least vertex id of each component
+        n_degenerate, rounds          the degenerate faces, and the hook / compress / verify rounds the library needed
+    Components are ordered by size, largest first, and by root ascending among equal sizes. Every output is a function of the input
+    alone: bit-reproducible."""
+    faces = _faces_arg(faces, "mesh_components")
+    face_root, root_faces, counts = _components_raw(faces, int(n_vertices))
+    roots, sizes, _, face_component = _rank_components(face_root, root_faces)
+    return {"face_component": face_component, "component_sizes": sizes, "component_roots": roots, "n_degenerate": counts[2], "rounds": counts[3]}
+
+
+def clean_mesh(vertices, faces, vertex_colors=None, *, min_faces=None, keep_largest=None, min_fraction=None):
+    """Drop the small connected components ("floaters") of a mesh and renumber what is left (f3dg_mesh_components, f3dg_mesh_compact_count /
+    _emit). ``vertices`` [N,3], ``faces`` [F,3] int64 or int32, ``vertex_colors`` [N,...] or None, all on one HIP device. A component
+    (``mesh_components``) is kept iff it has at least ``min_faces`` faces AND is among the ``keep_largest`` first of the ranking AND has
+    at least ``min_fraction`` of the largest component's faces -- each criterion only where it is given; with all three None every
+    component is kept and only degenerate faces and unreferenced vertices go. Returns a dict:
+        vertices [n,3], vertex_colors [n,...] or None     gathered by ``vertex_ids`` with torch indexing: differentiable
+        faces [f,3] int64                                 the kept faces in their input order, in the new numbering
+        vertex_ids [n] int64                              the old id of each new vertex, ascending
+        face_component [f] int64, component_sizes [K]     the kept faces' component and the kept components' sizes (the kept ones are
+                                                          always the first K of the ranking, so the indices are ``mesh_components``')"""
+    _require_hip(vertices)
+    faces = _faces_arg(faces, "clean_mesh")
+    if vertices.dim() != 2 or faces.device != vertices.device:
+        raise ValueError(f"clean_mesh: vertices must be [N,C] on the device of faces, got {tuple(vertices.shape)} on {vertices.device}")
+    N, F, dev = int(vertices.shape[0]), int(faces.shape[0]), vertices.device
+    if vertex_colors is not None:
+        _require_hip(vertex_colors)
+        if vertex_colors.shape[0] != N or vertex_colors.device != dev:
+            raise ValueError(f"clean_mesh: vertex_colors must hold one row per vertex ({N}) on {dev}, got {tuple(vertex_colors.shape)}")
+    with torch.no_grad():
+        if N == 0:
+            if F:
+                raise ValueError("clean_mesh: faces over an empty vertex set")
+            face_root = torch.empty((0,), dtype=torch.int32, device=dev)
+            sizes = face_component = vertex_ids = torch.empty((0,), dtype=torch.int64, device=dev)
+            keep_sizes, faces_out = sizes, torch.empty((0, 3), dtype=torch.int64, device=dev)
+        else:
+            face_root, root_faces, _ = _components_raw(faces, N)
+            roots, sizes, _, face_component = _rank_components(face_root, root_faces)
+            keep = torch.ones_like(sizes, dtype=torch.bool)
+            if min_faces is not None:
+                keep &= sizes >= int(min_faces)
+            if keep_largest is not None:
+                keep &= torch.arange(sizes.shape[0], device=dev) < int(keep_largest)
+            if min_fraction is not None and sizes.shape[0]:
+                keep &= sizes.to(torch.float64) >= float(min_fraction) * sizes[0].to(torch.float64)
+            keep_root = torch.zeros((N,), dtype=torch.uint8, device=dev)
+            keep_root[roots[keep]] = 1
+            keep_sizes = sizes[keep]
+            L = _lib.lib()
+            nbytes = L.f3dg_mesh_compact_workspace_bytes(N, F)
+            if nbytes == 0:
+                raise _lib.F3dgError(_lib.ERR_UNSUPPORTED, "f3dg_mesh_compact_workspace_bytes")
+            counts = (C.c_longlong * 2)()
+            is32 = int(faces.dtype == torch.int32)
+            with torch.cuda.device(dev):
+                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+                _lib.check(L.f3dg_mesh_compact_count(_stream(), _lib.ptr(ws), nbytes, N, F, _lib.ptr(faces), is32, _lib.ptr(face_root),
+                                                     _lib.ptr(keep_root), counts), "f3dg_mesh_compact_count")
+                nf, nv = int(counts[0]), int(counts[1])
+                faces_out = torch.empty((nf, 3), dtype=torch.int64, device=dev)
+                vertex_ids = torch.empty((nv,), dtype=torch.int64, device=dev)
+                if nf > 0:
+                    _lib.check(L.f3dg_mesh_compact_emit(_stream(), _lib.ptr(ws), nbytes, N, F, _lib.ptr(faces), is32, _lib.ptr(face_root),
+                                                        _lib.ptr(keep_root), nf, nv, _lib.ptr(faces_out), _lib.ptr(vertex_ids)),
+                               "f3dg_mesh_compact_emit")
+            fr = face_root.to(torch.int64)
+            face_component = face_component[(fr >= 0) & (keep_root[fr.clamp(min=0)] != 0)]
+    return {"vertices": vertices[vertex_ids], "faces": faces_out, "vertex_colors": None if vertex_colors is None else vertex_colors[vertex_ids],
+            "vertex_ids": vertex_ids, "face_component": face_component, "component_sizes": keep_sizes}
+
+
 def build_rotation(r):
     """visualize.py:42-63: rotation matrices [P,3,3] of (unnormalised) quaternions [P,4] (w, x, y, z), in its float32 operation order."""
     norm = torch.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + r[:, 2] * r[:, 2] + r[:, 3] * r[:, 3])
@@ -203,14 +322,19 @@ def bisect_level_set(sweep, end_points, end_sdf, n_steps=8):
 
 
 @torch.no_grad()
-def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, resolution=256, bounds=None, trunc=None, alpha_min=0.5):
+def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, resolution=256, bounds=None, trunc=None, alpha_min=0.5,
+                      min_component_faces=None, keep_largest=None):
     """The TSDF route to a coloured mesh of image ``bs`` of the Gaussian dict ``pc`` -- no tetrahedralisation from outside, nothing but
     this package (the semantics are this project's: ``f3dgaus_amd.tsdf``). All cameras are rendered in one
     launch sequence (``render_views(..., channels="rgb_depth_alpha", epilogue=False)``), depth, alpha and colour are fused into a
     volume whose longest side has ``resolution`` voxels (cubic voxels; the other sides as many as the box needs), and the zero level
     set is triangulated. ``bounds`` = ((x0, y0, z0), (x1, y1, z1)) in world space; None takes the box of ``pc["xyz"][bs]`` padded by
     the truncation distance (one host read). ``trunc`` defaults to four voxels. Returns ``TSDFVolume.extract``'s dict, ready for
-    ``ply.save_mesh_ply(path, m["vertices"], m["faces"], (m["vertex_colors"].clamp(0, 1) * 255).round().to(torch.uint8))``."""
+    ``ply.save_mesh_ply(path, m["vertices"], m["faces"], (m["vertex_colors"].clamp(0, 1) * 255).round().to(torch.uint8))``.
+
+    ``min_component_faces`` / ``keep_largest`` (opt-in; with both None the dict is exactly ``extract``'s): ``clean_mesh`` with ``min_faces``
+    / ``keep_largest`` on the extracted mesh. ``vertices`` / ``faces`` / ``vertex_colors`` are then the cleaned ones and ``components``
+    holds ``vertex_ids`` (rows of ``interp_v``), ``face_component`` and ``component_sizes``."""
     from .gaussian_renderer import render_views
     from .tsdf import TSDFVolume
     xyz = pc["xyz"][bs]
@@ -240,11 +364,18 @@ def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, 
     out = render_views(pc, bs, world_views, full_projs, camera_centers, bg, cfg, channels="rgb_depth_alpha", epilogue=False)
     vol.integrate(out["rendered_depth"], world_views.reshape(-1, 4, 4), cfg['model']['fov'], color=out["render"].contiguous(),
                   alpha=out["rendered_alpha"], alpha_min=alpha_min)
-    return vol.extract()
+    m = vol.extract()
+    if min_component_faces is None and keep_largest is None:
+        return m
+    c = clean_mesh(m["vertices"], m["faces"], m["vertex_colors"], min_faces=min_component_faces, keep_largest=keep_largest)
+    m.update(vertices=c["vertices"], faces=c["faces"], vertex_colors=c["vertex_colors"],
+             components={k: c[k] for k in ("vertex_ids", "face_component", "component_sizes")})
+    return m
 
 
 @torch.no_grad()
-def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, camera_centers, bg, cfg, n_binary_steps=8, sweep=None):
+def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, camera_centers, bg, cfg, n_binary_steps=8, sweep=None,
+                 min_component_faces=None, keep_largest=None):
     """visualize.py:447-546 for image ``bs`` of the Gaussian dict ``pc``: alpha of ``points`` [n,3] over all cameras (one ``AlphaSweep``,
     built here unless one is handed in), marching tetrahedra of ``cells`` [F,4] (any tetrahedralisation of ``points``; the reference's
     is CGAL on the host) on sdf = alpha - 0.5, ``n_binary_steps`` bisection steps, and the scale filter
@@ -252,7 +383,9 @@ def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, c
         vertices [E,3], faces [nf,3] int64, keep [E] bool                      the unfiltered mesh and the filter
         vertices_filtered, faces_filtered                                      the kept vertices and the faces whose three corners
                                                                                are kept, re-indexed (what update_vertices /
-                                                                               update_faces leave, :545-546)"""
+                                                                               update_faces leave, :545-546)
+    With ``min_component_faces`` or ``keep_largest`` set (opt-in; the keys above are untouched) the dict also carries ``vertices_clean`` /
+    ``faces_clean``: ``clean_mesh`` with ``min_faces`` / ``keep_largest`` on ``vertices_filtered`` / ``faces_filtered``."""
     from .gaussian_renderer import AlphaSweep
     _require_hip(points, points_scale, cells)
     own = sweep is None
@@ -273,5 +406,9 @@ def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, c
     keep = distance <= 3 * scale
     face_mask = keep[faces].all(dim=1)
     new_index = torch.cumsum(keep.to(torch.int64), 0) - 1
-    return {"vertices": vertices, "faces": faces, "keep": keep,
-            "vertices_filtered": vertices[keep], "faces_filtered": new_index[faces[face_mask]]}
+    out = {"vertices": vertices, "faces": faces, "keep": keep,
+           "vertices_filtered": vertices[keep], "faces_filtered": new_index[faces[face_mask]]}
+    if min_component_faces is not None or keep_largest is not None:
+        c = clean_mesh(out["vertices_filtered"], out["faces_filtered"], min_faces=min_component_faces, keep_largest=keep_largest)
+        out["vertices_clean"], out["faces_clean"] = c["vertices"], c["faces"]
+    return out

@@ -53,6 +53,10 @@
  *       the TSDF mesh route (depth maps fused into a volume, its surface cells as tetrahedra for f3dg_marching_tets_*): the reference
  *       meshes through an external Delaunay tetrahedralisation (visualize.py:440-548) and holds no TSDF code: the semantics are this
  *       build's, defined below
+ *   f3dg_mesh_components / f3dg_mesh_compact_count / f3dg_mesh_compact_emit
+ *       what follows either mesh route: connected components of the triangles and the removal of the small ones. The reference's
+ *       script leaves that to trimesh on the host (update_vertices / update_faces, visualize.py:545-546) and labels no components:
+ *       the semantics are this build's, defined below
  *
  * Memory ownership mirrors the reference: outputs and the workspace are allocated and owned by the caller
  * (torch tensors on the Python side). Instead of growing buffers through callbacks in the middle of the call
@@ -754,6 +758,52 @@ int f3dg_tsdf_cells_count(void* stream, int nx, int ny, int nz, float min_weight
 int f3dg_tsdf_cells_emit(void* stream, int nx, int ny, int nz, void* workspace, size_t workspace_bytes, long long n_active, int* tets);
 int f3dg_tsdf_vertices(void* stream, int nx, int ny, int nz, const float* origin, float voxel, long long E, const long long* interp_v,
                        const float* tsdf, const float* color, const float* color_weight, float* vertices, float* vertex_colors);
+
+/* Mesh clean-up: the connected components of a triangle mesh, and the compaction that keeps the chosen ones. Integers only: every
+ * output is a function of the input alone and bit-reproducible. THE SEMANTICS ARE THIS PROJECT'S; tests/mesh_clean_truth.py restates them.
+ *
+ * Mesh. faces [F,3] int64 (faces_int32 = 0) or int32 (faces_int32 = 1) over N vertices, 0 < N < 2^31, 0 <= F < 2^31.
+ *   A face with an id outside [0, N) makes the call fail with F3DG_ERR_BAD_ARG: every id is range-checked on the device before anything
+ *   is indexed with it, and a refused mesh writes none of the outputs.
+ *   A face is DEGENERATE when two of its ids are equal. It belongs to no component: its label is -1, it is counted on its own and
+ *   compaction always drops it.
+ *   Two non-degenerate faces are CONNECTED when they share a VERTEX ID, and components are the classes of the transitive closure. This is
+ *   vertex connectivity, not edge adjacency: the coarser relation (two unions per face, no edge table). It is the right one for floater
+ *   removal -- a piece that touches the body in a single vertex is not a floater -- and it knows nothing of positions: two vertices at
+ *   one place with two ids are two vertices (no welding).
+ *   A component's LABEL is the least vertex id among the vertices of its faces (its root). A duplicate face counts as often as it occurs.
+ * f3dg_mesh_components: BLOCKING. workspace: f3dg_mesh_components_workspace_bytes(N, F) bytes, 16-byte aligned, caller-owned.
+ *   face_component [F] int32, every element written: the root of the face's component, -1 for a degenerate face.
+ *   component_faces [N] int32, every element written: the number of faces of the component at its root's index, 0 everywhere else (a
+ *   vertex no non-degenerate face uses is the root of nothing).
+ *   h_counts[0..3] = number of components, faces of the largest, degenerate faces, rounds used. F == 0 is legal: all counts 0.
+ *   Method: a union-find forest over the vertices in the workspace, parent[v] <= v at all times; a round is hook (two unions per face:
+ *   roots are hooked by compare-and-swap, the greater root under the lesser, a failed swap continues from the value it returned),
+ *   compress (every vertex to its root) and verify (a count of the faces whose corners do not all point at one self-parented root),
+ *   followed by one 8-byte host read of that count and the range flag; rounds are repeated while the count is non-zero, at most 32 of
+ *   them (F3DG_ERR_UNSUPPORTED beyond; with coherent atomics the first round converges). One more host read returns the counts.
+ * f3dg_mesh_compact_count: BLOCKING, one host read. workspace: f3dg_mesh_compact_workspace_bytes(N, F) bytes, 16-byte aligned.
+ *   face_component as f3dg_mesh_components wrote it, keep_root [N] uint8. A face is KEPT iff face_component >= 0 and
+ *   keep_root[face_component] != 0 (a face_component >= N keeps nothing); a vertex is KEPT iff a kept face uses it. A kept face with an
+ *   id outside [0, N) is F3DG_ERR_BAD_ARG as above. h_counts[0..1] = kept faces, kept vertices.
+ * f3dg_mesh_compact_emit: after a count that returned F3DG_OK, same workspace, sizes and inputs; no host read.
+ *   faces_out [n_faces_kept,3] int64: the kept faces in their input order, in the NEW numbering; vertex_ids [n_vertices_kept] int64: the
+ *   old id of each new vertex, ascending (new id = the number of kept vertices with a smaller old id). The two counts are the capacities
+ *   of the arrays: rows beyond them are not written. On a workspace that holds no completed count of a mesh of these sizes nothing is
+ *   written.
+ * Refused before any HIP call, nothing written (h_counts included): F3DG_ERR_BAD_ARG for a NULL workspace, face_component,
+ *   component_faces, h_counts, keep_root, faces_out or vertex_ids (faces and face_component may be NULL where F == 0), N <= 0, F < 0,
+ *   non-positive n_faces_kept or n_vertices_kept, a workspace off the 16-byte grid, faces_out or vertex_ids off the 8-byte grid; F3DG_ERR_UNSUPPORTED for N or F at or
+ *   above 2^31; F3DG_ERR_WORKSPACE for workspace_bytes too small. The two *_workspace_bytes return 0 for every size the calls refuse. */
+size_t f3dg_mesh_components_workspace_bytes(long long N, long long F);
+int f3dg_mesh_components(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, const void* faces, int faces_int32,
+                         int* face_component, int* component_faces, long long* h_counts);
+size_t f3dg_mesh_compact_workspace_bytes(long long N, long long F);
+int f3dg_mesh_compact_count(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, const void* faces,
+                            int faces_int32, const int* face_component, const unsigned char* keep_root, long long* h_counts);
+int f3dg_mesh_compact_emit(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, const void* faces,
+                           int faces_int32, const int* face_component, const unsigned char* keep_root, long long n_faces_kept,
+                           long long n_vertices_kept, long long* faces_out, long long* vertex_ids);
 
 /* Runtime switches: process-wide DEFAULTS for what a call's own flags do not say (every arithmetic / list / path choice of a call has a
  * flag, above). The library knows sixteen names and one diagnostic pair; everything else returns F3DG_ERR_BAD_ARG.
