@@ -47,8 +47,7 @@ def _render(scene, device, scan, channels="all", th=None, small_kernels=False):
         torch.cuda.synchronize()
         kernel = L.f3dg_debug_last_render_kernel()
     finally:
-        L.f3dg_set_option(b"render_scan_th", 12)
-        L.f3dg_set_option(b"render_lowocc", 1)
+        helpers.restore_render_options("render_scan_th", "render_lowocc")
     return out.cpu().numpy(), kernel
 
 
