@@ -6,22 +6,23 @@
 //   occupancy_kernel   sdf > 0 as one bit per point (NaN and 0 are outside), :98
 //   classify_kernel    one thread per tetrahedron: range check of the four ids BEFORE anything is indexed with them, case index
 //                      sum occ_i 2^i (:126), per-workgroup counts of the one- and two-triangle tetrahedra, cnt[lo] += 1 per crossing edge
-//   (scan)             cnt -> start: every point `lo` owns the bucket [start[lo], start[lo + 1]) of the `hi` ends of its crossing edges
+//   (scans)            the two count arrays (the ballots and the ranks are f3dg_compact.h's; the arrays are long enough here to keep
+//                      the three-launch scan), and cnt -> start: every point `lo` owns the bucket [start[lo], start[lo + 1]) of the
+//                      `hi` ends of its crossing edges
 //   scatter_kernel     hi into the bucket of lo (integer atomics hand out the slots; their arrival order is erased by the sort below)
 //   sort_small_kernel  buckets of at most 32 entries: one thread each, insertion sort in place; longer buckets are queued
 //   sort_big_kernel    one 1024-thread workgroup per queued bucket: bitonic network in LDS (up to 8192 entries) or in place
 //   (scan)             first-occurrence flags -> rank of every bucket entry = row of that edge in interp_v: buckets are in `lo` order and
 //                      sorted by `hi`, so the rows are in ascending lexicographic order by construction, as torch.unique leaves them
 //   faces_kernel       one thread per tetrahedron: binary search of its crossing edges in their buckets, the triangle table (:23-43),
-//                      rows written at the scanned offset (one-triangle tetrahedra first, then the two-triangle ones, :131-136); every
+//                      rows written at the scanned count plus the rank inside the workgroup (block_rank; the ballots are rebuilt from the
+//                      cases, no flag words are stored), one-triangle tetrahedra first, then the two-triangle ones (:131-136); every
 //                      thread also writes the (lo, hi) row of the edges it looks up (all writers of a row write the same two values)
 // Nothing here is floating-point arithmetic and every count is an integer sum: the outputs are bit-reproducible.
 #include "f3dg_common.h"
+#include "f3dg_compact.h"
 
 namespace {
-
-typedef unsigned long long u64;
-typedef unsigned int u32;
 
 #define MESH_SMALL 32u              // longest bucket one thread sorts
 #define MESH_BIG_THREADS 1024
@@ -41,19 +42,17 @@ struct MeshLayout {
     u32 scan_tmp_elems, big_cap;
 };
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 MeshLayout mesh_layout(long long N, long long F, long long cap)
 {
     MeshLayout L;
     const size_t nb = (size_t)((F + F3DG_BLOCK - 1) / F3DG_BLOCK);
     size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = align256(o + bytes); return at; };
+    auto take = [&](size_t bytes) { const size_t at = o; o = f3dg_align256(o + bytes); return at; };
     L.header = take(sizeof(MeshHeader));
     L.occ = take((size_t)((N + 63) / 64) * 8);
     L.cases = take((size_t)F);
-    L.blk_one = take((nb + 1) * 4);
-    L.blk_two = take((nb + 1) * 4);
+    L.blk_one = take(nb * 4);
+    L.blk_two = take(nb * 4);
     L.cnt = take((size_t)(N + 1) * 4);
     L.start = take((size_t)(N + 1) * 4);
     const size_t big_cap = (size_t)cap / (MESH_SMALL + 1) + 1;          // a queued bucket holds more than MESH_SMALL entries
@@ -63,7 +62,7 @@ MeshLayout mesh_layout(long long N, long long F, long long cap)
     L.first = take((size_t)(cap + 1) * 4);
     size_t longest = (size_t)N + 1;
     if ((size_t)cap + 1 > longest) longest = (size_t)cap + 1;
-    if (nb + 1 > longest) longest = nb + 1;
+    if (nb > longest) longest = nb;
     L.scan_tmp_elems = (u32)((longest + F3DG_SCAN_CHUNK - 1) / F3DG_SCAN_CHUNK);
     L.scan_tmp = take((size_t)L.scan_tmp_elems * 4);
     L.total = o;
@@ -111,8 +110,7 @@ occupancy_kernel(const float* __restrict__ sdf, u32 N, u64* __restrict__ occ)
 {
     const u32 i = blockIdx.x * F3DG_BLOCK + threadIdx.x;
     const bool in = i < N && sdf[i] > 0.0f;            // NaN > 0 is false
-    const u64 m = __ballot(in);
-    if ((threadIdx.x & 63) == 0 && i < N) occ[i >> 6] = m;
+    store_flag_word(occ, __ballot(in), i, N);
 }
 
 template <typename I>
@@ -144,14 +142,14 @@ classify_kernel(const I* __restrict__ tets, u32 F, u32 N, const u64* __restrict_
         cases[t] = (unsigned char)c;
     }
     const u32 nt = case_triangles(c);
-    const u32 ones = __popcll(__ballot(nt == 1u)), twos = __popcll(__ballot(nt == 2u));
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) emitted += __shfl_down(emitted, off, 64);
-    if ((threadIdx.x & 63) == 0) { w_one[threadIdx.x >> 6] = ones; w_two[threadIdx.x >> 6] = twos; w_emit[threadIdx.x >> 6] = emitted; }
+    if ((threadIdx.x & 63) == 0) w_emit[threadIdx.x >> 6] = emitted;
+    wave_ballot(nt == 1u, w_one);
+    wave_ballot(nt == 2u, w_two);
     __syncthreads();
     if (threadIdx.x == 0) {
-        const u32 o = w_one[0] + w_one[1] + w_one[2] + w_one[3], w = w_two[0] + w_two[1] + w_two[2] + w_two[3];
-        const u32 m = w_emit[0] + w_emit[1] + w_emit[2] + w_emit[3];
+        const u32 o = block_count(w_one), w = block_count(w_two), m = block_count(w_emit);
         blk_one[blockIdx.x] = o;
         blk_two[blockIdx.x] = w;
         if (o) atomicAdd(&hdr->n_one, o);
@@ -268,14 +266,10 @@ faces_kernel(const I* __restrict__ tets, u32 F, u32 N, const unsigned char* __re
     const u32 t = blockIdx.x * F3DG_BLOCK + threadIdx.x;
     const u32 c = t < F ? cases[t] : 0u;
     const u32 nt = case_triangles(c);
-    const u64 m_one = __ballot(nt == 1u), m_two = __ballot(nt == 2u);
-    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { w_one[wave] = __popcll(m_one); w_two[wave] = __popcll(m_two); }
+    const u64 m_one = wave_ballot(nt == 1u, w_one), m_two = wave_ballot(nt == 2u, w_two);
     __syncthreads();
     if (nt == 0u) return;
-    const u64 below = (1ull << lane) - 1ull;
-    u64 at = nt == 1u ? (u64)blk_one[blockIdx.x] + __popcll(m_one & below) : (u64)blk_two[blockIdx.x] + __popcll(m_two & below);
-    for (u32 w = 0; w < wave; w++) at += nt == 1u ? w_one[w] : w_two[w];
+    const u64 at = nt == 1u ? (u64)blk_one[blockIdx.x] + block_rank(m_one, w_one) : (u64)blk_two[blockIdx.x] + block_rank(m_two, w_two);
 
     u32 v[4];
     load_tet(tets, t, N, v);
@@ -332,8 +326,6 @@ int count_impl(hipStream_t s, char* ws, const MeshLayout& L, u32 N, u32 F, long 
 
     F3DG_HIP_CHECK(hipMemsetAsync(hdr, 0, sizeof(MeshHeader), s));
     F3DG_HIP_CHECK(hipMemsetAsync(cnt, 0, ((size_t)N + 1) * 4, s));
-    F3DG_HIP_CHECK(hipMemsetAsync(blk_one + nb, 0, 4, s));
-    F3DG_HIP_CHECK(hipMemsetAsync(blk_two + nb, 0, 4, s));
     F3DG_KLAUNCH(occupancy_kernel, dim3(nbN), dim3(F3DG_BLOCK), 0, s, sdf, N, occ);
     F3DG_KLAUNCH(classify_kernel<I>, dim3(nb), dim3(F3DG_BLOCK), 0, s, tets, F, N, occ, cases, cnt, blk_one, blk_two, hdr);
     F3DG_HIP_CHECK(hipGetLastError());
@@ -353,9 +345,11 @@ int count_impl(hipStream_t s, char* ws, const MeshLayout& L, u32 N, u32 F, long 
 
     int rc = f3dg_launch_scan_inclusive(s, cnt, start, (u64)N + 1, scan_tmp, L.scan_tmp_elems, 1, nullptr);
     if (rc != F3DG_OK) return rc;
-    rc = f3dg_launch_scan_inclusive(s, blk_one, blk_one, (u64)nb + 1, scan_tmp, L.scan_tmp_elems, 1, nullptr);
+    // the two count arrays keep the three-launch scan: at the mesh path's size they hold 125,611 counts each, 31 rounds of 4,096 for
+    // the single workgroup of compact_scan_counts, which measured slower than these six launches (profiles/mesh_compaction_refactor.md)
+    rc = f3dg_launch_scan_inclusive(s, blk_one, blk_one, (u64)nb, scan_tmp, L.scan_tmp_elems, 1, nullptr);
     if (rc != F3DG_OK) return rc;
-    rc = f3dg_launch_scan_inclusive(s, blk_two, blk_two, (u64)nb + 1, scan_tmp, L.scan_tmp_elems, 1, nullptr);
+    rc = f3dg_launch_scan_inclusive(s, blk_two, blk_two, (u64)nb, scan_tmp, L.scan_tmp_elems, 1, nullptr);
     if (rc != F3DG_OK) return rc;
     F3DG_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)N * 4, s));         // from here on: the fill count of every bucket
     F3DG_HIP_CHECK(hipMemsetAsync(first + M, 0, 4, s));

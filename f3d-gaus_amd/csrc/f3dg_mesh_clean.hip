@@ -19,23 +19,19 @@
 //   cc_label_kernel      one thread per face: its label, and the per-root face counts. A closed surface is ONE address, so equal labels
 //                        are combined within the wave first (a ballot loop over the distinct labels, one atomicAdd of the popcount each).
 //   cc_stats_kernel      a fixed grid over the vertices: the number of roots that own faces and the largest count, one atomic per workgroup
-// Compaction: flags, counts per workgroup, one scan, emission at the scanned offsets -- the shape of the TSDF cell entries (f3dg_tsdf.hip).
-//   mc_flag_kernel       one thread per face: one keep bit per face (a ballot per wave), the workgroup's count, and one bit per used vertex
+// Compaction (f3dg_compact.h), of the kept faces and of the vertices they use:
+//   mc_flag_kernel       one thread per face: the face's flag and the workgroup's count (block_flag_and_count), and one bit per used vertex
 //                        (atomicOr: order-free)
-//   mc_vcount_kernel     one thread per 256 vertices: their count
-//   mc_scan_kernel       one workgroup: scan_array_in_place (f3dg_scan.h) over both count arrays, totals and `ready` into the header
-//   mc_emit_faces_kernel / mc_emit_vertices_kernel   one thread per face / vertex at its rank; a vertex's new id is its rank among the used
-//                        bits (the workgroup's scanned count, the words before it, the bits below it). Rows of 24 bytes at data-dependent
-//                        offsets and single 8-byte ids: no 16-byte store fits either layout; the count arrays are scanned in uint4s.
+//   mc_vcount_kernel     one thread per 256 vertices: their count (the vertex bits come from atomics, not from a ballot)
+//   mc_scan_kernel       one workgroup: compact_scan_counts over both count arrays, totals and `ready` into the header
+//   mc_emit_faces_kernel / mc_emit_vertices_kernel   one thread per face / vertex at its compact_rank; a vertex's new id is its rank among
+//                        the used bits. Rows of 24 bytes at data-dependent offsets and single 8-byte ids: no 16-byte store fits either
+//                        layout; the count arrays are scanned in uint4s.
 #include "f3dg_common.h"
-#include "f3dg_scan.h"
+#include "f3dg_compact.h"
 
 namespace {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
-#define MC_SCAN_ITEMS 16
 #define MC_MAX_ROUNDS 32
 #define MC_READY 0x6D636C6Eu
 #define MC_STATS_BLOCKS 1024u
@@ -57,30 +53,24 @@ struct McHeader {                   // first 256 bytes of the compaction workspa
 
 struct McLayout {
     size_t header, flags_f, flags_v, blk_f, blk_v, total;
-    u32 nb_f, nb_v, nw_f, nw_v, ns_f, ns_v;       // workgroups, 64-bit words, scan lengths (whole MC_SCAN_ITEMS) of the faces / vertices
+    CompactPlan f, v;                               // of the faces / vertices
 };
-
-size_t mc_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 McLayout mc_layout(u32 N, u32 F)
 {
     McLayout L;
-    L.nb_f = (F + F3DG_BLOCK - 1) / F3DG_BLOCK;
-    L.nb_v = (N + F3DG_BLOCK - 1) / F3DG_BLOCK;
-    L.nw_f = (F + 63u) / 64u;
-    L.nw_v = (N + 63u) / 64u;
-    L.ns_f = (L.nb_f + MC_SCAN_ITEMS - 1) / MC_SCAN_ITEMS * MC_SCAN_ITEMS;
-    L.ns_v = (L.nb_v + MC_SCAN_ITEMS - 1) / MC_SCAN_ITEMS * MC_SCAN_ITEMS;
+    L.f = compact_plan(F);
+    L.v = compact_plan(N);
     L.header = 0;
-    L.flags_f = mc_align256(sizeof(McHeader));
-    L.flags_v = L.flags_f + mc_align256((size_t)L.nw_f * 8);
-    L.blk_f = L.flags_v + mc_align256((size_t)L.nw_v * 8);
-    L.blk_v = L.blk_f + mc_align256((size_t)L.ns_f * 4);
-    L.total = L.blk_v + mc_align256((size_t)L.ns_v * 4);
+    L.flags_f = f3dg_align256(sizeof(McHeader));
+    L.flags_v = L.flags_f + L.f.flag_bytes;
+    L.blk_f = L.flags_v + L.v.flag_bytes;
+    L.blk_v = L.blk_f + L.f.count_bytes;
+    L.total = L.blk_v + L.v.count_bytes;
     return L;
 }
 
-size_t cc_total(u32 N) { return mc_align256(sizeof(CcHeader)) + mc_align256((size_t)N * 4); }
+size_t cc_total(u32 N) { return f3dg_align256(sizeof(CcHeader)) + f3dg_align256((size_t)N * 4); }
 
 // F3DG_OK, or why the sizes are refused
 int mc_check_sizes(long long N, long long F)
@@ -265,14 +255,7 @@ mc_flag_kernel(const I* __restrict__ faces, u32 F, u32 N, const int* __restrict_
             }
         }
     }
-    const u64 m = __ballot(keep);
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0u) {
-        if (f < F) flags_f[f >> 6] = m;
-        w_cnt[wave] = (u32)__popcll(m);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) blk_f[blockIdx.x] = w_cnt[0] + w_cnt[1] + w_cnt[2] + w_cnt[3];
+    block_flag_and_count(keep, f, F, flags_f, blk_f, w_cnt);
 }
 
 __global__ void __launch_bounds__(F3DG_BLOCK)
@@ -289,8 +272,8 @@ __global__ void __launch_bounds__(F3DG_BLOCK)
 mc_scan_kernel(u32* __restrict__ blk_f, u32 ns_f, u32* __restrict__ blk_v, u32 ns_v, u32 N, u32 F, McHeader* __restrict__ hdr)
 {
     __shared__ u64 wtot[F3DG_BLOCK / 64];
-    const u64 nf = scan_array_in_place<F3DG_BLOCK / 64, MC_SCAN_ITEMS, u64>(blk_f, ns_f, 0u, wtot);
-    const u64 nv = scan_array_in_place<F3DG_BLOCK / 64, MC_SCAN_ITEMS, u64>(blk_v, ns_v, 0u, wtot);
+    const u64 nf = compact_scan_counts(blk_f, ns_f, wtot);
+    const u64 nv = compact_scan_counts(blk_v, ns_v, wtot);
     if (threadIdx.x == 0) {
         hdr->n_faces = nf;
         hdr->n_vertices = nv;
@@ -304,15 +287,6 @@ __device__ __forceinline__ bool mc_ready(const McHeader* __restrict__ hdr, u32 N
     return hdr->ready == MC_READY && hdr->N == N && hdr->F == F;
 }
 
-// the new id of the used vertex v: the used vertices below it (v < N; the words read are those of v's own 256-vertex group)
-__device__ __forceinline__ u64 mc_rank(const u64* __restrict__ flags_v, const u32* __restrict__ blk_v, u32 v)
-{
-    const u32 w = v >> 6;
-    u64 r = (u64)blk_v[v >> 8] + (u64)__popcll(flags_v[w] & ((1ull << (v & 63u)) - 1ull));
-    for (u32 k = w & ~3u; k < w; k++) r += (u64)__popcll(flags_v[k]);
-    return r;
-}
-
 template <typename I>
 __global__ void __launch_bounds__(F3DG_BLOCK)
 mc_emit_faces_kernel(const I* __restrict__ faces, u32 F, u32 N, u64 n_rows, const u64* __restrict__ flags_f, const u64* __restrict__ flags_v,
@@ -320,19 +294,16 @@ mc_emit_faces_kernel(const I* __restrict__ faces, u32 F, u32 N, u64 n_rows, cons
 {
     if (!mc_ready(hdr, N, F)) return;                       // no completed count of this mesh on the workspace
     const u32 f = blockIdx.x * F3DG_BLOCK + threadIdx.x;
-    if (f >= F) return;
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, word = f >> 6;      // word = 4 blockIdx.x + wave
-    const u64 m = flags_f[word];
-    if (!((m >> lane) & 1ull)) return;
-    u64 row = (u64)blk_f[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
-    for (u32 w = 0; w < wave; w++) row += (u64)__popcll(flags_f[word - wave + w]);
+    if (f >= F || !compact_kept(flags_f, f)) return;
+    const u64 row = compact_rank(flags_f, blk_f, f);
     if (row >= n_rows) return;                              // the caller's array ends here
     u32 v[3];
     if (!load_face(faces, f, N, v)) return;                 // (not the faces that were counted)
     long long* out = faces_out + 3 * row;
-    out[0] = (long long)mc_rank(flags_v, blk_v, v[0]);
-    out[1] = (long long)mc_rank(flags_v, blk_v, v[1]);
-    out[2] = (long long)mc_rank(flags_v, blk_v, v[2]);
+    // a used vertex's new id: the used vertices below it
+    out[0] = (long long)compact_rank(flags_v, blk_v, v[0]);
+    out[1] = (long long)compact_rank(flags_v, blk_v, v[1]);
+    out[2] = (long long)compact_rank(flags_v, blk_v, v[2]);
 }
 
 __global__ void __launch_bounds__(F3DG_BLOCK)
@@ -341,9 +312,8 @@ mc_emit_vertices_kernel(u32 N, u32 F, u64 n_rows, const u64* __restrict__ flags_
 {
     if (!mc_ready(hdr, N, F)) return;
     const u32 v = blockIdx.x * F3DG_BLOCK + threadIdx.x;
-    if (v >= N) return;
-    if (!((flags_v[v >> 6] >> (v & 63u)) & 1ull)) return;
-    const u64 row = mc_rank(flags_v, blk_v, v);
+    if (v >= N || !compact_kept(flags_v, v)) return;
+    const u64 row = compact_rank(flags_v, blk_v, v);
     if (row < n_rows) vertex_ids[row] = (long long)v;
 }
 
@@ -351,7 +321,7 @@ template <typename I>
 int components_impl(hipStream_t s, char* ws, u32 N, u32 F, const I* faces, int* face_component, int* component_faces, long long* h_counts)
 {
     CcHeader* hdr = reinterpret_cast<CcHeader*>(ws);
-    u32* parent = reinterpret_cast<u32*>(ws + mc_align256(sizeof(CcHeader)));
+    u32* parent = reinterpret_cast<u32*>(ws + f3dg_align256(sizeof(CcHeader)));
     const u32 nb_f = (F + F3DG_BLOCK - 1) / F3DG_BLOCK, nb_v = (N + F3DG_BLOCK - 1) / F3DG_BLOCK;
     F3DG_HIP_CHECK(hipMemsetAsync(hdr, 0, sizeof(CcHeader), s));
     F3DG_KLAUNCH(cc_init_kernel, dim3(nb_v), dim3(F3DG_BLOCK), 0, s, parent, N);
@@ -395,12 +365,13 @@ int compact_count_impl(hipStream_t s, char* ws, const McLayout& L, u32 N, u32 F,
     u32* blk_f = reinterpret_cast<u32*>(ws + L.blk_f);
     u32* blk_v = reinterpret_cast<u32*>(ws + L.blk_v);
     F3DG_HIP_CHECK(hipMemsetAsync(hdr, 0, sizeof(McHeader), s));
-    F3DG_HIP_CHECK(hipMemsetAsync(flags_v, 0, (size_t)L.nw_v * 8, s));
-    if (L.ns_f > L.nb_f) F3DG_HIP_CHECK(hipMemsetAsync(blk_f + L.nb_f, 0, (size_t)(L.ns_f - L.nb_f) * 4, s));
-    if (L.ns_v > L.nb_v) F3DG_HIP_CHECK(hipMemsetAsync(blk_v + L.nb_v, 0, (size_t)(L.ns_v - L.nb_v) * 4, s));
-    F3DG_KLAUNCH(mc_flag_kernel<I>, dim3(L.nb_f), dim3(F3DG_BLOCK), 0, s, faces, F, N, face_component, keep_root, flags_f, flags_v, blk_f, hdr);
-    F3DG_KLAUNCH(mc_vcount_kernel, dim3((L.nb_v + F3DG_BLOCK - 1) / F3DG_BLOCK), dim3(F3DG_BLOCK), 0, s, (const u64*)flags_v, L.nw_v, blk_v, L.nb_v);
-    F3DG_KLAUNCH(mc_scan_kernel, dim3(1), dim3(F3DG_BLOCK), 0, s, blk_f, L.ns_f, blk_v, L.ns_v, N, F, hdr);
+    F3DG_HIP_CHECK(hipMemsetAsync(flags_v, 0, (size_t)L.v.n_words * 8, s));
+    F3DG_HIP_CHECK(compact_clear_padding(s, blk_f, L.f));
+    F3DG_HIP_CHECK(compact_clear_padding(s, blk_v, L.v));
+    F3DG_KLAUNCH(mc_flag_kernel<I>, dim3(L.f.n_blocks), dim3(F3DG_BLOCK), 0, s, faces, F, N, face_component, keep_root, flags_f, flags_v, blk_f, hdr);
+    F3DG_KLAUNCH(mc_vcount_kernel, dim3((L.v.n_blocks + F3DG_BLOCK - 1) / F3DG_BLOCK), dim3(F3DG_BLOCK), 0, s, (const u64*)flags_v, L.v.n_words, blk_v,
+                 L.v.n_blocks);
+    F3DG_KLAUNCH(mc_scan_kernel, dim3(1), dim3(F3DG_BLOCK), 0, s, blk_f, L.f.n_scan, blk_v, L.v.n_scan, N, F, hdr);
     F3DG_HIP_CHECK(hipGetLastError());
     // the one host read: the two counts and whether an id was out of range
     McHeader h;
@@ -421,8 +392,8 @@ int compact_emit_impl(hipStream_t s, char* ws, const McLayout& L, u32 N, u32 F, 
     const u64* flags_v = reinterpret_cast<const u64*>(ws + L.flags_v);
     const u32* blk_f = reinterpret_cast<const u32*>(ws + L.blk_f);
     const u32* blk_v = reinterpret_cast<const u32*>(ws + L.blk_v);
-    F3DG_KLAUNCH(mc_emit_faces_kernel<I>, dim3(L.nb_f), dim3(F3DG_BLOCK), 0, s, faces, F, N, n_faces, flags_f, flags_v, blk_f, blk_v, hdr, faces_out);
-    F3DG_KLAUNCH(mc_emit_vertices_kernel, dim3(L.nb_v), dim3(F3DG_BLOCK), 0, s, N, F, n_vertices, flags_v, blk_v, hdr, vertex_ids);
+    F3DG_KLAUNCH(mc_emit_faces_kernel<I>, dim3(L.f.n_blocks), dim3(F3DG_BLOCK), 0, s, faces, F, N, n_faces, flags_f, flags_v, blk_f, blk_v, hdr, faces_out);
+    F3DG_KLAUNCH(mc_emit_vertices_kernel, dim3(L.v.n_blocks), dim3(F3DG_BLOCK), 0, s, N, F, n_vertices, flags_v, blk_v, hdr, vertex_ids);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }

@@ -12,19 +12,15 @@
 //                           the floor, of Z > z_near and of the two band tests wherever float32 rounding could flip them. One writer
 //                           per voxel, a fixed view order, no atomics: bit-reproducible. A voxel no view of the call sees is not
 //                           written at all.
-//   tsdf_classify_kernel    one thread per cell: eight corners, one bit per cell (a ballot per wave) and the workgroup's count
-//   tsdf_scan_kernel        one workgroup: scan_array_in_place (f3dg_scan.h) over the workgroup counts, total and `ready` into the header
-//   tsdf_emit_kernel        one thread per cell: its row from the scanned count, the bits of the earlier waves and lanes; six int4
+// The surface cells are compacted as f3dg_compact.h describes:
+//   tsdf_classify_kernel    one thread per cell: eight corners, then the cell's flag and the workgroup's count (block_flag_and_count)
+//   tsdf_scan_kernel        one workgroup: compact_scan_counts, total and `ready` into the header
+//   tsdf_emit_kernel        one thread per active cell at its compact_rank: six int4
 //   tsdf_vertices_kernel    one thread per crossing edge, float32, the operation order of the header
 #include "f3dg_common.h"
-#include "f3dg_scan.h"
+#include "f3dg_compact.h"
 
 namespace {
-
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
-#define TSDF_SCAN_ITEMS 16
 
 struct TsdfArgs {
     int nx, ny, nz, n_views, H, W;
@@ -114,10 +110,9 @@ struct TsdfCellsHeader {            // first 256 bytes of the workspace
 
 struct TsdfCellsLayout {
     size_t header, flags, blk, total;
-    u32 n_cells, n_blocks, n_words, n_scan;         // n_scan: n_blocks rounded up to whole TSDF_SCAN_ITEMS
+    u32 n_cells;
+    CompactPlan cells;
 };
-
-size_t tsdf_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // F3DG_OK, or why the volume is refused (`cells`: the cell entries need two voxels along every axis)
 int tsdf_check_dims(int nx, int ny, int nz, bool cells)
@@ -132,13 +127,11 @@ TsdfCellsLayout tsdf_cells_layout(int nx, int ny, int nz)
 {
     TsdfCellsLayout L;
     L.n_cells = (u32)(nx - 1) * (u32)(ny - 1) * (u32)(nz - 1);
-    L.n_blocks = (L.n_cells + F3DG_BLOCK - 1) / F3DG_BLOCK;
-    L.n_words = (L.n_cells + 63u) / 64u;
-    L.n_scan = (L.n_blocks + TSDF_SCAN_ITEMS - 1) / TSDF_SCAN_ITEMS * TSDF_SCAN_ITEMS;
+    L.cells = compact_plan(L.n_cells);
     L.header = 0;
-    L.flags = tsdf_align256(sizeof(TsdfCellsHeader));
-    L.blk = L.flags + tsdf_align256((size_t)L.n_words * 8);
-    L.total = L.blk + tsdf_align256((size_t)L.n_scan * 4);
+    L.flags = f3dg_align256(sizeof(TsdfCellsHeader));
+    L.blk = L.flags + L.cells.flag_bytes;
+    L.total = L.blk + L.cells.count_bytes;
     return L;
 }
 
@@ -170,21 +163,14 @@ tsdf_classify_kernel(u32 nx, u32 ny, u32 n_cells, float min_weight, const float*
         }
         active = ok && neg != 0u && neg != 8u;
     }
-    const u64 m = __ballot(active);
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0u) {
-        if (c < n_cells) flags[c >> 6] = m;
-        w_cnt[wave] = (u32)__popcll(m);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = w_cnt[0] + w_cnt[1] + w_cnt[2] + w_cnt[3];
+    block_flag_and_count(active, c, n_cells, flags, blk, w_cnt);
 }
 
 __global__ void __launch_bounds__(F3DG_BLOCK)
 tsdf_scan_kernel(u32* __restrict__ blk, u32 n_scan, u32 nx, u32 ny, u32 nz, TsdfCellsHeader* __restrict__ hdr)
 {
     __shared__ u64 wtot[F3DG_BLOCK / 64];
-    const u64 total = scan_array_in_place<F3DG_BLOCK / 64, TSDF_SCAN_ITEMS, u64>(blk, n_scan, 0u, wtot);
+    const u64 total = compact_scan_counts(blk, n_scan, wtot);
     if (threadIdx.x == 0) {
         hdr->n_active = total;
         hdr->nx = nx; hdr->ny = ny; hdr->nz = nz;
@@ -193,17 +179,13 @@ tsdf_scan_kernel(u32* __restrict__ blk, u32 n_scan, u32 nx, u32 ny, u32 nz, Tsdf
 }
 
 __global__ void __launch_bounds__(F3DG_BLOCK)
-tsdf_emit_kernel(u32 nx, u32 ny, u32 nz, u32 n_cells, u32 n_words, u64 n_rows, const u64* __restrict__ flags, const u32* __restrict__ blk,
+tsdf_emit_kernel(u32 nx, u32 ny, u32 nz, u32 n_cells, u64 n_rows, const u64* __restrict__ flags, const u32* __restrict__ blk,
                  const TsdfCellsHeader* __restrict__ hdr, int4* __restrict__ tets)
 {
     if (!hdr->ready || hdr->nx != nx || hdr->ny != ny || hdr->nz != nz) return;      // no completed count of this volume on the workspace
     const u32 c = blockIdx.x * F3DG_BLOCK + threadIdx.x;
-    if (c >= n_cells) return;
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, word = c >> 6;     // word = 4 blockIdx.x + wave < n_words
-    const u64 m = flags[word];
-    if (!((m >> lane) & 1ull)) return;
-    u64 row = (u64)blk[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
-    for (u32 w = 0; w < wave; w++) row += (u64)__popcll(flags[word - wave + w]);
+    if (c >= n_cells || !compact_kept(flags, c)) return;
+    const u64 row = compact_rank(flags, blk, c);
     if (row >= n_rows) return;                                                       // the caller's array ends here
     const int b = (int)tsdf_cell_base(c, nx, ny);
     const int X = 1, Y = (int)nx, Z = (int)(nx * ny), D = X + Y + Z;
@@ -312,10 +294,10 @@ extern "C" int f3dg_tsdf_cells_count(void* stream, int nx, int ny, int nz, float
     TsdfCellsHeader* hdr = (TsdfCellsHeader*)(ws + L.header);
     u32* blk = (u32*)(ws + L.blk);
     F3DG_HIP_CHECK(hipMemsetAsync(hdr, 0, sizeof(TsdfCellsHeader), s));
-    if (L.n_scan > L.n_blocks) F3DG_HIP_CHECK(hipMemsetAsync(blk + L.n_blocks, 0, (size_t)(L.n_scan - L.n_blocks) * 4, s));
-    F3DG_KLAUNCH(tsdf_classify_kernel, dim3(L.n_blocks), dim3(F3DG_BLOCK), 0, s, (u32)nx, (u32)ny, L.n_cells, min_weight, tsdf, weight,
+    F3DG_HIP_CHECK(compact_clear_padding(s, blk, L.cells));
+    F3DG_KLAUNCH(tsdf_classify_kernel, dim3(L.cells.n_blocks), dim3(F3DG_BLOCK), 0, s, (u32)nx, (u32)ny, L.n_cells, min_weight, tsdf, weight,
                  (u64*)(ws + L.flags), blk);
-    F3DG_KLAUNCH(tsdf_scan_kernel, dim3(1), dim3(F3DG_BLOCK), 0, s, blk, L.n_scan, (u32)nx, (u32)ny, (u32)nz, hdr);
+    F3DG_KLAUNCH(tsdf_scan_kernel, dim3(1), dim3(F3DG_BLOCK), 0, s, blk, L.cells.n_scan, (u32)nx, (u32)ny, (u32)nz, hdr);
     F3DG_HIP_CHECK(hipGetLastError());
     // the one host read: the number of active cells
     u64 n_active = 0;
@@ -334,8 +316,8 @@ extern "C" int f3dg_tsdf_cells_emit(void* stream, int nx, int ny, int nz, void* 
     const TsdfCellsLayout L = tsdf_cells_layout(nx, ny, nz);
     if (workspace_bytes < L.total) return F3DG_ERR_WORKSPACE;
     char* ws = (char*)workspace;
-    F3DG_KLAUNCH(tsdf_emit_kernel, dim3(L.n_blocks), dim3(F3DG_BLOCK), 0, (hipStream_t)stream, (u32)nx, (u32)ny, (u32)nz, L.n_cells, L.n_words,
-                 (u64)n_active, (const u64*)(ws + L.flags), (const u32*)(ws + L.blk), (const TsdfCellsHeader*)(ws + L.header), (int4*)tets);
+    F3DG_KLAUNCH(tsdf_emit_kernel, dim3(L.cells.n_blocks), dim3(F3DG_BLOCK), 0, (hipStream_t)stream, (u32)nx, (u32)ny, (u32)nz, L.n_cells, (u64)n_active,
+                 (const u64*)(ws + L.flags), (const u32*)(ws + L.blk), (const TsdfCellsHeader*)(ws + L.header), (int4*)tets);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }

@@ -3,7 +3,8 @@
 
 The larger inputs are the smallest at which every path of csrc/f3dg_mesh.hip runs: several workgroups of tetrahedra (17^3 Kuhn grid:
 96 of 256), buckets sorted by one thread (at most 32 entries), in LDS (33 .. 8192: the small fan, 1,080 entries in one bucket) and in
-place in global memory (the fan: 11,700 entries in one bucket), and the three bucket sizes around the first threshold (30, 32, 33)."""
+place in global memory (the fan: 11,700 entries in one bucket), the three bucket sizes around the first threshold (30, 32, 33), and
+a 58^3 Kuhn grid (4,341 workgroups of tetrahedra: the second round of the scan of the per-workgroup counts begins at workgroup 4,097)."""
 import numpy as np
 import pytest
 import torch
@@ -98,6 +99,32 @@ def test_library_equals_the_restatement(f3d, gpu_device, truth, name, dtype):
     assert len(iv) > 0 and len(fc) > 0
     assert iv.dtype == torch.int64 and torch.equal(iv.cpu(), torch.from_numpy(interp_v))
     assert fc.dtype == torch.int64 and torch.equal(fc.cpu(), torch.from_numpy(faces))
+
+
+@pytest.fixture(scope="module")
+def kuhn58():
+    """A 58^3 Kuhn grid: 1,111,158 tetrahedra in 4,341 workgroups, so a single-workgroup scan of the per-workgroup counts (4,096 per
+    round) takes a second round. The restatement is computed once for both index types."""
+    pts, tets = mesh_truth.kuhn_grid(58)
+    sdf, tets = mesh_truth.noisy_sphere_sdf(pts, 1), mesh_truth.permuted(tets, 3)
+    return (sdf, tets) + mesh_truth.marching_tets(sdf, tets)
+
+
+@pytest.mark.parametrize("dtype", (torch.int64, torch.int32))
+def test_tetrahedra_past_the_first_round_of_the_count_scan(f3d, gpu_device, kuhn58, dtype):
+    """One- and two-triangle tetrahedra at and beyond workgroup 4,096: their face rows come from the carry of the count scan."""
+    sdf, tets, interp_v, faces, stats = kuhn58
+    nt = mesh_truth.NUM_TRIANGLES[((sdf > 0)[tets] * np.array([1, 2, 4, 8])).sum(1)]
+    late = np.arange(len(tets)) // 256 >= 4096
+    print(f"kuhn58 ({dtype}): {len(tets)} tetrahedra, one-triangle {stats['n_one']} ({(late & (nt == 1)).sum()} late), "
+          f"two-triangle {stats['n_two']} ({(late & (nt == 2)).sum()} late), {len(interp_v)} edges, {len(faces)} faces")
+    assert len(tets) == 1_111_158 and (len(tets) + 255) // 256 == 4341
+    assert stats["n_one"] == 88_720 and stats["n_two"] == 35_820
+    assert (late & (nt == 1)).sum() == 4_975 and (late & (nt == 2)).sum() == 2_090
+    assert len(interp_v) == 79_694 and len(faces) == 160_360
+    iv, fc = f3d.mesh.marching_tets_topology(torch.from_numpy(sdf).to(gpu_device), torch.from_numpy(tets).to(gpu_device, dtype))
+    assert iv.dtype == torch.int64 and np.array_equal(iv.cpu().numpy(), interp_v)
+    assert fc.dtype == torch.int64 and np.array_equal(fc.cpu().numpy(), faces)
 
 
 def test_a_small_edge_capacity_is_grown(f3d, gpu_device, truth):

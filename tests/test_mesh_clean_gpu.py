@@ -5,7 +5,8 @@ anywhere. Every figure is printed before it is asserted (``pytest -s``).
 
 Shapes: one, two and three faces; 63 / 64 / 65 / 257 independent triangles (the wave and workgroup edges of the ballot aggregation and the
 scans); a 4,099-face strip (17 workgroups, one dependency chain across all of them) in three vertex orders; the strip among 1,000
-triangles (1,001 components, 20 workgroups); 48^3 and 32^3 volumes for the routes."""
+triangles (1,001 components, 20 workgroups); 1,048,833 independent triangles for the compaction alone (the smallest that enters the second
+round of its single-workgroup count scan, at workgroup 4,097); 48^3 and 32^3 volumes for the routes."""
 import ctypes as C
 
 import numpy as np
@@ -206,6 +207,51 @@ def test_emit_on_a_workspace_without_a_count_writes_nothing(gpu_device):
     want = M.clean(faces, N)
     assert np.array_equal(out[:F - 3].cpu().numpy(), want["faces"][:F - 3]) and bool((out[F - 3:] == SENT).all())
     assert np.array_equal(ids[:N - 2].cpu().numpy(), want["vertex_ids"][:N - 2]) and bool((ids[N - 2:] == SENT).all())
+
+
+def _second_round_case():
+    """4096 * 256 + 257 independent triangles: 4,098 workgroups of faces and 12,292 of vertices, so the single-workgroup scan of the
+    counts (4,096 per round) takes two rounds over the faces and four over the vertices. Computed once, shared, never modified."""
+    if "second round" not in _TRUTH:
+        n = 4096 * 256 + 257
+        faces, N = M.independent(n)
+        f = np.arange(n, dtype=np.int64)
+        kept = (f * 2654435761) % 7 < 3
+        kept[[0, 4096 * 256 - 1, 4096 * 256, n - 1]] = True               # the faces on either side of the round's edge, and both ends
+        labels = 3 * f                                                      # each triangle's least vertex id
+        keep_root = np.zeros(N, dtype=np.uint8)
+        keep_root[labels[kept]] = 1
+        faces_out, vertex_ids, kept_truth = M.compact(faces, N, labels, keep_root)
+        assert np.array_equal(kept_truth, kept)
+        _TRUTH["second round"] = (faces, N, labels.astype(np.int32), keep_root, faces_out, vertex_ids)
+    return _TRUTH["second round"]
+
+
+@pytest.mark.parametrize("dtype", [torch.int64, torch.int32])
+def test_compaction_past_the_first_round_of_the_count_scan(gpu_device, dtype):
+    """Kept faces and used vertices beyond workgroup 4,096 (element 1,048,577): the carry of the count scan, the length of its padding
+    and the word index of the rank are exercised only from there."""
+    dev = gpu_device
+    L = _lib.lib()
+    faces, N, labels, keep_root, faces_out, vertex_ids = _second_round_case()
+    F = len(faces)
+    assert F == 1_048_833 and N == 3_146_499 and (F + 255) // 256 > 4096 and (N + 255) // 256 == 12_292
+    ft = _dev(faces, dev, dtype)
+    fc, keep = torch.from_numpy(labels).to(dev), torch.from_numpy(keep_root).to(dev)
+    nbytes = L.f3dg_mesh_compact_workspace_bytes(N, F)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    hc = (C.c_longlong * 2)(-7, -7)
+    rc = L.f3dg_mesh_compact_count(_stream(), _lib.ptr(ws), nbytes, N, F, _lib.ptr(ft), int(dtype == torch.int32), _lib.ptr(fc), _lib.ptr(keep), hc)
+    print(f"second round ({dtype}): rc {rc}, kept {list(hc)} (truth {[len(faces_out), len(vertex_ids)]})")
+    assert rc == _lib.OK
+    assert list(hc) == [len(faces_out), len(vertex_ids)] == [449_502, 1_348_506]
+    out = torch.full((hc[0], 3), SENT, dtype=torch.int64, device=dev)
+    ids = torch.full((hc[1],), SENT, dtype=torch.int64, device=dev)
+    assert L.f3dg_mesh_compact_emit(_stream(), _lib.ptr(ws), nbytes, N, F, _lib.ptr(ft), int(dtype == torch.int32), _lib.ptr(fc), _lib.ptr(keep),
+                                    hc[0], hc[1], _lib.ptr(out), _lib.ptr(ids)) == _lib.OK
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy(), faces_out)
+    assert np.array_equal(ids.cpu().numpy(), vertex_ids)
 
 
 def test_bitwise_repeatable(gpu_device):

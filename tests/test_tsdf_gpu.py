@@ -6,7 +6,8 @@ printed before it is asserted (``pytest -s``).
 
 Shapes: the integration volume is 40 x 33 x 27 (no multiple of a wave or a workgroup along any axis, 140 workgroups) under five 48 x 40
 views; the chunking case 165 views (one past a full camera table and a ragged rest) of 8 x 8 pixels; the cell volumes 37 x 21 x 19
-(51 workgroups of cells, a sparse active set) and 2 x 2 x 2 (one cell); the sphere 48^3."""
+(51 workgroups of cells, a sparse active set), 2 x 2 x 2 (one cell) and 129 x 129 x 66 (4,160 workgroups of cells: the count scan's second
+round begins at workgroup 4,097; cells and tets only); the sphere 48^3."""
 import ctypes as C
 
 import numpy as np
@@ -246,6 +247,29 @@ def test_cells_edge_volumes(gpu_device):
     assert want["n_active"] == 1 and len(want["faces"]) > 0
     s["tsdf"][:] = -np.abs(s["tsdf"]) - 0.1
     assert _check_mesh(_volume((2, 2, 2), s, dev), s, 1.0, "2 x 2 x 2 all behind")[0]["n_active"] == 0
+
+
+def test_cells_past_the_first_round_of_the_count_scan(gpu_device):
+    """129 x 129 x 66: 1,064,960 cells in 4,160 workgroups, so the single-workgroup scan of the workgroup counts (4,096 per round)
+    takes a second round. Three blobs in free space, one of them in the last z layers: its cells get their rows from the carry."""
+    dims = (129, 129, 66)
+    nx, ny, nz = dims
+    s = T.empty_state(dims)
+    z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    t = np.full((nz, ny, nx), 0.5, np.float32)
+    for cx, cy, cz, r in ((20, 30, 3, 5.3), (100, 90, 62, 6.1), (64, 64, 33, 4.2)):
+        d = np.sqrt((x - cx) ** 2 + (y - cy) ** 2 + (z - cz) ** 2)
+        t = np.minimum(t, np.clip((d - r) / 4.0, -1, 1).astype(np.float32))
+    s["tsdf"] = t
+    s["weight"][:] = 2.0
+    n_active, want, active = T.cells_tets(s["tsdf"], s["weight"], 1.0)
+    groups = np.flatnonzero(active.reshape(-1)) // 256
+    print(f"129 x 129 x 66: {active.size} cells, {n_active} active in workgroups {groups.min()} .. {groups.max()}, {(groups >= 4096).sum()} at or beyond 4096")
+    assert active.size == 1_064_960 and n_active == 1300
+    assert groups.min() == 12 and groups.max() == 4143 and (groups >= 4096).sum() == 56
+    tets = _volume(dims, s, gpu_device).surface_tets()
+    assert tets.dtype == torch.int32 and tets.shape == (6 * n_active, 4)
+    assert np.array_equal(tets.cpu().numpy(), want)
 
 
 def test_emit_on_a_workspace_without_a_count_writes_nothing(gpu_device):
