@@ -16,7 +16,7 @@ _sys.modules.setdefault("diff_gof_rasterization", diff_gof_rasterization)
 from .diff_gof_rasterization import (GaussianRasterizationSettings_GOF, GaussianRasterizer_GOF,  # noqa: E402,F401
                                      rasterize_views, rasterize_views_autograd, set_deferred_status, deferred_status, flush)
 
-from . import gaussian_renderer, gaussian_predictor, unet_gs, cycle, dist, ply, mesh, losses, frames, warp, tsdf  # noqa: E402,F401
+from . import gaussian_renderer, gaussian_predictor, unet_gs, cycle, dist, ply, mesh, losses, frames, warp, tsdf, contribution  # noqa: E402,F401
 from .gaussian_renderer import (render_predicted_more_v2_gof, render_predicted_more_v3_gof,  # noqa: E402,F401
                                 render_predicted_more_v2_gof_in, AlphaSweep,
                                 render_views, depth_to_normal, depths_to_points)
@@ -26,6 +26,7 @@ from .mesh import marching_tetrahedra, tetra_points, bisect_level_set, extract_m
 from .tsdf import TSDFVolume  # noqa: E402,F401
 from .frames import compose_frames, compose_orbit_frames, depth_range, colormap_lut  # noqa: E402,F401
 from .warp import forward_warp, relative_transforms  # noqa: E402,F401
+from .contribution import GaussianContribution, contribution_raw, gaussian_contribution, prune_gaussians  # noqa: E402,F401
 
 
 

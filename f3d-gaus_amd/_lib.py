@@ -126,6 +126,12 @@ SIGNATURES = {
     "f3dg_mesh_compact_workspace_bytes": (_sz, [_ll, _ll]),
     "f3dg_mesh_compact_count": (_i, [_p, _p, _sz, _ll, _ll, _p, _i, _p, _p, C.POINTER(_ll)]),
     "f3dg_mesh_compact_emit": (_i, [_p, _p, _sz, _ll, _ll, _p, _i, _p, _p, _ll, _ll, _p, _p]),
+    # stream ws ws_bytes cap | n_views P W H tanx tany | stats final_T
+    "f3dg_contribution": (_i, [_p, _p, _sz, _ll, _i, _i, _i, _i, _f, _f, _p, _p]),
+    # P  /  stream ws ws_bytes P | stats keep min_touched min_max_weight min_sum_weight | h_kept  /  ... P n_kept | n_arrays srcs dsts row_floats (host) | kept_ids
+    "f3dg_gaussian_compact_workspace_bytes": (_sz, [_ll]),
+    "f3dg_gaussian_compact_count": (_i, [_p, _p, _sz, _ll, _p, _p, _ll, _f, C.c_double, C.POINTER(_ll)]),
+    "f3dg_gaussian_compact_emit": (_i, [_p, _p, _sz, _ll, _ll, _i, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i), _p]),
     "f3dg_set_option": (_i, [C.c_char_p, _i]),
     "f3dg_profile_enable": (_i, [_i]),
     "f3dg_debug_launch_count": (C.c_longlong, [_i]),

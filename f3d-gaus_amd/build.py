@@ -24,7 +24,7 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 # are pure overhead (measured on the compositing kernel: DESIGN.md section 5). Results are bit-identical either way.
 EXTRA_FLAGS = {name: os.environ.get("F3DG_EXTRA_" + name.split(".")[0].upper(), default).split()
                for name, default in (("f3dg_render.hip", "-fno-slp-vectorize"), ("f3dg_render4.hip", "-fno-slp-vectorize"), ("f3dg_render5.hip", "-fno-slp-vectorize"), ("f3dg_backward.hip", "-fno-slp-vectorize"), ("f3dg_backward5.hip", "-fno-slp-vectorize"),
-                                     ("f3dg_integrate.hip", "-fno-slp-vectorize"), ("f3dg_preprocess.hip", "-fno-slp-vectorize"))}
+                                     ("f3dg_integrate.hip", "-fno-slp-vectorize"), ("f3dg_preprocess.hip", "-fno-slp-vectorize"), ("f3dg_contribution.hip", "-fno-slp-vectorize"))}
 
 
 def sources():

@@ -400,7 +400,7 @@ extern "C" int f3dg_forward_sets(void* stream, void* workspace, size_t workspace
                       !g_f3dg_reference_kernels && !small_disabled((unsigned)P, (unsigned)n_views, (unsigned)W, (unsigned)H);
     // (the header is initialised by the first workgroup of the projection kernel; without Gaussians there is no such launch)
     const F3dgHeaderInit hinit = { hdr, (unsigned)max_rendered, (unsigned)fast, (unsigned)save_aux, (unsigned)small,
-                                   { (unsigned)P, (unsigned)n_views, (unsigned)W, (unsigned)H } };
+                                   { (unsigned)P, (unsigned)n_views, (unsigned)W, (unsigned)H }, (unsigned)n_sets };
     if (P == 0)
         F3DG_KLAUNCH(init_header_kernel, dim3(1), dim3(64), 0, s, hdr, (unsigned)max_rendered, (unsigned)fast, (unsigned)save_aux);
 

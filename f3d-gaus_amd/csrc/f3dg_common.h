@@ -52,7 +52,8 @@ struct F3dgHeader {
     unsigned int overflow;       // 1 if num_rendered > capacity
     unsigned int capacity;       // instance capacity the workspace was carved for
     unsigned int bwd_stale;      // 1: f3dg_backward ran on a workspace whose last forward was not a SAVE_AUX call of the general path
-    unsigned int reserved1[2];
+    unsigned int n_sets;         // Gaussian sets of the forward's call (0 or 1: one set). f3dg_contribution refuses more
+    unsigned int reserved1;
     unsigned int alpha_fast;      // arithmetic the compositing forward of this call used for alpha (1: error-free float32 pairs): the
                                   // backward must repeat it to the bit
     unsigned int save_aux;        // 1 when the forward of this workspace ran with F3DG_FLAG_SAVE_AUX (the auxiliary planes are valid)
@@ -176,7 +177,8 @@ struct F3dgViewConsts {           // passed by pointer: [V] of these are the cal
 struct F3dgHeaderInit {
     F3dgHeader* hdr;              // null: the header is initialised elsewhere
     unsigned capacity, alpha_fast, save_aux, small_path;
-    unsigned shape[4];            // P, n_views, W, H (recorded for the small-call path)
+    unsigned shape[4];            // P, n_views, W, H (recorded for the small-call path and for f3dg_contribution)
+    unsigned n_sets;
 };
 
 // ---- launchers (each returns F3DG_OK or a negative error) -------------------------------------------

@@ -223,7 +223,7 @@ preprocess_kernel(int P, int D, int M, int views_per_set,
         reinterpret_cast<unsigned*>(init.hdr)[threadIdx.x] = 0;
         if (threadIdx.x == 0) {
             init.hdr->capacity = init.capacity; init.hdr->alpha_fast = init.alpha_fast; init.hdr->save_aux = init.save_aux;
-            init.hdr->small_path = init.small_path;
+            init.hdr->small_path = init.small_path; init.hdr->n_sets = init.n_sets;
             init.hdr->small_shape[0] = init.shape[0]; init.hdr->small_shape[1] = init.shape[1];
             init.hdr->small_shape[2] = init.shape[2]; init.hdr->small_shape[3] = init.shape[3];
         }

@@ -53,6 +53,9 @@
  *       the TSDF mesh route (depth maps fused into a volume, its surface cells as tetrahedra for f3dg_marching_tets_*): the reference
  *       meshes through an external Delaunay tetrahedralisation (visualize.py:440-548) and holds no TSDF code: the semantics are this
  *       build's, defined below
+ *   f3dg_contribution / f3dg_gaussian_compact_count / f3dg_gaussian_compact_emit
+ *       per-Gaussian contribution statistics of rendered views and the pruning of a set by them: not in the reference, the
+ *       semantics are this build's, defined below
  *   f3dg_mesh_components / f3dg_mesh_compact_count / f3dg_mesh_compact_emit
  *       what follows either mesh route: connected components of the triangles and the removal of the small ones. The reference's
  *       script leaves that to trimesh on the host (update_vertices / update_faces, visualize.py:545-546) and labels no components:
@@ -804,6 +807,59 @@ int f3dg_mesh_compact_count(void* stream, void* workspace, size_t workspace_byte
 int f3dg_mesh_compact_emit(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, const void* faces,
                            int faces_int32, const int* face_component, const unsigned char* keep_root, long long n_faces_kept,
                            long long n_vertices_kept, long long* faces_out, long long* vertex_ids);
+
+/* ---- Which Gaussians matter: contribution statistics and the pruning of a set (f3dg_contribution.hip) -----------
+ *
+ * For the views of a call and a pair (pixel, entry g of the pixel's tile list), walked in list order from T = 1 exactly as the exact
+ * forward walks it, in the REFERENCE's arithmetic whatever the forward ran in:
+ *   skipped   the pixel is done, or t <= 0.2, or alpha < 1/255: the pair counts nowhere;
+ *   stopper   not skipped and T (1 - alpha) < 0.0001f: the pixel is done, stops[g] += 1. (The entry that ends a pixel's walk is not
+ *             blended, but without it the pixel would blend on: "never blended" is not "no effect".)
+ *   blended   any other pair: w = alpha T (the float32 number the exact forward adds to its alpha channel), blended[g] += 1,
+ *             max_weight[g] = max(., w), sum_weight[g] += w, T = T (1 - alpha).
+ * touched = blended + stops. A Gaussian with touched == 0 over a set of views can be removed without changing one bit of an exact
+ * render of those views (kept rows in input order: the depth sort is stable by id).
+ *
+ * The record, F3DG_CONTRIBUTION_BYTES = 32 per Gaussian, 32-byte aligned:
+ *   u64 sum_fixed  sum of round(w 2^32), half to even: exact and independent of the order of the pairs;  sum_weight = sum_fixed / 2^32
+ *   u64 counts     blended | stops << 32
+ *   u32 max_bits   the bits of max_weight (non-negative floats order as their bit patterns);  u32 pad[3]
+ * Integer adds and an unsigned maximum only: every byte is bit-reproducible, run to run, culled or unculled lists, general or
+ * small-call path, one call of n views or n calls of one.
+ * LIMIT: the views x W x H pixels of all the calls that add into one array must stay below 2^31 (each counter then fits 32 bits, the
+ * sum 63); f3dg_contribution refuses a call that alone reaches it, the caller watches the total.
+ *
+ * f3dg_contribution follows a forward (f3dg_forward_batched / f3dg_forward, any arithmetic, with or without F3DG_FLAG_SAVE_AUX, culled
+ * lists or not, either path) on the same workspace with the same max_rendered, n_views, P, W, H and fields of view: everything it
+ * reads -- the 64-byte records, the sorted lists, the tile ranges -- is still there. It ADDS into stats [P] and never clears it: the
+ * caller zero-fills once and accumulates over calls. final_T (may be NULL) [n_views, H, W] receives every pixel's T at the end of its
+ * walk -- plane 0 of the exact SAVE_AUX forward's final_T, to the bit. After a forward that overflowed max_rendered the lists are
+ * empty: nothing is added, final_T is 1. P == 0 adds nothing.
+ * BLOCKING: the workspace header (256 bytes) is read back first. F3DG_ERR_BAD_ARG: null workspace, a size out of range, stats null or off
+ * the 32-byte grid with P > 0, a workspace whose forward rendered several Gaussian sets (f3dg_forward_sets with n_sets > 1: not
+ * served); F3DG_ERR_WORKSPACE: workspace_bytes below f3dg_workspace_bytes of the shape; F3DG_ERR_STATE: the workspace's last forward had
+ * another shape or capacity. One launch.
+ *
+ * f3dg_gaussian_compact_count / _emit: stream compaction of a Gaussian set, as the mesh routes' (count -> one host read -> emit).
+ * Element i of P is kept when   blended + stops >= min_touched  and  max_weight >= min_max_weight  and  sum_weight >= min_sum_weight
+ * (stats, may be NULL: no thresholds; sum_weight is (double)sum_fixed / 2^32) and keep[i] != 0 (keep, [P] bytes, may be NULL). At least
+ * one of stats and keep must be given. min_touched >= 0; 0, 0.0f and 0.0 switch a threshold off; a NaN threshold is F3DG_ERR_BAD_ARG.
+ * BLOCKING: *h_kept = the number of kept elements (the one host read). P == 0 keeps nothing. P above 2^28 - 1 is F3DG_ERR_UNSUPPORTED.
+ * _emit: after a count that returned F3DG_OK with *h_kept > 0, same workspace and P; no host read. kept_ids [n_kept] int32: the kept
+ * ids ascending; array k of n_arrays <= F3DG_COMPACT_MAX_ARRAYS (host arrays srcs, dsts, row_floats): dsts[k] [n_kept, row_floats[k]]
+ * receives the kept rows of srcs[k] [P, row_floats[k]] (float32 rows; any 4-byte type gathers the same way) in input order. n_kept is
+ * the capacity of the outputs: rows beyond it are not written. F3DG_ERR_BAD_ARG: n_arrays > F3DG_COMPACT_MAX_ARRAYS, a row width <= 0,
+ * a null array, n_kept <= 0 or > P. On a workspace that holds no completed count of P elements nothing is written. */
+#define F3DG_CONTRIBUTION_BYTES 32
+#define F3DG_COMPACT_MAX_ARRAYS 8
+int f3dg_contribution(void* stream, const void* workspace, size_t workspace_bytes, long long max_rendered, int n_views, int P, int W,
+                      int H, float tan_fovx, float tan_fovy, void* stats, float* final_T);
+size_t f3dg_gaussian_compact_workspace_bytes(long long P);
+int f3dg_gaussian_compact_count(void* stream, void* workspace, size_t workspace_bytes, long long P, const void* stats,
+                                const unsigned char* keep, long long min_touched, float min_max_weight, double min_sum_weight,
+                                long long* h_kept);
+int f3dg_gaussian_compact_emit(void* stream, const void* workspace, size_t workspace_bytes, long long P, long long n_kept, int n_arrays,
+                               const void* const* srcs, void* const* dsts, const int* row_floats, int* kept_ids);
 
 /* Runtime switches: process-wide DEFAULTS for what a call's own flags do not say (every arithmetic / list / path choice of a call has a
  * flag, above). The library knows sixteen names and one diagnostic pair; everything else returns F3DG_ERR_BAD_ARG.
