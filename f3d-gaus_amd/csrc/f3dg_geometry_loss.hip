@@ -8,26 +8,19 @@
 // full-size cotangent maps. Here the two derived maps exist in registers only: N = normal_world and D = depth_normal of a pixel are
 // formed with the epilogue's own expressions (f3dg_epilogue.h), so the terms are those of the maps f3dg_render_epilogue_view writes.
 //
-// forward   a workgroup of 256 threads owns a 32 x 16 pixel tile of one frame, two pixels per thread (rows ty and ty + 8); its five
-//           sums go through a pairwise tree in LDS (fixed order) into the tile's own slot of `partials`; f3dg_frame_sums_kernel<5> adds
-//           one frame's slots in a fixed order. No float atomics, bit-reproducible, and no frame's sums see another frame's data.
+// forward   the two-stage, fixed-order sums of f3dg_tile_sums.h with TERMS = 5: a workgroup per 32 x 16 pixel tile of one frame, two
+//           pixels per thread.
 // backward  one thread per (frame, pixel), 256 consecutive pixels of a frame per workgroup, as epilogue_backward_kernel: channels 3..5
 //           from this pixel's own N, D and target; channel 6 as the gather over the up to four interior axial neighbours whose depth
 //           normal reads this pixel's depth, each neighbour's cotangent -W0 w(q) N(q) recomputed from the raster. Nothing is saved by
 //           the forward, no atomics, every element of dL_draster is assigned.
 #include "f3dg_common.h"
 #include "f3dg_epilogue.h"
-#include "f3dg_frame_sums.h"
+#include "f3dg_tile_sums.h"
 
-#define F3DG_GEOM_TW 32
-#define F3DG_GEOM_TH 16
-#define F3DG_GEOM_THREADS 256
-#define F3DG_GEOM_ROWS (F3DG_GEOM_THREADS / F3DG_GEOM_TW)      // rows of a tile the threads cover at once: 8
 #define F3DG_GEOM_TERMS 5
 
 namespace {
-
-struct GeomGrid { unsigned tiles_x, tiles_y; };
 
 // what both kernels read (by value)
 struct GeomArgs {
@@ -81,14 +74,14 @@ __device__ __forceinline__ void geom_depth_normal(const float* __restrict__ dep,
 
 __device__ __forceinline__ float geom_sign(float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); }
 
-__global__ void __launch_bounds__(F3DG_GEOM_THREADS)
-geom_fwd_kernel(GeomGrid grid, GeomArgs a, float* __restrict__ partials)
+__global__ void __launch_bounds__(F3DG_TILE_THREADS)
+geom_fwd_kernel(TileGrid grid, GeomArgs a, float* __restrict__ partials)
 {
     __shared__ float s_c2w[16];
-    __shared__ float s_red[F3DG_GEOM_TERMS * F3DG_GEOM_THREADS];
+    __shared__ float s_red[F3DG_GEOM_TERMS * F3DG_TILE_THREADS];
     const int tid = threadIdx.x;
-    const unsigned per_frame = grid.tiles_x * grid.tiles_y;
-    const unsigned f = blockIdx.x / per_frame, tile = blockIdx.x - f * per_frame;
+    const TileOfBlock t = tile_of_block(grid);
+    const unsigned f = t.frame;
     if (tid == 0) geom_camera(a.world_view, f, s_c2w);
     __syncthreads();
     const int H = a.H, W = a.W, HW = H * W;
@@ -96,12 +89,13 @@ geom_fwd_kernel(GeomGrid grid, GeomArgs a, float* __restrict__ partials)
     const float* dep = ras + 6 * HW;
     const float* Cw = s_c2w;
     const float ax = 1.0f / a.fx, bx = -(W / 2.0f) / a.fx, ay = 1.0f / a.fy, by = -(H / 2.0f) / a.fy;
-    const int x = (int)(tile % grid.tiles_x) * F3DG_GEOM_TW + tid % F3DG_GEOM_TW;
-    const int y0 = (int)(tile / grid.tiles_x) * F3DG_GEOM_TH + tid / F3DG_GEOM_TW;
+    int tx, ty;
+    tile_thread(tid, tx, ty);
+    const int x = t.x0 + tx, y0 = t.y0 + ty;
     float acc[F3DG_GEOM_TERMS] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
 #pragma unroll
-    for (int j = 0; j < F3DG_GEOM_TH / F3DG_GEOM_ROWS; j++) {
-        const int y = y0 + j * F3DG_GEOM_ROWS;
+    for (int j = 0; j < F3DG_TILE_H / F3DG_TILE_ROWS; j++) {
+        const int y = y0 + j * F3DG_TILE_ROWS;
         if (!(x < W && y < H)) continue;
         const int n = y * W + x;
         const size_t fn = (size_t)f * HW + n;
@@ -120,24 +114,9 @@ geom_fwd_kernel(GeomGrid grid, GeomArgs a, float* __restrict__ partials)
         }
         if (a.alpha_target) acc[4] = acc[4] + fabsf(alpha - a.alpha_target[fn]);
     }
-#pragma unroll
-    for (int q = 0; q < F3DG_GEOM_TERMS; q++) s_red[q * F3DG_GEOM_THREADS + tid] = acc[q];
-    for (int half = F3DG_GEOM_THREADS / 2; half >= 1; half >>= 1) {       // fixed-order pairwise sum of s_red[q][0 .. 2 * half)
-        __syncthreads();
-        if (tid < half) {
-#pragma unroll
-            for (int q = 0; q < F3DG_GEOM_TERMS; q++)
-                s_red[q * F3DG_GEOM_THREADS + tid] = s_red[q * F3DG_GEOM_THREADS + tid] + s_red[q * F3DG_GEOM_THREADS + tid + half];
-        }
-    }
-    if (tid == 0) {
-        float* out = partials + F3DG_GEOM_TERMS * (size_t)blockIdx.x;       // [frame][tile][5]
-#pragma unroll
-        for (int q = 0; q < F3DG_GEOM_TERMS; q++) out[q] = s_red[q * F3DG_GEOM_THREADS];
-    }
+    tile_sums_put(s_red, acc, tid);
+    tile_sums_reduce<F3DG_GEOM_TERMS>(s_red, tid, partials);
 }
-
-// Second stage: f3dg_frame_sums_kernel<5> (f3dg_frame_sums.h), one wave per frame over that frame's tile slots in a fixed order.
 
 // dL/draster for L = sum_f sum_k frame_weights[f,k] frame_sums[f,k]. A term whose weight is exactly 0 is not evaluated (its data
 // cannot reach the gradient, whatever it holds), as a term whose target is null.
@@ -145,9 +124,10 @@ __global__ void __launch_bounds__(F3DG_BLOCK)
 geom_bwd_kernel(unsigned blocks_per_frame, GeomArgs a, const float* __restrict__ frame_weights, float* __restrict__ dL_draster)
 {
     __shared__ float s_c2w[16];
-    const unsigned f = blockIdx.x / blocks_per_frame;
+    unsigned f;
+    int n;
+    frame_pixel_of_block(blocks_per_frame, f, n);
     const int H = a.H, W = a.W, HW = H * W;
-    const int n = (int)(blockIdx.x - f * blocks_per_frame) * F3DG_BLOCK + (int)threadIdx.x;
     if (threadIdx.x == 0) geom_camera(a.world_view, f, s_c2w);
     __syncthreads();
     if (n >= HW) return;
@@ -215,25 +195,11 @@ geom_bwd_kernel(unsigned blocks_per_frame, GeomArgs a, const float* __restrict__
     dpix[8 * HW + n] = W1;
 }
 
-// tiles of one frame and workgroups of the forward; false when the sizes are not positive, a frame does not fit the kernels' int
-// indices (channel * H * W + pixel, channel < 9) or the grid does not fit 31 bits
-bool geom_grid(int n_frames, int W, int H, GeomGrid& g, unsigned long long& blocks)
-{
-    if (n_frames <= 0 || W <= 0 || H <= 0 || 9ll * H * W > 0x7FFFFFF0ll) return false;
-    g.tiles_x = ((unsigned)W + F3DG_GEOM_TW - 1u) / F3DG_GEOM_TW;
-    g.tiles_y = ((unsigned)H + F3DG_GEOM_TH - 1u) / F3DG_GEOM_TH;
-    blocks = (unsigned long long)g.tiles_x * g.tiles_y * (unsigned long long)n_frames;
-    return blocks <= 0x7FFFFFFFull;
-}
-
 } // namespace
 
 extern "C" size_t f3dg_geometry_loss_partials_bytes(int n_frames, int W, int H)
 {
-    GeomGrid g;
-    unsigned long long blocks;
-    if (!geom_grid(n_frames, W, H, g, blocks)) return 0;
-    return (size_t)blocks * F3DG_GEOM_TERMS * sizeof(float);
+    return tile_partials_bytes<F3DG_GEOM_TERMS>(n_frames, W, H, 9ll * H * W);
 }
 
 extern "C" int f3dg_geometry_loss_forward(void* stream, int n_frames, int H, int W, const float* raster, const float* world_view,
@@ -243,17 +209,14 @@ extern "C" int f3dg_geometry_loss_forward(void* stream, int n_frames, int H, int
 {
     if (n_frames <= 0 || H <= 0 || W <= 0 || !raster || !world_view || !frame_sums || !partials) return F3DG_ERR_BAD_ARG;
     if (flags & ~F3DG_GEOM_ALPHA_WEIGHT) return F3DG_ERR_BAD_ARG;
-    GeomGrid g;
-    unsigned long long blocks;
-    if (!geom_grid(n_frames, W, H, g, blocks)) return F3DG_ERR_UNSUPPORTED;
-    if (partials_bytes < (size_t)blocks * F3DG_GEOM_TERMS * sizeof(float)) return F3DG_ERR_WORKSPACE;
+    TileGrid g;
+    unsigned blocks;
+    if (!tile_grid(n_frames, W, H, 9ll * H * W, g, blocks)) return F3DG_ERR_UNSUPPORTED;
+    if (partials_bytes < tile_partials_bytes<F3DG_GEOM_TERMS>(blocks)) return F3DG_ERR_WORKSPACE;
     const GeomArgs a = { H, W, raster, world_view, fx, fy, flags, depth_target, normal_target, alpha_target, mask };
-    F3DG_KLAUNCH(geom_fwd_kernel, dim3((unsigned)blocks), dim3(F3DG_GEOM_THREADS), 0, (hipStream_t)stream, g, a, partials);
+    F3DG_KLAUNCH(geom_fwd_kernel, dim3(blocks), dim3(F3DG_TILE_THREADS), 0, (hipStream_t)stream, g, a, partials);
     F3DG_HIP_CHECK(hipGetLastError());
-    F3DG_KLAUNCH(f3dg_frame_sums_kernel<F3DG_GEOM_TERMS>, dim3((unsigned)n_frames), dim3(64), 0, (hipStream_t)stream, g.tiles_x * g.tiles_y, partials,
-                 frame_sums);
-    F3DG_HIP_CHECK(hipGetLastError());
-    return F3DG_OK;
+    return tile_frame_sums<F3DG_GEOM_TERMS>((hipStream_t)stream, n_frames, g, partials, frame_sums);
 }
 
 extern "C" int f3dg_geometry_loss_backward(void* stream, int n_frames, int H, int W, const float* raster, const float* world_view,
@@ -262,14 +225,13 @@ extern "C" int f3dg_geometry_loss_backward(void* stream, int n_frames, int H, in
 {
     if (n_frames <= 0 || H <= 0 || W <= 0 || !raster || !world_view || !frame_weights || !dL_draster) return F3DG_ERR_BAD_ARG;
     if (flags & ~F3DG_GEOM_ALPHA_WEIGHT) return F3DG_ERR_BAD_ARG;
-    GeomGrid g;
-    unsigned long long blocks;
-    if (!geom_grid(n_frames, W, H, g, blocks)) return F3DG_ERR_UNSUPPORTED;
-    const unsigned long long per_frame = ((unsigned long long)H * W + F3DG_BLOCK - 1) / F3DG_BLOCK;
-    if (per_frame * (unsigned long long)n_frames > 0x7FFFFFFFull) return F3DG_ERR_UNSUPPORTED;
+    TileGrid g;
+    unsigned blocks;
+    if (!tile_grid(n_frames, W, H, 9ll * H * W, g, blocks)) return F3DG_ERR_UNSUPPORTED;
+    unsigned per_frame;
+    if (!frame_pixel_grid(n_frames, H, W, per_frame, blocks)) return F3DG_ERR_UNSUPPORTED;
     const GeomArgs a = { H, W, raster, world_view, fx, fy, flags, depth_target, normal_target, alpha_target, mask };
-    F3DG_KLAUNCH(geom_bwd_kernel, dim3((unsigned)(per_frame * n_frames)), dim3(F3DG_BLOCK), 0, (hipStream_t)stream, (unsigned)per_frame, a,
-                 frame_weights, dL_draster);
+    F3DG_KLAUNCH(geom_bwd_kernel, dim3(blocks), dim3(F3DG_BLOCK), 0, (hipStream_t)stream, per_frame, a, frame_weights, dL_draster);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }

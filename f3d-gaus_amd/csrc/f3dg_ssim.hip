@@ -13,91 +13,52 @@
 // one tile row (the tile is exactly one lane group wide), so no access has a bank conflict whatever the row stride is: the vertical
 // pass needs no padding. LDS per workgroup: forward 28,448 B (5 workgroups = 20 waves per CU), backward 23,088 B (7 = 28 waves).
 //
-// Sums: every tile writes its three partial sums to its own slot of a caller-provided buffer (pairwise tree in LDS, fixed order), and
-// ssim_plane_sums_kernel adds the slots of ONE plane in a fixed order: no float atomics, bit-reproducible, and no plane's sums ever see
-// another plane's data.
+// Sums: the two-stage, fixed-order scheme of f3dg_tile_sums.h with TERMS = 3 (m, |a - b|, (a - b)^2) and a plane as its frame.
 #include "f3dg_common.h"
 #include "f3dg_ssim_tile.h"
+#include "f3dg_tile_sums.h"
 
 namespace {
 
-struct SsimGrid { unsigned tiles_x, tiles_y; };
-
-__device__ __forceinline__ SsimTile ssim_tile_of_block(unsigned block, SsimGrid grid, int W, int H, unsigned& plane, unsigned& tile)
+__device__ __forceinline__ SsimTile ssim_tile(const TileOfBlock& b, int W, int H)
 {
-    const unsigned per_plane = grid.tiles_x * grid.tiles_y;
-    plane = block / per_plane;
-    tile = block - plane * per_plane;
     SsimTile t;
     t.W = W; t.H = H;
-    t.y0 = (int)(tile / grid.tiles_x) * F3DG_SSIM_TH;
-    t.x0 = (int)(tile % grid.tiles_x) * F3DG_SSIM_TW;
-    t.plane_off = (size_t)plane * (size_t)H * (size_t)W;
+    t.y0 = b.y0;
+    t.x0 = b.x0;
+    t.plane_off = (size_t)b.frame * (size_t)H * (size_t)W;
     return t;
 }
 
-__global__ void __launch_bounds__(F3DG_SSIM_THREADS)
-ssim_fwd_kernel(SsimGrid grid, int W, int H, const float* __restrict__ img1, const float* __restrict__ img2, float* __restrict__ map,
+__global__ void __launch_bounds__(F3DG_TILE_THREADS)
+ssim_fwd_kernel(TileGrid grid, int W, int H, const float* __restrict__ img1, const float* __restrict__ img2, float* __restrict__ map,
                 float* __restrict__ dm_dmu1, float* __restrict__ dm_dsigma1_sq, float* __restrict__ dm_dsigma12, float* __restrict__ partials)
 {
     __shared__ float s_a[F3DG_SSIM_STAGE], s_b[F3DG_SSIM_STAGE];
     __shared__ float s_h[5 * F3DG_SSIM_HROWS];
-    __shared__ float s_red[3 * F3DG_SSIM_THREADS];
+    __shared__ float s_red[3 * F3DG_TILE_THREADS];
     const int tid = threadIdx.x;
-    unsigned plane, tile;
-    const SsimTile t = ssim_tile_of_block(blockIdx.x, grid, W, H, plane, tile);
+    const SsimTile t = ssim_tile(tile_of_block(grid), W, H);
     ssim_fwd_stage(t, img1, img2, s_a, s_b, tid);
     __syncthreads();
     ssim_fwd_hpass(s_a, s_b, s_h, tid);
     __syncthreads();
     ssim_fwd_vpass(t, s_a, s_b, s_h, map, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, s_red, tid);
     if (!partials) return;                      // (uniform: a kernel argument)
-    for (int half = F3DG_SSIM_THREADS / 2; half >= 1; half >>= 1) {
-        __syncthreads();
-        ssim_reduce_level(s_red, half, tid);
-    }
-    if (tid == 0) {
-        float* out = partials + 3 * (size_t)blockIdx.x;        // [plane][tile][3]
-        out[0] = s_red[0];
-        out[1] = s_red[F3DG_SSIM_THREADS];
-        out[2] = s_red[2 * F3DG_SSIM_THREADS];
-    }
+    tile_sums_reduce<3>(s_red, tid, partials);
 }
 
-// Second stage: one wave per plane adds that plane's tile slots -- lane l takes tiles l, l + 64, ... in ascending order, then a
-// pairwise tree over the 64 lanes in LDS. plane_sums [n_planes][3] = sum of m, of |a - b|, of (a - b)^2.
-__global__ void __launch_bounds__(64)
-ssim_plane_sums_kernel(unsigned tiles_per_plane, const float* __restrict__ partials, float* __restrict__ plane_sums)
-{
-    __shared__ float s[3 * 64];
-    const unsigned lane = threadIdx.x, plane = blockIdx.x;
-    const float* p = partials + 3 * (size_t)plane * tiles_per_plane;
-    float acc[3] = { 0.0f, 0.0f, 0.0f };
-    for (unsigned i = lane; i < tiles_per_plane; i += 64u) {
-        acc[0] = acc[0] + p[3 * (size_t)i];
-        acc[1] = acc[1] + p[3 * (size_t)i + 1];
-        acc[2] = acc[2] + p[3 * (size_t)i + 2];
-    }
-    for (int q = 0; q < 3; q++) s[q * 64 + lane] = acc[q];
-    for (unsigned half = 32u; half >= 1u; half >>= 1) {
-        __syncthreads();
-        if (lane < half)
-            for (int q = 0; q < 3; q++) s[q * 64 + lane] = s[q * 64 + lane] + s[q * 64 + lane + half];
-    }
-    if (lane == 0)
-        for (int q = 0; q < 3; q++) plane_sums[3 * (size_t)plane + q] = s[q * 64];
-}
-
-__global__ void __launch_bounds__(F3DG_SSIM_THREADS)
-ssim_bwd_kernel(SsimGrid grid, int W, int H, const float* __restrict__ img1, const float* __restrict__ img2,
+__global__ void __launch_bounds__(F3DG_TILE_THREADS)
+ssim_bwd_kernel(TileGrid grid, int W, int H, const float* __restrict__ img1, const float* __restrict__ img2,
                 const float* __restrict__ dL_dmap, const float* __restrict__ plane_weights, const float* __restrict__ dm_dmu1,
                 const float* __restrict__ dm_dsigma1_sq, const float* __restrict__ dm_dsigma12, float* __restrict__ dL_dimg1)
 {
     __shared__ float s_x[3 * F3DG_SSIM_STAGE];
     __shared__ float s_h[3 * F3DG_SSIM_HROWS];
     const int tid = threadIdx.x;
-    unsigned plane, tile;
-    const SsimTile t = ssim_tile_of_block(blockIdx.x, grid, W, H, plane, tile);
+    const TileOfBlock b = tile_of_block(grid);
+    const unsigned plane = b.frame;
+    const SsimTile t = ssim_tile(b, W, H);
     float w_ssim = 0.0f, w_l1 = 0.0f, w_l2 = 0.0f;
     if (plane_weights) {
         w_ssim = plane_weights[3 * (size_t)plane];
@@ -111,24 +72,11 @@ ssim_bwd_kernel(SsimGrid grid, int W, int H, const float* __restrict__ img1, con
     ssim_bwd_vpass(t, s_h, img1, img2, w_l1, w_l2, dL_dimg1, tid);
 }
 
-// tiles of one plane and workgroups of the call; false when the sizes are not positive or the grid does not fit 31 bits
-bool ssim_grid(int n_planes, int W, int H, SsimGrid& g, unsigned long long& blocks)
-{
-    if (n_planes <= 0 || W <= 0 || H <= 0) return false;
-    g.tiles_x = ((unsigned)W + F3DG_SSIM_TW - 1u) / F3DG_SSIM_TW;
-    g.tiles_y = ((unsigned)H + F3DG_SSIM_TH - 1u) / F3DG_SSIM_TH;
-    blocks = (unsigned long long)g.tiles_x * g.tiles_y * (unsigned long long)n_planes;
-    return blocks <= 0x7FFFFFFFull;
-}
-
 } // namespace
 
 extern "C" size_t f3dg_ssim_partials_bytes(int n_planes, int W, int H)
 {
-    SsimGrid g;
-    unsigned long long blocks;
-    if (!ssim_grid(n_planes, W, H, g, blocks)) return 0;
-    return (size_t)blocks * 3 * sizeof(float);
+    return tile_partials_bytes<3>(n_planes, W, H, 0);
 }
 
 extern "C" int f3dg_ssim_forward(void* stream, int n_planes, int W, int H, const float* img1, const float* img2, float* map,
@@ -137,20 +85,15 @@ extern "C" int f3dg_ssim_forward(void* stream, int n_planes, int W, int H, const
 {
     if (n_planes <= 0 || W <= 0 || H <= 0 || !img1 || !img2) return F3DG_ERR_BAD_ARG;
     if (plane_sums && !partials) return F3DG_ERR_BAD_ARG;
-    SsimGrid g;
-    unsigned long long blocks;
-    if (!ssim_grid(n_planes, W, H, g, blocks)) return F3DG_ERR_UNSUPPORTED;
-    if (partials && partials_bytes < (size_t)blocks * 3 * sizeof(float)) return F3DG_ERR_WORKSPACE;
+    TileGrid g;
+    unsigned blocks;
+    if (!tile_grid(n_planes, W, H, 0, g, blocks)) return F3DG_ERR_UNSUPPORTED;
+    if (partials && partials_bytes < tile_partials_bytes<3>(blocks)) return F3DG_ERR_WORKSPACE;
     if (!map && !dm_dmu1 && !dm_dsigma1_sq && !dm_dsigma12 && !partials) return F3DG_OK;
-    F3DG_KLAUNCH(ssim_fwd_kernel, dim3((unsigned)blocks), dim3(F3DG_SSIM_THREADS), 0, (hipStream_t)stream, g, W, H, img1, img2, map,
+    F3DG_KLAUNCH(ssim_fwd_kernel, dim3(blocks), dim3(F3DG_TILE_THREADS), 0, (hipStream_t)stream, g, W, H, img1, img2, map,
                  dm_dmu1, dm_dsigma1_sq, dm_dsigma12, partials);
     F3DG_HIP_CHECK(hipGetLastError());
-    if (plane_sums) {
-        F3DG_KLAUNCH(ssim_plane_sums_kernel, dim3((unsigned)n_planes), dim3(64), 0, (hipStream_t)stream, g.tiles_x * g.tiles_y, partials,
-                     plane_sums);
-        F3DG_HIP_CHECK(hipGetLastError());
-    }
-    return F3DG_OK;
+    return plane_sums ? tile_frame_sums<3>((hipStream_t)stream, n_planes, g, partials, plane_sums) : F3DG_OK;
 }
 
 extern "C" int f3dg_ssim_backward(void* stream, int n_planes, int W, int H, const float* img1, const float* img2, const float* dL_dmap,
@@ -160,10 +103,10 @@ extern "C" int f3dg_ssim_backward(void* stream, int n_planes, int W, int H, cons
     if (n_planes <= 0 || W <= 0 || H <= 0 || !img1 || !img2 || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_dimg1)
         return F3DG_ERR_BAD_ARG;
     if (!dL_dmap && !plane_weights) return F3DG_ERR_BAD_ARG;
-    SsimGrid g;
-    unsigned long long blocks;
-    if (!ssim_grid(n_planes, W, H, g, blocks)) return F3DG_ERR_UNSUPPORTED;
-    F3DG_KLAUNCH(ssim_bwd_kernel, dim3((unsigned)blocks), dim3(F3DG_SSIM_THREADS), 0, (hipStream_t)stream, g, W, H, img1, img2, dL_dmap,
+    TileGrid g;
+    unsigned blocks;
+    if (!tile_grid(n_planes, W, H, 0, g, blocks)) return F3DG_ERR_UNSUPPORTED;
+    F3DG_KLAUNCH(ssim_bwd_kernel, dim3(blocks), dim3(F3DG_TILE_THREADS), 0, (hipStream_t)stream, g, W, H, img1, img2, dL_dmap,
                  plane_weights, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, dL_dimg1);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;

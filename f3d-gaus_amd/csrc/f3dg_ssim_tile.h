@@ -7,15 +7,13 @@
 // separably to the image zero-padded by 5; m = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)), utils/loss_utils.py:43-58.
 // Compiled with -ffp-contract=off like the rest of the library: every product and sum below is one float32 rounding.
 #pragma once
+#include "f3dg_tile_sums.h"                          // the tile: 32 wide (one LDS lane group per tile row), 16 high, 256 threads
 
-#define F3DG_SSIM_TW 32                              // tile width: one 32-lane LDS lane group per tile row
-#define F3DG_SSIM_TH 16                              // tile height: two pixels per thread in the vertical pass
 #define F3DG_SSIM_R 5                                // window radius
-#define F3DG_SSIM_SW (F3DG_SSIM_TW + 2 * F3DG_SSIM_R)    // 42 staged columns
-#define F3DG_SSIM_SH (F3DG_SSIM_TH + 2 * F3DG_SSIM_R)    // 26 staged rows
-#define F3DG_SSIM_THREADS 256
+#define F3DG_SSIM_SW (F3DG_TILE_W + 2 * F3DG_SSIM_R)    // 42 staged columns
+#define F3DG_SSIM_SH (F3DG_TILE_H + 2 * F3DG_SSIM_R)    // 26 staged rows
 #define F3DG_SSIM_STAGE (F3DG_SSIM_SH * F3DG_SSIM_SW)    // 1,092 floats per staged plane
-#define F3DG_SSIM_HROWS (F3DG_SSIM_SH * F3DG_SSIM_TW)    // 832 floats per horizontally blurred plane
+#define F3DG_SSIM_HROWS (F3DG_SSIM_SH * F3DG_TILE_W)    // 832 floats per horizontally blurred plane
 
 // The reference's taps: float32(exp(-(i - 5)^2 / 4.5)) over their float32 sum (torch.Tensor(...) / .sum()), i = 0..10.
 #define F3DG_SSIM_TAPS { 0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c3ep-3f, 0x1.10656p-2f, \
@@ -34,7 +32,7 @@ struct SsimTile {
 __device__ __forceinline__ void ssim_fwd_stage(const SsimTile& t, const float* __restrict__ img1, const float* __restrict__ img2,
                                                float* s_a, float* s_b, int tid)
 {
-    for (int i = tid; i < F3DG_SSIM_STAGE; i += F3DG_SSIM_THREADS) {
+    for (int i = tid; i < F3DG_SSIM_STAGE; i += F3DG_TILE_THREADS) {
         const int r = i / F3DG_SSIM_SW, c = i - r * F3DG_SSIM_SW;
         const int y = t.y0 - F3DG_SSIM_R + r, x = t.x0 - F3DG_SSIM_R + c;
         float a = 0.0f, b = 0.0f;
@@ -52,8 +50,8 @@ __device__ __forceinline__ void ssim_fwd_stage(const SsimTile& t, const float* _
 __device__ __forceinline__ void ssim_fwd_hpass(const float* s_a, const float* s_b, float* s_h, int tid)
 {
     const float g[11] = F3DG_SSIM_TAPS;
-    for (int i = tid; i < F3DG_SSIM_HROWS; i += F3DG_SSIM_THREADS) {
-        const int r = i / F3DG_SSIM_TW, c = i - r * F3DG_SSIM_TW;
+    for (int i = tid; i < F3DG_SSIM_HROWS; i += F3DG_TILE_THREADS) {
+        const int r = i / F3DG_TILE_W, c = i - r * F3DG_TILE_W;
         const float* pa = s_a + r * F3DG_SSIM_SW + c;
         const float* pb = s_b + r * F3DG_SSIM_SW + c;
         float m1 = 0.0f, m2 = 0.0f, e11 = 0.0f, e22 = 0.0f, e12 = 0.0f;
@@ -99,18 +97,19 @@ __device__ __forceinline__ void ssim_fwd_vpass(const SsimTile& t, const float* s
                                                float* __restrict__ dm_dsigma12, float* red, int tid)
 {
     const float g[11] = F3DG_SSIM_TAPS;
-    const int tx = tid % F3DG_SSIM_TW;
+    int tx, ty0;
+    tile_thread(tid, tx, ty0);
     float sum_m = 0.0f, sum_l1 = 0.0f, sum_l2 = 0.0f;
 #pragma unroll
-    for (int j = 0; j < F3DG_SSIM_TH / (F3DG_SSIM_THREADS / F3DG_SSIM_TW); j++) {
-        const int ty = tid / F3DG_SSIM_TW + j * (F3DG_SSIM_THREADS / F3DG_SSIM_TW);
+    for (int j = 0; j < F3DG_TILE_H / F3DG_TILE_ROWS; j++) {
+        const int ty = ty0 + j * F3DG_TILE_ROWS;
         float v[5];
 #pragma unroll
         for (int q = 0; q < 5; q++) {
-            const float* p = s_h + q * F3DG_SSIM_HROWS + ty * F3DG_SSIM_TW + tx;
+            const float* p = s_h + q * F3DG_SSIM_HROWS + ty * F3DG_TILE_W + tx;
             float acc = 0.0f;
 #pragma unroll
-            for (int k = 0; k < 11; k++) acc = acc + g[k] * p[k * F3DG_SSIM_TW];
+            for (int k = 0; k < 11; k++) acc = acc + g[k] * p[k * F3DG_TILE_W];
             v[q] = acc;
         }
         const int x = t.x0 + tx, y = t.y0 + ty;
@@ -128,20 +127,9 @@ __device__ __forceinline__ void ssim_fwd_vpass(const SsimTile& t, const float* s
             sum_l2 = sum_l2 + d * d;
         }
     }
-    red[0 * F3DG_SSIM_THREADS + tid] = sum_m;
-    red[1 * F3DG_SSIM_THREADS + tid] = sum_l1;
-    red[2 * F3DG_SSIM_THREADS + tid] = sum_l2;
-}
-
-// One level of the fixed-order pairwise sum of red[q][0 .. 2 * half): the kernel runs it for half = 128, 64, ... 1 with a barrier
-// in front of each level, so the tile sums are the same bits in every run.
-__device__ __forceinline__ void ssim_reduce_level(float* red, int half, int tid)
-{
-    if (tid < half) {
-#pragma unroll
-        for (int q = 0; q < 3; q++)
-            red[q * F3DG_SSIM_THREADS + tid] = red[q * F3DG_SSIM_THREADS + tid] + red[q * F3DG_SSIM_THREADS + tid + half];
-    }
+    red[0 * F3DG_TILE_THREADS + tid] = sum_m;
+    red[1 * F3DG_TILE_THREADS + tid] = sum_l1;
+    red[2 * F3DG_TILE_THREADS + tid] = sum_l2;
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -152,7 +140,7 @@ __device__ __forceinline__ void ssim_bwd_stage(const SsimTile& t, const float* _
                                                const float* __restrict__ dm_dmu1, const float* __restrict__ dm_dsigma1_sq,
                                                const float* __restrict__ dm_dsigma12, float* s_x, int tid)
 {
-    for (int i = tid; i < F3DG_SSIM_STAGE; i += F3DG_SSIM_THREADS) {
+    for (int i = tid; i < F3DG_SSIM_STAGE; i += F3DG_TILE_THREADS) {
         const int r = i / F3DG_SSIM_SW, c = i - r * F3DG_SSIM_SW;
         const int y = t.y0 - F3DG_SSIM_R + r, x = t.x0 - F3DG_SSIM_R + c;
         float x1 = 0.0f, x2 = 0.0f, x3 = 0.0f;
@@ -173,8 +161,8 @@ __device__ __forceinline__ void ssim_bwd_stage(const SsimTile& t, const float* _
 __device__ __forceinline__ void ssim_bwd_hpass(const float* s_x, float* s_h, int tid)
 {
     const float g[11] = F3DG_SSIM_TAPS;
-    for (int i = tid; i < F3DG_SSIM_HROWS; i += F3DG_SSIM_THREADS) {
-        const int r = i / F3DG_SSIM_TW, c = i - r * F3DG_SSIM_TW;
+    for (int i = tid; i < F3DG_SSIM_HROWS; i += F3DG_TILE_THREADS) {
+        const int r = i / F3DG_TILE_W, c = i - r * F3DG_TILE_W;
 #pragma unroll
         for (int q = 0; q < 3; q++) {
             const float* p = s_x + q * F3DG_SSIM_STAGE + r * F3DG_SSIM_SW + c;
@@ -192,19 +180,20 @@ __device__ __forceinline__ void ssim_bwd_vpass(const SsimTile& t, const float* s
                                                const float* __restrict__ img2, float w_l1, float w_l2, float* __restrict__ dL_dimg1, int tid)
 {
     const float g[11] = F3DG_SSIM_TAPS;
-    const int tx = tid % F3DG_SSIM_TW;
+    int tx, ty0;
+    tile_thread(tid, tx, ty0);
 #pragma unroll
-    for (int j = 0; j < F3DG_SSIM_TH / (F3DG_SSIM_THREADS / F3DG_SSIM_TW); j++) {
-        const int ty = tid / F3DG_SSIM_TW + j * (F3DG_SSIM_THREADS / F3DG_SSIM_TW);
+    for (int j = 0; j < F3DG_TILE_H / F3DG_TILE_ROWS; j++) {
+        const int ty = ty0 + j * F3DG_TILE_ROWS;
         const int x = t.x0 + tx, y = t.y0 + ty;
         if (!(x < t.W && y < t.H)) continue;
         float v[3];
 #pragma unroll
         for (int q = 0; q < 3; q++) {
-            const float* p = s_h + q * F3DG_SSIM_HROWS + ty * F3DG_SSIM_TW + tx;
+            const float* p = s_h + q * F3DG_SSIM_HROWS + ty * F3DG_TILE_W + tx;
             float acc = 0.0f;
 #pragma unroll
-            for (int k = 0; k < 11; k++) acc = acc + g[k] * p[k * F3DG_SSIM_TW];
+            for (int k = 0; k < 11; k++) acc = acc + g[k] * p[k * F3DG_TILE_W];
             v[q] = acc;
         }
         const size_t idx = t.plane_off + (size_t)y * t.W + x;

@@ -27,10 +27,10 @@
 // depth up to 32768 are exact to q / 2 per contribution; beyond, a contribution saturates). A target pixel receives at most H W
 // contributions (one per source pixel), so with H W <= 2^23 (F3DG_ERR_UNSUPPORTED beyond) a sum stays below 2^15 2^24 2^23 = 2^62.
 //
-// masked L1      masked_l1_fwd_kernel (a 32 x 16 tile per workgroup, fixed-order LDS tree, the tile's own slot of `partials`) +
-//                f3dg_frame_sums_kernel<2>; masked_l1_bwd_kernel assigns g m sign(a - b) -- the mould of f3dg_geometry_loss.hip.
+// masked L1      masked_l1_fwd_kernel, the two-stage, fixed-order sums of f3dg_tile_sums.h with TERMS = 2; masked_l1_bwd_kernel assigns
+//                g m sign(a - b) -- the mould of f3dg_geometry_loss.hip.
 #include "f3dg_common.h"
-#include "f3dg_frame_sums.h"
+#include "f3dg_tile_sums.h"
 
 #define F3DG_WARP_Q_INV 16777216.0        // 1 / q, q = 2^-24
 #define F3DG_WARP_Q (1.0 / F3DG_WARP_Q_INV)
@@ -38,10 +38,6 @@
 #define F3DG_WARP_MAX_PIXELS (1ll << 23)
 #define F3DG_WARP_MAX_C 16
 #define F3DG_WARP_MAX_ERODE 15
-#define F3DG_ML1_TW 32
-#define F3DG_ML1_TH 16
-#define F3DG_ML1_THREADS 256
-#define F3DG_ML1_ROWS (F3DG_ML1_THREADS / F3DG_ML1_TW)
 
 namespace {
 
@@ -236,52 +232,41 @@ bool warp_layout(int n_src, int n_views, int C, int W, int H, WarpLayout& L, boo
 }
 
 // ------------------------------------------------------------------------------------------------ masked L1
-struct Ml1Grid { unsigned tiles_x, tiles_y; };
-
-__global__ void __launch_bounds__(F3DG_ML1_THREADS)
-masked_l1_fwd_kernel(Ml1Grid grid, int C, int H, int W, const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ mask,
+__global__ void __launch_bounds__(F3DG_TILE_THREADS)
+masked_l1_fwd_kernel(TileGrid grid, int C, int H, int W, const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ mask,
                      float* __restrict__ partials)
 {
-    __shared__ float s_red[2 * F3DG_ML1_THREADS];
+    __shared__ float s_red[2 * F3DG_TILE_THREADS];
     const int tid = threadIdx.x;
-    const unsigned per_frame = grid.tiles_x * grid.tiles_y;
-    const unsigned f = blockIdx.x / per_frame, tile = blockIdx.x - f * per_frame;
+    const TileOfBlock t = tile_of_block(grid);
+    const unsigned f = t.frame;
     const int HW = H * W;
-    const int x = (int)(tile % grid.tiles_x) * F3DG_ML1_TW + tid % F3DG_ML1_TW;
-    const int y0 = (int)(tile / grid.tiles_x) * F3DG_ML1_TH + tid / F3DG_ML1_TW;
+    int tx, ty;
+    tile_thread(tid, tx, ty);
+    const int x = t.x0 + tx, y0 = t.y0 + ty;
     const float* af = a + (size_t)f * C * HW;
     const float* bf = b + (size_t)f * C * HW;
-    float acc0 = 0.0f, acc1 = 0.0f;
+    float acc[2] = { 0.0f, 0.0f };
 #pragma unroll
-    for (int j = 0; j < F3DG_ML1_TH / F3DG_ML1_ROWS; j++) {
-        const int y = y0 + j * F3DG_ML1_ROWS;
+    for (int j = 0; j < F3DG_TILE_H / F3DG_TILE_ROWS; j++) {
+        const int y = y0 + j * F3DG_TILE_ROWS;
         if (!(x < W && y < H)) continue;
         const int n = y * W + x;
         const float m = mask[(size_t)f * HW + n];
-        for (int c = 0; c < C; c++) acc0 = acc0 + m * fabsf(af[(size_t)c * HW + n] - bf[(size_t)c * HW + n]);
-        acc1 = acc1 + m;
+        for (int c = 0; c < C; c++) acc[0] = acc[0] + m * fabsf(af[(size_t)c * HW + n] - bf[(size_t)c * HW + n]);
+        acc[1] = acc[1] + m;
     }
-    s_red[tid] = acc0;
-    s_red[F3DG_ML1_THREADS + tid] = acc1;
-    for (int half = F3DG_ML1_THREADS / 2; half >= 1; half >>= 1) {       // fixed-order pairwise sum
-        __syncthreads();
-        if (tid < half) {
-            s_red[tid] = s_red[tid] + s_red[tid + half];
-            s_red[F3DG_ML1_THREADS + tid] = s_red[F3DG_ML1_THREADS + tid] + s_red[F3DG_ML1_THREADS + tid + half];
-        }
-    }
-    if (tid == 0) {
-        partials[2 * (size_t)blockIdx.x] = s_red[0];                      // [frame][tile][2]
-        partials[2 * (size_t)blockIdx.x + 1] = s_red[F3DG_ML1_THREADS];
-    }
+    tile_sums_put(s_red, acc, tid);
+    tile_sums_reduce<2>(s_red, tid, partials);
 }
 
 __global__ void __launch_bounds__(F3DG_BLOCK)
 masked_l1_bwd_kernel(unsigned blocks_per_frame, int C, int HW, const float* __restrict__ a, const float* __restrict__ b,
                      const float* __restrict__ mask, const float* __restrict__ frame_weights, float* __restrict__ dL_da)
 {
-    const unsigned f = blockIdx.x / blocks_per_frame;
-    const int n = (int)(blockIdx.x - f * blocks_per_frame) * F3DG_BLOCK + (int)threadIdx.x;
+    unsigned f;
+    int n;
+    frame_pixel_of_block(blocks_per_frame, f, n);
     if (n >= HW) return;
     const float gm = frame_weights[2 * (size_t)f] * mask[(size_t)f * HW + n];
     const size_t base = (size_t)f * C * HW + n;
@@ -289,15 +274,6 @@ masked_l1_bwd_kernel(unsigned blocks_per_frame, int C, int HW, const float* __re
         const float d = a[base + (size_t)c * HW] - b[base + (size_t)c * HW];
         dL_da[base + (size_t)c * HW] = gm * (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f));
     }
-}
-
-bool ml1_grid(int n_frames, int C, int W, int H, Ml1Grid& g, unsigned long long& blocks)
-{
-    if (n_frames <= 0 || C <= 0 || W <= 0 || H <= 0 || (long long)C * H * W > 0x7FFFFFF0ll) return false;
-    g.tiles_x = ((unsigned)W + F3DG_ML1_TW - 1u) / F3DG_ML1_TW;
-    g.tiles_y = ((unsigned)H + F3DG_ML1_TH - 1u) / F3DG_ML1_TH;
-    blocks = (unsigned long long)g.tiles_x * g.tiles_y * (unsigned long long)n_frames;
-    return blocks <= 0x7FFFFFFFull;
 }
 
 } // namespace
@@ -354,39 +330,33 @@ extern "C" int f3dg_forward_warp(void* stream, int n_src, int n_views, int C, in
 
 extern "C" size_t f3dg_masked_l1_partials_bytes(int n_frames, int C, int W, int H)
 {
-    Ml1Grid g;
-    unsigned long long blocks;
-    if (!ml1_grid(n_frames, C, W, H, g, blocks)) return 0;
-    return (size_t)blocks * 2 * sizeof(float);
+    return C > 0 ? tile_partials_bytes<2>(n_frames, W, H, (long long)C * H * W) : 0;
 }
 
 extern "C" int f3dg_masked_l1_forward(void* stream, int n_frames, int C, int H, int W, const float* a, const float* b, const float* mask,
                                       float* partials, size_t partials_bytes, float* frame_sums)
 {
     if (n_frames <= 0 || C <= 0 || H <= 0 || W <= 0 || !a || !b || !mask || !partials || !frame_sums) return F3DG_ERR_BAD_ARG;
-    Ml1Grid g;
-    unsigned long long blocks;
-    if (!ml1_grid(n_frames, C, W, H, g, blocks)) return F3DG_ERR_UNSUPPORTED;
-    if (partials_bytes < (size_t)blocks * 2 * sizeof(float)) return F3DG_ERR_WORKSPACE;
-    F3DG_KLAUNCH(masked_l1_fwd_kernel, dim3((unsigned)blocks), dim3(F3DG_ML1_THREADS), 0, (hipStream_t)stream, g, C, H, W, a, b, mask, partials);
+    TileGrid g;
+    unsigned blocks;
+    if (!tile_grid(n_frames, W, H, (long long)C * H * W, g, blocks)) return F3DG_ERR_UNSUPPORTED;
+    if (partials_bytes < tile_partials_bytes<2>(blocks)) return F3DG_ERR_WORKSPACE;
+    F3DG_KLAUNCH(masked_l1_fwd_kernel, dim3(blocks), dim3(F3DG_TILE_THREADS), 0, (hipStream_t)stream, g, C, H, W, a, b, mask, partials);
     F3DG_HIP_CHECK(hipGetLastError());
-    F3DG_KLAUNCH(f3dg_frame_sums_kernel<2>, dim3((unsigned)n_frames), dim3(64), 0, (hipStream_t)stream, g.tiles_x * g.tiles_y,
-                 (const float*)partials, frame_sums);
-    F3DG_HIP_CHECK(hipGetLastError());
-    return F3DG_OK;
+    return tile_frame_sums<2>((hipStream_t)stream, n_frames, g, partials, frame_sums);
 }
 
 extern "C" int f3dg_masked_l1_backward(void* stream, int n_frames, int C, int H, int W, const float* a, const float* b, const float* mask,
                                        const float* frame_weights, float* dL_da)
 {
     if (n_frames <= 0 || C <= 0 || H <= 0 || W <= 0 || !a || !b || !mask || !frame_weights || !dL_da) return F3DG_ERR_BAD_ARG;
-    Ml1Grid g;
-    unsigned long long blocks;
-    if (!ml1_grid(n_frames, C, W, H, g, blocks)) return F3DG_ERR_UNSUPPORTED;
-    const unsigned long long per_frame = ((unsigned long long)H * W + F3DG_BLOCK - 1) / F3DG_BLOCK;
-    if (per_frame * (unsigned long long)n_frames > 0x7FFFFFFFull) return F3DG_ERR_UNSUPPORTED;
-    F3DG_KLAUNCH(masked_l1_bwd_kernel, dim3((unsigned)(per_frame * n_frames)), dim3(F3DG_BLOCK), 0, (hipStream_t)stream, (unsigned)per_frame, C,
-                 H * W, a, b, mask, frame_weights, dL_da);
+    TileGrid g;
+    unsigned blocks;
+    if (!tile_grid(n_frames, W, H, (long long)C * H * W, g, blocks)) return F3DG_ERR_UNSUPPORTED;
+    unsigned per_frame;
+    if (!frame_pixel_grid(n_frames, H, W, per_frame, blocks)) return F3DG_ERR_UNSUPPORTED;
+    F3DG_KLAUNCH(masked_l1_bwd_kernel, dim3(blocks), dim3(F3DG_BLOCK), 0, (hipStream_t)stream, per_frame, C, H * W, a, b, mask, frame_weights,
+                 dL_da);
     F3DG_HIP_CHECK(hipGetLastError());
     return F3DG_OK;
 }

@@ -34,6 +34,19 @@ __all__ = ["ssim", "ssim_map", "l1_loss", "l2_loss", "psnr", "image_metrics", "p
            "geometry_sums", "geometry_loss", "normal_consistency", "distortion_loss", "depth_loss", "warping_sums", "warping_loss"]
 
 
+def _sum_buffers(partials_bytes, shape, terms, dev, who, unit, size):
+    """(tile slots, their bytes, sums [n, terms]) of a two-stage sum over ``shape = (n, ...)``; 0 bytes is a shape the library refuses."""
+    nbytes = partials_bytes(*shape)
+    if nbytes == 0:
+        raise ValueError(f"{who}: bad {unit} count / size ({shape[0]} {unit}s of {size})")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=dev), nbytes, torch.empty((shape[0], terms), dtype=torch.float32, device=dev)
+
+
+def _dense(g, dev):
+    """A cotangent as the backward kernels read it: dense float32 on ``dev`` (None stays None)."""
+    return None if g is None else g.to(device=dev, dtype=torch.float32).contiguous()
+
+
 def _forward_call(img1, img2, n_planes, H, W, want_map, want_planes):
     """The raw forward on contiguous float32 device tensors: (map | None, three planes | None, plane_sums [n_planes, 3])."""
     L = _lib.lib()
@@ -41,11 +54,7 @@ def _forward_call(img1, img2, n_planes, H, W, want_map, want_planes):
     new = lambda: torch.empty((n_planes, H, W), dtype=torch.float32, device=dev)
     m = new() if want_map else None
     planes = (new(), new(), new()) if want_planes else (None, None, None)
-    nbytes = L.f3dg_ssim_partials_bytes(n_planes, W, H)
-    if nbytes == 0:
-        raise ValueError(f"image loss: bad plane count / size ({n_planes} planes of {H} x {W})")
-    partials = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-    sums = torch.empty((n_planes, 3), dtype=torch.float32, device=dev)
+    partials, nbytes, sums = _sum_buffers(L.f3dg_ssim_partials_bytes, (n_planes, W, H), 3, dev, "image loss", "plane", f"{H} x {W}")
     rc = L.f3dg_ssim_forward(_stream(), n_planes, W, H, _lib.ptr(img1), _lib.ptr(img2), _lib.ptr(m), *[_lib.ptr(p) for p in planes],
                              _lib.ptr(partials), nbytes, _lib.ptr(sums))
     _lib.check(rc, "f3dg_ssim_forward")
@@ -74,8 +83,7 @@ class _ImageLoss(torch.autograd.Function):
             return None, None, None
         img1, img2, p1, p2, p3 = ctx.saved_tensors
         n_planes, H, W = img1.shape
-        dense = lambda g: None if g is None else g.to(device=img1.device, dtype=torch.float32).contiguous()
-        g_map, g_sums = dense(g_map), dense(g_sums)
+        g_map, g_sums = _dense(g_map, img1.device), _dense(g_sums, img1.device)
         d_img1 = torch.empty_like(img1)
         rc = _lib.lib().f3dg_ssim_backward(_stream(), n_planes, W, H, _lib.ptr(img1), _lib.ptr(img2), _lib.ptr(g_map), _lib.ptr(g_sums),
                                            _lib.ptr(p1), _lib.ptr(p2), _lib.ptr(p3), _lib.ptr(d_img1))
@@ -186,11 +194,7 @@ class _GeometryLoss(torch.autograd.Function):
     def forward(ctx, raster, world_view, depth_target, normal_target, alpha_target, mask, fx, fy, flags):
         F, _, H, W = raster.shape
         L = _lib.lib()
-        nbytes = L.f3dg_geometry_loss_partials_bytes(F, W, H)
-        if nbytes == 0:
-            raise ValueError(f"geometry loss: bad frame count / size ({F} frames of {H} x {W})")
-        partials = torch.empty(nbytes // 4, dtype=torch.float32, device=raster.device)
-        sums = torch.empty((F, 5), dtype=torch.float32, device=raster.device)
+        partials, nbytes, sums = _sum_buffers(L.f3dg_geometry_loss_partials_bytes, (F, W, H), 5, raster.device, "geometry loss", "frame", f"{H} x {W}")
         rc = L.f3dg_geometry_loss_forward(_stream(), F, H, W, _lib.ptr(raster), _lib.ptr(world_view), fx, fy, flags, _lib.ptr(depth_target),
                                           _lib.ptr(normal_target), _lib.ptr(alpha_target), _lib.ptr(mask), _lib.ptr(partials), nbytes,
                                           _lib.ptr(sums))
@@ -209,7 +213,7 @@ class _GeometryLoss(torch.autograd.Function):
         raster, world_view, depth_target, normal_target, alpha_target, mask = ctx.saved_tensors
         fx, fy, flags = ctx.scalars
         F, _, H, W = raster.shape
-        g_sums = g_sums.to(device=raster.device, dtype=torch.float32).contiguous()
+        g_sums = _dense(g_sums, raster.device)
         d_raster = torch.empty_like(raster)
         rc = _lib.lib().f3dg_geometry_loss_backward(_stream(), F, H, W, _lib.ptr(raster), _lib.ptr(world_view), fx, fy, flags,
                                                     _lib.ptr(depth_target), _lib.ptr(normal_target), _lib.ptr(alpha_target), _lib.ptr(mask),
@@ -368,11 +372,7 @@ class _MaskedL1(torch.autograd.Function):
     def forward(ctx, a, b, m):
         F, C, H, W = a.shape
         L = _lib.lib()
-        nbytes = L.f3dg_masked_l1_partials_bytes(F, C, W, H)
-        if nbytes == 0:
-            raise ValueError(f"warping loss: bad frame count / size ({F} frames of {C} x {H} x {W})")
-        partials = torch.empty(nbytes // 4, dtype=torch.float32, device=a.device)
-        sums = torch.empty((F, 2), dtype=torch.float32, device=a.device)
+        partials, nbytes, sums = _sum_buffers(L.f3dg_masked_l1_partials_bytes, (F, C, W, H), 2, a.device, "warping loss", "frame", f"{C} x {H} x {W}")
         rc = L.f3dg_masked_l1_forward(_stream(), F, C, H, W, _lib.ptr(a), _lib.ptr(b), _lib.ptr(m), _lib.ptr(partials), nbytes, _lib.ptr(sums))
         _lib.check(rc, "f3dg_masked_l1_forward")
         ctx.set_materialize_grads(False)
@@ -387,7 +387,7 @@ class _MaskedL1(torch.autograd.Function):
             return None, None, None
         a, b, m = ctx.saved_tensors
         F, C, H, W = a.shape
-        g_sums = g_sums.to(device=a.device, dtype=torch.float32).contiguous()
+        g_sums = _dense(g_sums, a.device)
         d_a = torch.empty_like(a)
         rc = _lib.lib().f3dg_masked_l1_backward(_stream(), F, C, H, W, _lib.ptr(a), _lib.ptr(b), _lib.ptr(m), _lib.ptr(g_sums), _lib.ptr(d_a))
         _lib.check(rc, "f3dg_masked_l1_backward")

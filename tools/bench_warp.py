@@ -4,8 +4,9 @@ of the same definition on the same device: ``scatter_reduce_(amin)`` for the z-b
 ``max_pool2d`` for the erosion, batched over all pairs, float32. The parent of this feature could not warp at all, so the composite is the
 baseline. Prints ONE JSON line. Device events around runs that end in a synchronise; both routes alternate in one process; the median of
 the rounds is reported, with the bytes each call has to move (inputs read once, outputs written once) and the workspace it also touches.
+``--loss`` adds forward + backward of losses.warping_loss of a random render against the warp's output (src x views frames), the same way.
 
-    python tools/bench_warp.py [--rounds 15] [--src 8] [--views 4] [--res 256] [--erode 5]
+    python tools/bench_warp.py [--rounds 15] [--src 8] [--views 4] [--res 256] [--erode 5] [--loss]
 """
 import argparse
 import json
@@ -19,7 +20,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import f3dgaus_amd  # noqa: E402,F401
-from f3dgaus_amd import _lib, synthetic, warp  # noqa: E402
+from f3dgaus_amd import _lib, losses, synthetic, warp  # noqa: E402
 
 
 def torch_composite(image, depth, rel, fx, fy, z_near=0.01, tol=0.05, floor=1 / 16, threshold=0.9, erode=5):
@@ -85,6 +86,7 @@ def main():
     ap.add_argument("--views", type=int, default=4)
     ap.add_argument("--res", type=int, default=256)
     ap.add_argument("--erode", type=int, default=5)
+    ap.add_argument("--loss", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_warp needs a HIP device: a time measured anywhere else says nothing")
@@ -138,6 +140,17 @@ def main():
            "io_bytes": io_bytes, "workspace_bytes": ws_bytes, "io_GBps_fused": round(io_bytes / (f_ms * 1e-3) / 1e9, 1), "agreement": agree,
            "note": "per call of all src x views pairs, rel included in both routes; io_bytes = inputs read once + outputs written once, "
                    "workspace_bytes = accumulators + z-buffer + pre-erosion mask that the fused route also fills, updates and reads"}
+    if args.loss:
+        render = torch.rand(B * V, C, R, R, generator=g, device=dev).requires_grad_()
+
+        def loss():
+            render.grad = None
+            losses.warping_loss(render, of["warped"], of["mask"]).backward()
+
+        for _ in range(2):
+            timed(loss)
+        tl = [timed(loss)[0] for _ in range(args.rounds)]
+        out["loss_fwd_bwd_ms"], out["loss_fwd_bwd_min_ms"] = round(statistics.median(tl), 4), round(min(tl), 4)
     print(json.dumps(out))
 
 
