@@ -65,6 +65,7 @@ SIGNATURES = {
                                              _p, _f, _f, _f, _p, _p, C.POINTER(_ll)]),
     "f3dg_integrate_points_view": (_i, [_p, _p, _sz, _ll, _i, _i, _i, _i, _i, _i, _p, _p, _f, _f, _p, _p, _p, _p]),
     "f3dg_debug_integrate_redo": (_i, [_p, _p, _i, _i, _i, _i, _i, _ll, C.POINTER(_i)]),
+    "f3dg_debug_integrate_export": (_i, [_p, _p, _i, _i, _i, _i, _i, _ll, _i, _p, _p, _p, _p]),
     "f3dg_mark_visible": (_i, [_p, _i, _p, _p, _p, _p]),
     # stream ws ws_bytes | N F max_edges | sdf tets tets_int32 | h_counts[4]   /   ... | tets tets_int32 n_one | interp_v faces
     "f3dg_marching_tets_workspace_bytes": (_sz, [_ll, _ll, _ll]),

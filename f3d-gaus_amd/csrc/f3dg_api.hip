@@ -541,6 +541,28 @@ extern "C" int f3dg_debug_integrate_redo(void* stream, const void* workspace, in
     return F3DG_OK;
 }
 
+extern "C" int f3dg_debug_integrate_export(void* stream, const void* workspace, int P, int PN_max, int W, int H, int n_views,
+                                           long long max_rendered, int view, unsigned* contrib_n /*[HW]*/,
+                                           unsigned short* contrib_ids /*[HW*1024]*/, unsigned* last_contributor /*[HW]*/,
+                                           float* final_T /*[HW]*/)
+{
+    if (!workspace || P <= 0 || W <= 0 || H <= 0 || n_views <= 0 || PN_max < 0 || max_rendered < 0 || view < 0 || view >= n_views)
+        return F3DG_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const F3dgLayout L = f3dg_layout(P, W, H, n_views, max_rendered);
+    const F3dgIntegLayout I = f3dg_integ_layout(P, PN_max, W, H, max_rendered, n_views);
+    const char* ws = static_cast<const char*>(workspace);
+    const size_t HW = (size_t)W * H, v = (size_t)view;
+    // camera `view`'s slice of every per-camera array, as f3dg_launch_integrate_points addresses them
+#define CP(dst, off, bytes) if (dst) F3DG_HIP_CHECK(hipMemcpyAsync(dst, ws + (off), (bytes), hipMemcpyDeviceToDevice, s))
+    CP(contrib_n, I.contrib_n + v * HW * sizeof(unsigned), HW * sizeof(unsigned));
+    CP(contrib_ids, I.contrib_ids + v * HW * 1024 * sizeof(unsigned short), HW * 1024 * sizeof(unsigned short));
+    CP(last_contributor, L.n_contrib + v * 2 * HW * sizeof(unsigned), HW * sizeof(unsigned));
+    CP(final_T, L.final_T + v * 4 * HW * sizeof(float), HW * sizeof(float));
+#undef CP
+    return F3DG_OK;
+}
+
 extern "C" int f3dg_integrate_points(void* stream, void* workspace, size_t workspace_bytes, long long max_rendered,
                                      int PN, int P, int W, int H, const float* points3D, const float* viewmatrix,
                                      float tan_fovx, float tan_fovy, float* out_color, float* out_alpha_integrated,

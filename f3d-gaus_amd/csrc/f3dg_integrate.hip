@@ -580,7 +580,7 @@ integrate_points_bin_kernel(int PN, const float* __restrict__ points3D, const fl
                             int tiles_x, float focal_x, float focal_y, const F3dgHeader* __restrict__ hdr,
                             float* __restrict__ out_alpha_integrated, float* __restrict__ out_color_integrated,
                             unsigned* __restrict__ pix_points, unsigned long long* __restrict__ tile_last,
-                            unsigned* __restrict__ pt_pix, unsigned* __restrict__ pt_rank)
+                            unsigned* __restrict__ pt_pix, unsigned* __restrict__ pt_rank, float* __restrict__ alpha_min)
 {
     const unsigned idx = blockIdx.x * F3DG_BLOCK + threadIdx.x;
     if (idx >= (unsigned)PN)
@@ -594,6 +594,10 @@ integrate_points_bin_kernel(int PN, const float* __restrict__ points3D, const fl
             out_color_integrated[3 * (size_t)idx] = 0.0f;
             out_color_integrated[3 * (size_t)idx + 1] = 0.0f;
             out_color_integrated[3 * (size_t)idx + 2] = 0.0f;
+        }
+        if (alpha_min) {             // torch.min(final_alpha, alpha_integrated) with the fill 1.0f: only a value above 1 (or +inf) changes
+            const float cur = alpha_min[idx];
+            alpha_min[idx] = cur != cur ? __builtin_nanf("") : fminf(cur, 1.0f);
         }
         pt_pix[idx] = 0xFFFFFFFFu;
         return;
@@ -847,7 +851,8 @@ int f3dg_launch_integrate_points(hipStream_t s, int view, int P, int PN, int W, 
     F3DG_HIP_CHECK(hipMemsetAsync(ws + I.pix_points, 0, I.clear_bytes, s));
     const dim3 pgrid((PN + F3DG_BLOCK - 1) / F3DG_BLOCK);
     F3DG_KLAUNCH(integrate_points_bin_kernel, pgrid, dim3(F3DG_BLOCK), 0, s, PN, points3D, viewmatrix, W, H, tiles_x,
-                       focal_x, focal_y, hdr, out_alpha_integrated, out_color_integrated, pix_points, tile_last, pt_pix, pt_rank);
+                       focal_x, focal_y, hdr, out_alpha_integrated, out_color_integrated, pix_points, tile_last, pt_pix, pt_rank,
+                       alpha_min);
     int rc = f3dg_launch_scan_inclusive(s, pix_points, pix_start, (unsigned long long)W * H,
                                         reinterpret_cast<unsigned*>(ws + I.scan_tmp), I.scan_tmp_elems, 1, nullptr);
     if (rc != F3DG_OK) return rc;

@@ -779,7 +779,8 @@ def integrate_prepare(means3D, sh, colors_precomp, opacities, scales, rotations,
 def integrate_points(prepared, points3D, alpha_min=None, want_outputs=True):
     """``f3dg_integrate_points``: one point set against a ``PreparedIntegration``. Returns (alpha_integrated [PN],
     color_integrated [PN,3]) (None, None with ``want_outputs=False``); ``alpha_min`` [PN] float32, if given, is updated in
-    place to ``torch.min(alpha_min, alpha_integrated)`` -- the accumulation of visualize.py:463 without a second kernel."""
+    place to ``torch.min(alpha_min, alpha_integrated)`` on every point (NaN propagates; a point outside the frustum / image has
+    alpha_integrated 1) -- the accumulation of visualize.py:463 without a second kernel."""
     pr = prepared
     device = pr.buffer.device
     if points3D.ndim != 2 or points3D.size(1) != 3:

@@ -278,7 +278,8 @@ long long f3dg_integrate(void* stream, void* workspace, size_t workspace_bytes, 
  * once by f3dg_integrate_prepare and stays in the workspace (sized with PN_max = the largest point set that will follow);
  * f3dg_integrate_points then costs one lane per point. out_color is written by prepare (channels 0..7) and read by
  * points (which also writes channel 8). out_alpha_integrated / out_color_integrated may be NULL; alpha_min, if not NULL,
- * is updated as alpha_min[i] = min(alpha_min[i], alpha_integrated[i]) (torch.min semantics, visualize.py:463). */
+ * is updated as alpha_min[i] = min(alpha_min[i], alpha_integrated[i]) (torch.min semantics, visualize.py:463: NaN propagates) for
+ * EVERY point -- alpha_integrated is 1 for a point outside the frustum / image, so a value above 1 comes down to 1 there. */
 long long f3dg_integrate_prepare(void* stream, void* workspace, size_t workspace_bytes, long long max_rendered,
                                  int PN_max, int P, int D, int M, const float* background, int W, int H,
                                  const float* means3D, const float* shs, const float* colors_precomp,
@@ -319,6 +320,14 @@ int f3dg_integrate_points_view(void* stream, void* workspace, size_t workspace_b
  * arguments as the preparation. */
 int f3dg_debug_integrate_redo(void* stream, const void* workspace, int P, int PN_max, int W, int H, int n_views, long long max_rendered,
                               int* h_tiles);
+
+/* Inspection: what the per-pixel pass of the last preparation on this workspace left for camera `view`, copied to device buffers of the
+ * caller (any pointer may be NULL): contrib_n [H*W] (contributors per pixel), contrib_ids [H*W*1024] (their 1-based positions in the
+ * tile's list as the 16-bit values the reference stores, forward.cu:969; only the first contrib_n of a pixel's 1,024 are defined),
+ * last_contributor [H*W] (the full position of the last one) and final_T [H*W] (transmittance of the centre ray). Same shape arguments
+ * as the preparation; asynchronous on `stream`. Records, list and ranges of the workspace come from f3dg_debug_export. */
+int f3dg_debug_integrate_export(void* stream, const void* workspace, int P, int PN_max, int W, int H, int n_views, long long max_rendered,
+                                int view, unsigned* contrib_n, unsigned short* contrib_ids, unsigned* last_contributor, float* final_T);
 
 /* present[i] = (view-space z of means3D[i] > 0.2), auxiliary.h:177-202. present is uint8 [P]. */
 int f3dg_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix,
