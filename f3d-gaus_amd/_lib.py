@@ -127,6 +127,13 @@ SIGNATURES = {
     "f3dg_mesh_compact_workspace_bytes": (_sz, [_ll, _ll]),
     "f3dg_mesh_compact_count": (_i, [_p, _p, _sz, _ll, _ll, _p, _i, _p, _p, C.POINTER(_ll)]),
     "f3dg_mesh_compact_emit": (_i, [_p, _p, _sz, _ll, _ll, _p, _i, _p, _p, _ll, _ll, _p, _p]),
+    # N F  /  stream ws ws_bytes | N F faces faces_int32 | nbr_start nbr boundary h_counts[4]
+    "f3dg_mesh_adjacency_workspace_bytes": (_sz, [_ll, _ll]),
+    "f3dg_mesh_adjacency": (_i, [_p, _p, _sz, _ll, _ll, _p, _i, _p, _p, _p, C.POINTER(_ll)]),
+    # stream | N nbr_start nbr pinned | vertices_in lambda mu iterations | scratch vertices_out
+    "f3dg_mesh_smooth": (_i, [_p, _ll, _p, _p, _p, _p, _f, _f, _i, _p, _p]),
+    # stream ws ws_bytes | N F faces faces_int32 | vertices normals
+    "f3dg_mesh_vertex_normals": (_i, [_p, _p, _sz, _ll, _ll, _p, _i, _p, _p]),
     # stream ws ws_bytes cap | n_views P W H tanx tany | stats final_T
     "f3dg_contribution": (_i, [_p, _p, _sz, _ll, _i, _i, _i, _i, _f, _f, _p, _p]),
     # P  /  stream ws ws_bytes P | stats keep min_touched min_max_weight min_sum_weight | h_kept  /  ... P n_kept | n_arrays srcs dsts row_floats (host) | kept_ids

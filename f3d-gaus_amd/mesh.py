@@ -229,6 +229,127 @@ def clean_mesh(vertices, faces, vertex_colors=None, *, min_faces=None, keep_larg
             "vertex_ids": vertex_ids, "face_component": face_component, "component_sizes": keep_sizes}
 
 
+def _no_grad_input(t, who, name):
+    if torch.is_tensor(t) and t.requires_grad:
+        raise NotImplementedError(f"{who} produces no gradient for `{name}`: detach it (the smoothed mesh is data)")
+
+
+def _vertices_arg(vertices, faces, who):
+    _require_hip(vertices)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32 or vertices.device != faces.device:
+        raise ValueError(f"{who}: vertices must be [N,3] float32 on the device of faces, got {tuple(vertices.shape)} {vertices.dtype} on {vertices.device}")
+    return vertices.contiguous()
+
+
+@torch.no_grad()
+def mesh_adjacency(faces, n_vertices):
+    """The vertex adjacency of the mesh ``faces`` [F,3] (int64 or int32, on a HIP device) over ``n_vertices`` vertices
+    (f3dg_mesh_adjacency, csrc/f3dg_mesh_smooth.hip; the definition is include/f3dg.h's). Returns a dict:
+        nbr_start [N+1] int32, nbr [2E] int32     the CSR of every vertex's distinct neighbours, ascending
+        boundary [N] bool                         the vertex has an edge with exactly one face
+        n_edges, n_boundary_vertices, n_degenerate, max_row     E, the flagged vertices, the faces with two equal ids (they contribute
+                                                  nothing), the incidence entries of the longest row (two per incident face)
+        faces, n_vertices, workspace              what ``vertex_normals`` needs to read the sorted incidence rows again
+    A face with an id outside [0, n_vertices) raises. One blocking host read. Every output is a function of the input alone."""
+    faces = _faces_arg(faces, "mesh_adjacency")
+    N, F, dev = int(n_vertices), int(faces.shape[0]), faces.device
+    if N <= 0:
+        raise ValueError(f"mesh_adjacency: the mesh needs at least one vertex (got {N})")
+    L = _lib.lib()
+    nbytes = L.f3dg_mesh_adjacency_workspace_bytes(N, F)
+    if nbytes == 0:
+        raise _lib.F3dgError(_lib.ERR_UNSUPPORTED, "f3dg_mesh_adjacency_workspace_bytes")
+    counts = (C.c_longlong * 4)()
+    with torch.cuda.device(dev):
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        nbr_start = torch.empty((N + 1,), dtype=torch.int32, device=dev)
+        nbr = torch.empty((6 * F,), dtype=torch.int32, device=dev)
+        boundary = torch.empty((N,), dtype=torch.uint8, device=dev)
+        _lib.check(L.f3dg_mesh_adjacency(_stream(), _lib.ptr(ws), nbytes, N, F, _lib.ptr(faces), int(faces.dtype == torch.int32),
+                                         _lib.ptr(nbr_start), _lib.ptr(nbr), _lib.ptr(boundary), counts), "f3dg_mesh_adjacency")
+    two_e = int(counts[0])
+    return {"nbr_start": nbr_start, "nbr": nbr[:two_e].clone(), "boundary": boundary.to(torch.bool), "n_edges": two_e // 2,
+            "n_boundary_vertices": int(counts[1]), "n_degenerate": int(counts[2]), "max_row": int(counts[3]),
+            "faces": faces, "n_vertices": N, "workspace": ws}
+
+
+def _adjacency_for(adjacency, faces, N, who):
+    if adjacency is None:
+        return mesh_adjacency(faces, N)
+    if adjacency["n_vertices"] != N or adjacency["nbr_start"].device != faces.device:
+        raise ValueError(f"{who}: the adjacency was built for {adjacency['n_vertices']} vertices on {adjacency['nbr_start'].device}, "
+                         f"the mesh has {N} on {faces.device}")
+    return adjacency
+
+
+@torch.no_grad()
+def smooth_mesh(vertices, faces, iterations=10, lam=0.5, mu=-0.53, pin_boundary=True, pinned=None, adjacency=None):
+    """Taubin lambda|mu smoothing of ``vertices`` [N,3] float32 over the mesh ``faces`` [F,3] (f3dg_mesh_smooth; the definition is
+    include/f3dg.h's): ``iterations`` times a step with ``lam`` followed by a step with ``mu`` (``mu == 0``: Laplacian smoothing, one step
+    per iteration), every step in float64 over the distinct neighbours of a vertex with uniform weights, rounded to float32 once.
+    ``pin_boundary``: vertices with a boundary edge stay where they are (the open rim of a TSDF mesh curls otherwise); ``pinned`` [N] bool
+    or uint8: further vertices that stay (OR-ed with the boundary). ``adjacency``: a ``mesh_adjacency`` of the same mesh, built here
+    otherwise. Returns {"vertices": [N,3] float32 (a new tensor), "adjacency": the dict}. The result is data: an input that requires grad
+    raises; bit-reproducible."""
+    _no_grad_input(vertices, "smooth_mesh", "vertices")
+    faces = _faces_arg(faces, "smooth_mesh")
+    vertices = _vertices_arg(vertices, faces, "smooth_mesh")
+    N, dev = int(vertices.shape[0]), vertices.device
+    lam, mu, iterations = float(lam), float(mu), int(iterations)
+    if not (0.0 < lam <= 1.0) or not (mu == 0.0 or mu < -lam) or iterations < 0:
+        raise ValueError(f"smooth_mesh: needs 0 < lam <= 1, mu == 0 or mu < -lam, and iterations >= 0 (got {lam}, {mu}, {iterations})")
+    if N == 0:
+        return {"vertices": vertices.clone(), "adjacency": adjacency}
+    adjacency = _adjacency_for(adjacency, faces, N, "smooth_mesh")
+    pin = None
+    if pinned is not None:
+        _require_hip(pinned)
+        if pinned.shape != (N,) or pinned.device != dev:
+            raise ValueError(f"smooth_mesh: pinned must be [{N}] on {dev}, got {tuple(pinned.shape)} on {pinned.device}")
+        pin = pinned != 0
+    if pin_boundary:
+        pin = adjacency["boundary"] if pin is None else pin | adjacency["boundary"]
+    pin = None if pin is None else pin.to(torch.uint8).contiguous()
+    with torch.cuda.device(dev):
+        out, scratch = torch.empty_like(vertices), torch.empty_like(vertices)
+        _lib.check(_lib.lib().f3dg_mesh_smooth(_stream(), N, _lib.ptr(adjacency["nbr_start"]), _lib.ptr(adjacency["nbr"]), _lib.ptr(pin),
+                                               _lib.ptr(vertices), lam, mu, iterations, _lib.ptr(scratch), _lib.ptr(out)), "f3dg_mesh_smooth")
+    return {"vertices": out, "adjacency": adjacency}
+
+
+@torch.no_grad()
+def vertex_normals(vertices, faces, adjacency=None):
+    """Area-weighted unit vertex normals [N,3] float32 of the mesh (f3dg_mesh_vertex_normals; the definition is include/f3dg.h's): the
+    float64 sum of the cross products of a vertex's faces in a canonical order, normalised; (0, 0, 0) for a vertex without a face or
+    with a zero or non-finite sum. ``adjacency``: a ``mesh_adjacency`` of THESE faces (its workspace holds the sorted incidence rows),
+    built here otherwise. The result is data: an input that requires grad raises; bit-reproducible."""
+    _no_grad_input(vertices, "vertex_normals", "vertices")
+    faces = _faces_arg(faces, "vertex_normals")
+    vertices = _vertices_arg(vertices, faces, "vertex_normals")
+    N, F, dev = int(vertices.shape[0]), int(faces.shape[0]), vertices.device
+    if N == 0:
+        return torch.empty((0, 3), dtype=torch.float32, device=dev)
+    adjacency = _adjacency_for(adjacency, faces, N, "vertex_normals")
+    if int(adjacency["faces"].shape[0]) != F or adjacency["faces"].dtype != faces.dtype:
+        raise ValueError("vertex_normals: the adjacency was built on other faces")
+    ws = adjacency["workspace"]
+    with torch.cuda.device(dev):
+        normals = torch.zeros((N, 3), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().f3dg_mesh_vertex_normals(_stream(), _lib.ptr(ws), ws.numel(), N, F, _lib.ptr(faces), int(faces.dtype == torch.int32),
+                                                       _lib.ptr(vertices), _lib.ptr(normals)), "f3dg_mesh_vertex_normals")
+    return normals
+
+
+def _smooth_and_normals(vertices, faces, smooth_iterations, smooth_lambda, smooth_mu, want_normals):
+    """The tail of both mesh routes: (vertices, normals or None) after the opt-in smoothing and normals."""
+    adjacency = None
+    if smooth_iterations is not None:
+        r = smooth_mesh(vertices.detach(), faces, iterations=smooth_iterations, lam=smooth_lambda, mu=smooth_mu)
+        vertices, adjacency = r["vertices"], r["adjacency"]
+    normals = vertex_normals(vertices.detach(), faces, adjacency=adjacency) if want_normals else None
+    return vertices, normals
+
+
 def build_rotation(r):
     """visualize.py:42-63: rotation matrices [P,3,3] of (unnormalised) quaternions [P,4] (w, x, y, z), in its float32 operation order."""
     norm = torch.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + r[:, 2] * r[:, 2] + r[:, 3] * r[:, 3])
@@ -323,7 +444,8 @@ def bisect_level_set(sweep, end_points, end_sdf, n_steps=8):
 
 @torch.no_grad()
 def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, resolution=256, bounds=None, trunc=None, alpha_min=0.5,
-                      min_component_faces=None, keep_largest=None):
+                      min_component_faces=None, keep_largest=None, smooth_iterations=None, smooth_lambda=0.5, smooth_mu=-0.53,
+                      vertex_normals=False):
     """The TSDF route to a coloured mesh of image ``bs`` of the Gaussian dict ``pc`` -- no tetrahedralisation from outside, nothing but
     this package (the semantics are this project's: ``f3dgaus_amd.tsdf``). All cameras are rendered in one
     launch sequence (``render_views(..., channels="rgb_depth_alpha", epilogue=False)``), depth, alpha and colour are fused into a
@@ -334,7 +456,11 @@ def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, 
 
     ``min_component_faces`` / ``keep_largest`` (opt-in; with both None the dict is exactly ``extract``'s): ``clean_mesh`` with ``min_faces``
     / ``keep_largest`` on the extracted mesh. ``vertices`` / ``faces`` / ``vertex_colors`` are then the cleaned ones and ``components``
-    holds ``vertex_ids`` (rows of ``interp_v``), ``face_component`` and ``component_sizes``."""
+    holds ``vertex_ids`` (rows of ``interp_v``), ``face_component`` and ``component_sizes``.
+
+    ``smooth_iterations`` (opt-in, after the clean-up): ``vertices`` becomes ``smooth_mesh``'s with ``smooth_lambda`` / ``smooth_mu`` and a
+    pinned boundary. ``vertex_normals`` (opt-in, last): the dict gains ``vertex_normals`` [n,3], ready for
+    ``ply.save_mesh_ply(..., vertex_normals=m["vertex_normals"])``. With the defaults the dict is exactly what it was without them."""
     from .gaussian_renderer import render_views
     from .tsdf import TSDFVolume
     xyz = pc["xyz"][bs]
@@ -365,17 +491,21 @@ def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, 
     vol.integrate(out["rendered_depth"], world_views.reshape(-1, 4, 4), cfg['model']['fov'], color=out["render"].contiguous(),
                   alpha=out["rendered_alpha"], alpha_min=alpha_min)
     m = vol.extract()
-    if min_component_faces is None and keep_largest is None:
-        return m
-    c = clean_mesh(m["vertices"], m["faces"], m["vertex_colors"], min_faces=min_component_faces, keep_largest=keep_largest)
-    m.update(vertices=c["vertices"], faces=c["faces"], vertex_colors=c["vertex_colors"],
-             components={k: c[k] for k in ("vertex_ids", "face_component", "component_sizes")})
+    if min_component_faces is not None or keep_largest is not None:
+        c = clean_mesh(m["vertices"], m["faces"], m["vertex_colors"], min_faces=min_component_faces, keep_largest=keep_largest)
+        m.update(vertices=c["vertices"], faces=c["faces"], vertex_colors=c["vertex_colors"],
+                 components={k: c[k] for k in ("vertex_ids", "face_component", "component_sizes")})
+    if smooth_iterations is not None or vertex_normals:
+        v, n = _smooth_and_normals(m["vertices"], m["faces"], smooth_iterations, smooth_lambda, smooth_mu, vertex_normals)
+        m["vertices"] = v
+        if n is not None:
+            m["vertex_normals"] = n
     return m
 
 
 @torch.no_grad()
 def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, camera_centers, bg, cfg, n_binary_steps=8, sweep=None,
-                 min_component_faces=None, keep_largest=None):
+                 min_component_faces=None, keep_largest=None, smooth_iterations=None, smooth_lambda=0.5, smooth_mu=-0.53, vertex_normals=False):
     """visualize.py:447-546 for image ``bs`` of the Gaussian dict ``pc``: alpha of ``points`` [n,3] over all cameras (one ``AlphaSweep``,
     built here unless one is handed in), marching tetrahedra of ``cells`` [F,4] (any tetrahedralisation of ``points``; the reference's
     is CGAL on the host) on sdf = alpha - 0.5, ``n_binary_steps`` bisection steps, and the scale filter
@@ -385,7 +515,10 @@ def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, c
                                                                                are kept, re-indexed (what update_vertices /
                                                                                update_faces leave, :545-546)
     With ``min_component_faces`` or ``keep_largest`` set (opt-in; the keys above are untouched) the dict also carries ``vertices_clean`` /
-    ``faces_clean``: ``clean_mesh`` with ``min_faces`` / ``keep_largest`` on ``vertices_filtered`` / ``faces_filtered``."""
+    ``faces_clean``: ``clean_mesh`` with ``min_faces`` / ``keep_largest`` on ``vertices_filtered`` / ``faces_filtered``.
+    ``smooth_iterations`` (opt-in, after the clean-up): ``vertices_smooth``, ``smooth_mesh`` with ``smooth_lambda`` / ``smooth_mu`` and a
+    pinned boundary on the last mesh above (the clean one if there is one, the filtered one otherwise; its faces are that mesh's).
+    ``vertex_normals`` (opt-in, last): ``vertex_normals`` of that mesh, on the smoothed vertices if it was smoothed."""
     from .gaussian_renderer import AlphaSweep
     _require_hip(points, points_scale, cells)
     own = sweep is None
@@ -411,4 +544,11 @@ def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, c
     if min_component_faces is not None or keep_largest is not None:
         c = clean_mesh(out["vertices_filtered"], out["faces_filtered"], min_faces=min_component_faces, keep_largest=keep_largest)
         out["vertices_clean"], out["faces_clean"] = c["vertices"], c["faces"]
+    if smooth_iterations is not None or vertex_normals:
+        last = "clean" if "vertices_clean" in out else "filtered"
+        v, n = _smooth_and_normals(out["vertices_" + last], out["faces_" + last], smooth_iterations, smooth_lambda, smooth_mu, vertex_normals)
+        if smooth_iterations is not None:
+            out["vertices_smooth"] = v
+        if n is not None:
+            out["vertex_normals"] = n
     return out

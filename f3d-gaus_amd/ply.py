@@ -79,22 +79,30 @@ def load_ply(gs_dic, bb, path):
     write_ply(path, [c(xyz), np.zeros_like(c(xyz)), c(f_dc), c(f_rest), c(opacities), c(scale), c(rotation)], names)
 
 
-def save_mesh_ply(path, vertices, faces, vertex_colors=None):
+def save_mesh_ply(path, vertices, faces, vertex_colors=None, vertex_normals=None):
     """Triangle mesh as binary little-endian PLY, in place of the ``trimesh.Trimesh(...).export`` of visualize.py:538,548: vertex
-    x y z float32 (and uchar red green blue when ``vertex_colors`` [n,3] is given), face ``list uchar int vertex_indices``.
-    vertices [n,3], faces [m,3]; tensors or arrays, on any device."""
+    x y z float32 (then nx ny nz float32 when ``vertex_normals`` [n,3] is given, then uchar red green blue when ``vertex_colors`` [n,3]
+    is given), face ``list uchar int vertex_indices``. vertices [n,3], faces [m,3]; tensors or arrays, on any device. Without normals
+    the file is byte for byte what it was before they could be written."""
     a = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
     v = np.ascontiguousarray(a(vertices), dtype="<f4").reshape(-1, 3)
     f = np.ascontiguousarray(a(faces)).reshape(-1, 3)
     assert f.size == 0 or (f.min() >= 0 and f.max() < len(v)), "face index outside the vertices"
     vdt = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % len(v)
+    if vertex_normals is not None:
+        vdt += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += "property float nx\nproperty float ny\nproperty float nz\n"
     if vertex_colors is not None:
         vdt += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
         header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(f)
     vrows = np.zeros(len(v), dtype=vdt)
     vrows["x"], vrows["y"], vrows["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if vertex_normals is not None:
+        n = np.ascontiguousarray(a(vertex_normals), dtype="<f4").reshape(-1, 3)
+        assert len(n) == len(v), (n.shape, v.shape)
+        vrows["nx"], vrows["ny"], vrows["nz"] = n[:, 0], n[:, 1], n[:, 2]
     if vertex_colors is not None:
         c = np.asarray(a(vertex_colors), dtype=np.uint8).reshape(-1, 3)
         assert len(c) == len(v), (c.shape, v.shape)
@@ -111,8 +119,9 @@ def save_mesh_ply(path, vertices, faces, vertex_colors=None):
         out.write(frows.tobytes())
 
 
-def read_mesh_ply(path):
-    """(vertices [n,3] float32, faces [m,3] int32, vertex_colors [n,3] uint8 or None) of a PLY written by ``save_mesh_ply``."""
+def read_mesh_ply(path, with_normals=False):
+    """(vertices [n,3] float32, faces [m,3] int32, vertex_colors [n,3] uint8 or None) of a PLY written by ``save_mesh_ply``; with
+    ``with_normals`` a fourth element, the vertex normals [n,3] float32 or None where the file holds none."""
     raw = open(path, "rb").read()
     end = raw.index(b"end_header\n") + len(b"end_header\n")
     lines = raw[:end].decode("ascii").splitlines()
@@ -120,11 +129,15 @@ def read_mesh_ply(path):
     n = int([ln for ln in lines if ln.startswith("element vertex")][0].split()[-1])
     m = int([ln for ln in lines if ln.startswith("element face")][0].split()[-1])
     assert "property list uchar int vertex_indices" in lines
-    colours = "property uchar red" in lines
-    vdt = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if colours else [])
+    colours, normals = "property uchar red" in lines, "property float nx" in lines
+    vdt = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] if normals else [])
+    vdt += [("red", "u1"), ("green", "u1"), ("blue", "u1")] if colours else []
     vrows = np.frombuffer(raw, dtype=vdt, count=n, offset=end)
     frows = np.frombuffer(raw, dtype=[("n", "u1"), ("i", "<i4", (3,))], count=m, offset=end + vrows.nbytes)
     assert end + vrows.nbytes + frows.nbytes == len(raw) and (frows["n"] == 3).all()
     v = np.stack([vrows["x"], vrows["y"], vrows["z"]], 1) if n else np.zeros((0, 3), dtype=np.float32)
     c = np.stack([vrows["red"], vrows["green"], vrows["blue"]], 1) if colours else None
-    return v, np.array(frows["i"]).reshape(-1, 3), c
+    out = (v, np.array(frows["i"]).reshape(-1, 3), c)
+    if with_normals:
+        out += ((np.stack([vrows["nx"], vrows["ny"], vrows["nz"]], 1) if n else np.zeros((0, 3), dtype=np.float32)) if normals else None,)
+    return out

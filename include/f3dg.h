@@ -60,6 +60,9 @@
  *       what follows either mesh route: connected components of the triangles and the removal of the small ones. The reference's
  *       script leaves that to trimesh on the host (update_vertices / update_faces, visualize.py:545-546) and labels no components:
  *       the semantics are this build's, defined below
+ *   f3dg_mesh_adjacency / f3dg_mesh_smooth / f3dg_mesh_vertex_normals
+ *       vertex adjacency of a triangle mesh, Taubin smoothing and area-weighted vertex normals: not in the reference (its script
+ *       exports what trimesh makes of the raw mesh): the semantics are this build's, defined below
  *
  * Memory ownership mirrors the reference: outputs and the workspace are allocated and owned by the caller
  * (torch tensors on the Python side). Instead of growing buffers through callbacks in the middle of the call
@@ -816,6 +819,61 @@ int f3dg_mesh_compact_count(void* stream, void* workspace, size_t workspace_byte
 int f3dg_mesh_compact_emit(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, const void* faces,
                            int faces_int32, const int* face_component, const unsigned char* keep_root, long long n_faces_kept,
                            long long n_vertices_kept, long long* faces_out, long long* vertex_ids);
+
+/* Mesh smoothing and vertex normals: the vertex adjacency of a triangle mesh, Taubin lambda|mu smoothing over it, area-weighted vertex
+ * normals (f3dg_mesh_smooth.hip). Integer atomics only and no float atomics: every output is a function of
+ * the input alone and bit-reproducible. THE SEMANTICS ARE THIS PROJECT'S; tests/mesh_smooth_truth.py restates them in float64 numpy.
+ *
+ * Mesh. vertices [N,3] float32, faces [F,3] int64 (faces_int32 = 0) or int32 (faces_int32 = 1), 0 < N < 2^31, 0 <= F < 2^31 and
+ *   6 F < 2^31 (nbr_start is int32 and the caller's nbr holds 6 F entries). An id outside [0, N) makes the call fail with
+ *   F3DG_ERR_BAD_ARG: every id is range-checked on the device before anything is indexed with it, and a refused mesh writes none of the
+ *   outputs (as f3dg_mesh_components). A face with two equal ids is DEGENERATE: it contributes nothing anywhere and is counted on its own.
+ * Incidence rows. Every non-degenerate face f = (a, b, c) gives each corner two 64-bit entries  nbr << 32 | f << 1 | succ : corner a gets
+ *   (b, f, 1) and (c, f, 0), corner b gets (c, f, 1) and (a, f, 0), corner c gets (a, f, 1) and (b, f, 0); succ marks the corner that
+ *   follows in the face's winding. A vertex's ROW is its entries SORTED ASCENDING (atomics hand out the slots of the scatter; the sort
+ *   erases their arrival order). The rows stay in the workspace for f3dg_mesh_vertex_normals.
+ * Neighbours. N(v) = the distinct nbr values of v's row, ascending; deg(v) = |N(v)|. Edge (v, w) is a BOUNDARY edge iff exactly ONE entry
+ *   of v's row has nbr == w (three or more entries for one w: non-manifold, not boundary). boundary[v] = 1 iff v has a boundary edge,
+ *   else 0. The dense CSR: nbr_start [N+1] int32 (nbr_start[0] = 0, nbr_start[N] = 2E, E the number of undirected edges), nbr int32,
+ *   N(v) at [nbr_start[v], nbr_start[v+1]). The caller sizes nbr at 6 F entries (2E <= 6 F), of which the first 2E are written.
+ * f3dg_mesh_adjacency: BLOCKING, one host read. workspace: f3dg_mesh_adjacency_workspace_bytes(N, F) bytes, 16-byte aligned,
+ *   caller-owned. boundary [N] uint8. h_counts[0..3] = 2E, boundary vertices, degenerate faces, entries of the longest row. F == 0 is
+ *   legal: nbr_start and boundary are zeros, all counts 0.
+ *   Method: one thread per face counts (range check first), one workgroup scans the counts (f3dg_scan.h), one thread per face scatters
+ *   (atomicAdd on a per-vertex fill counter), rows of at most 32 entries are sorted by one thread, longer rows by a 1024-thread workgroup
+ *   (a bitonic network in LDS up to 4,096 entries, in place beyond), one thread per vertex counts its distinct neighbours and sets its
+ *   boundary flag, one workgroup scans the degrees, one thread per vertex writes its nbr segment. No thread waits on another's write.
+ * One smoothing STEP with factor s. For a vertex that is not pinned and has deg > 0, in float64 with no contraction:
+ *   S = sum over w in N(v), ascending in w, of (double)p_w (starting from 0.0), per coordinate, and
+ *   p'_v = (float)( p_v + (double)s * ( S / (double)deg - p_v ) ).
+ *   A pinned vertex (pinned[v] != 0) and a vertex with deg == 0 are copied through; both still count as neighbours of others.
+ *   One Taubin ITERATION is a step with lambda followed by a step with mu; mu == 0 is Laplacian smoothing, one step per iteration.
+ *   Only IEEE + - * / and one rounding to float32 per step: the kernel is bit-identical to the restatement.
+ * f3dg_mesh_smooth: no host read, no workspace. nbr_start, nbr as f3dg_mesh_adjacency wrote them (an entry of nbr outside [0, N) is
+ *   skipped: it adds nothing to S); pinned [N] uint8 or NULL (nothing pinned); vertices_in, scratch, vertices_out [N,3] float32, no two
+ *   of them the same array (scratch may be NULL where the call takes at most one step). The steps ping-pong between vertices_out and
+ *   scratch so that the last one lands in vertices_out; iterations == 0 copies vertices_in. vertices_in is never written.
+ *   Valid: 0 < lambda <= 1; mu == 0 or mu < -lambda; iterations >= 0. (The usual choice: lambda 0.5, mu -0.53, 10 iterations.)
+ * Vertex normals. For every entry of v's row with succ == 1, IN ROW ORDER (each incident face once, in a canonical order), the face's
+ *   cross product (p1 - p0) x (p2 - p0) in the face's own corner order, in float64 from the float32 vertices:
+ *   (uy wz - uz wy, uz wx - ux wz, ux wy - uy wx) with u = p1 - p0, w = p2 - p0. The cross products are summed in float64 from 0.0
+ *   (area weighting), n = sqrt((sx sx + sy sy) + sz sz), and normals[v] = (float)(s / n) per coordinate; (0, 0, 0) where n is zero or
+ *   not finite, and for a vertex with no face.
+ * f3dg_mesh_vertex_normals: after an f3dg_mesh_adjacency that returned F3DG_OK, on the same workspace, sizes and faces; no host read.
+ *   normals [N,3] float32. On a workspace that holds no completed adjacency build of a mesh of these sizes NOTHING is written (as
+ *   f3dg_mesh_compact_emit). F == 0: zeros.
+ * Refused before any HIP call, nothing written (h_counts included): F3DG_ERR_BAD_ARG for a NULL workspace, nbr_start, nbr (where F > 0),
+ *   boundary, h_counts, faces (where F > 0), vertices_in, vertices_out, scratch (where more than one step is taken), vertices or normals;
+ *   N <= 0, F < 0; a workspace off the 16-byte grid; lambda, mu or iterations outside the valid set above (NaN included); two of
+ *   vertices_in, scratch, vertices_out equal. F3DG_ERR_UNSUPPORTED for N or F at or above 2^31 or 6 F at or above 2^31;
+ *   F3DG_ERR_WORKSPACE for workspace_bytes too small. f3dg_mesh_adjacency_workspace_bytes returns 0 for every size the calls refuse. */
+size_t f3dg_mesh_adjacency_workspace_bytes(long long N, long long F);
+int f3dg_mesh_adjacency(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, const void* faces, int faces_int32,
+                        int* nbr_start, int* nbr, unsigned char* boundary, long long* h_counts);
+int f3dg_mesh_smooth(void* stream, long long N, const int* nbr_start, const int* nbr, const unsigned char* pinned, const float* vertices_in,
+                     float lambda, float mu, int iterations, float* scratch, float* vertices_out);
+int f3dg_mesh_vertex_normals(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, const void* faces,
+                             int faces_int32, const float* vertices, float* normals);
 
 /* ---- Which Gaussians matter: contribution statistics and the pruning of a set (f3dg_contribution.hip) -----------
  *
