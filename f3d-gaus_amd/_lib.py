@@ -14,6 +14,7 @@ PENDING = 1
 GEOM_ALPHA_WEIGHT = 1
 MAX_PANELS, PANEL_RGB, PANEL_SIGNED, PANEL_COLORMAP = 8, 0, 1, 2
 TSDF_MAX_VIEWS = 128
+RASTER_CULL = {"none": 0, "back": 1, "front": 2}
 
 
 class Panel(C.Structure):
@@ -134,6 +135,10 @@ SIGNATURES = {
     "f3dg_mesh_smooth": (_i, [_p, _ll, _p, _p, _p, _p, _f, _f, _i, _p, _p]),
     # stream ws ws_bytes | N F faces faces_int32 | vertices normals
     "f3dg_mesh_vertex_normals": (_i, [_p, _p, _sz, _ll, _ll, _p, _i, _p, _p]),
+    # V F H W  /  stream ws ws_bytes | N F vertices faces faces_int32 | V world_views fx fy H W z_near cull | C attrs | face_id depth bary attrs_out | h_counts[7]
+    "f3dg_mesh_raster_workspace_bytes": (_sz, [_ll, _ll, _ll, _ll]),
+    "f3dg_mesh_raster": (_i, [_p, _p, _sz, _ll, _ll, _p, _p, _i, _i, _p, C.c_double, C.c_double, _i, _i, C.c_double, _i, _i, _p, _p, _p, _p, _p,
+                              C.POINTER(_ll)]),
     # stream ws ws_bytes cap | n_views P W H tanx tany | stats final_T
     "f3dg_contribution": (_i, [_p, _p, _sz, _ll, _i, _i, _i, _i, _f, _f, _p, _p]),
     # P  /  stream ws ws_bytes P | stats keep min_touched min_max_weight min_sum_weight | h_kept  /  ... P n_kept | n_arrays srcs dsts row_floats (host) | kept_ids

@@ -350,6 +350,116 @@ def _smooth_and_normals(vertices, faces, smooth_iterations, smooth_lambda, smoot
     return vertices, normals
 
 
+def _focal_pair(fov, H, W):
+    """fx, fy in pixels as ``TSDFVolume.integrate`` forms them: ``fov`` in degrees (``cfg['model']['fov']``) or a pair ``(fx, fy)``."""
+    if isinstance(fov, (tuple, list)):
+        return float(fov[0]), float(fov[1])
+    FoV = float(fov) * math.pi / 180
+    return W / (2 * math.tan(FoV / 2.)), H / (2 * math.tan(FoV / 2.))
+
+
+def interpolate_vertex_attributes(attrs, faces, face_id, bary):
+    """The rasteriser's attribute interpolation as torch operations, differentiable in ``attrs`` alone: ``attrs`` [N,C], ``faces``
+    [F,3], ``face_id`` [V,H,W] (-1: empty) and ``bary`` [V,3,H,W] as ``render_mesh`` returns them -> [V,C,H,W], the three gathered
+    corner rows weighted by ``bary`` and summed as ``(a0 b0 + a1 b1) + a2 b2`` in float32; 0 where the pixel is empty. It equals the
+    kernel's fused output within the float32 roundings of that sum (the kernel sums in float64 and rounds once)."""
+    _require_hip(attrs, faces, face_id, bary)
+    if attrs.dim() != 2 or face_id.dim() != 3 or bary.dim() != 4 or bary.shape[1] != 3:
+        raise ValueError(f"interpolate_vertex_attributes: attrs [N,C], face_id [V,H,W], bary [V,3,H,W]; got {tuple(attrs.shape)}, "
+                         f"{tuple(face_id.shape)}, {tuple(bary.shape)}")
+    hit = face_id >= 0
+    corners = faces.to(torch.int64)[face_id.clamp(min=0).to(torch.int64)]        # [V,H,W,3]
+    w = bary.detach().permute(0, 2, 3, 1)                                        # [V,H,W,3]
+    out = (attrs[corners[..., 0]] * w[..., 0:1] + attrs[corners[..., 1]] * w[..., 1:2]) + attrs[corners[..., 2]] * w[..., 2:3]
+    return (out * hit[..., None].to(out.dtype)).permute(0, 3, 1, 2)
+
+
+def render_mesh(vertices, faces, world_views, fov, resolution, *, vertex_colors=None, vertex_normals=None, cull='none', z_near=0.01):
+    """Draw the mesh ``vertices`` [N,3] float32 / ``faces`` [F,3] (int64 or int32) from the cameras ``world_views`` [V,4,4] (or
+    [V,1,4,4]; the renderer's row-vector convention) with the exact z-buffered rasteriser (f3dg_mesh_raster, csrc/f3dg_mesh_raster.hip;
+    the definition is include/f3dg.h's). ``fov`` in degrees as ``cfg['model']['fov']`` or a pair ``(fx, fy)`` in pixels, as
+    ``TSDFVolume.integrate`` takes it; ``resolution`` an int or ``(H, W)``; ``cull`` 'none', 'back' or 'front' (front: counter-clockwise
+    in world space seen from outside); a face with a corner at or behind ``z_near`` is dropped, not clipped. Returns a dict:
+        face_id [V,H,W] int32 (-1: empty), depth [V,H,W], alpha [V,H,W] (1.0 where a face is), bary [V,3,H,W]
+        color [V,3,H,W] or None      ``vertex_colors`` [N,3] interpolated perspective-correctly
+        normal [V,3,H,W] or None     ``vertex_normals`` [N,3] interpolated, renormalised; 0 where empty or of zero length (world space)
+        counts                       dict: rasterised, near, guard, degenerate, culled (pairs; they sum to V F), large, covered (pixels)
+    Geometry is data: ``vertices`` that require grad raise. Attributes that require grad go through
+    ``interpolate_vertex_attributes`` (differentiable in them alone) instead of the kernel's fused output. One blocking host read;
+    every output is a function of the inputs alone: bit-reproducible. A face with an id outside [0, N) raises."""
+    _no_grad_input(vertices, "render_mesh", "vertices")
+    _require_hip(world_views)
+    faces = _faces_arg(faces, "render_mesh")
+    vertices = _vertices_arg(vertices, faces, "render_mesh")
+    if cull not in _lib.RASTER_CULL:
+        raise ValueError(f"render_mesh: cull must be one of {sorted(_lib.RASTER_CULL)}, got {cull!r}")
+    H, W = (int(resolution[0]), int(resolution[1])) if isinstance(resolution, (tuple, list)) else (int(resolution), int(resolution))
+    N, F, dev = int(vertices.shape[0]), int(faces.shape[0]), vertices.device
+    wv = world_views.detach().reshape(-1, 4, 4).to(torch.float32).contiguous()
+    V = int(wv.shape[0])
+    if N <= 0 or V <= 0 or wv.device != dev:
+        raise ValueError(f"render_mesh: needs at least one vertex and one camera on {dev} (got {N} vertices, {V} cameras on {wv.device})")
+    fx, fy = _focal_pair(fov, H, W)
+    sets = []
+    for name, a in (("vertex_colors", vertex_colors), ("vertex_normals", vertex_normals)):
+        if a is not None:
+            _require_hip(a)
+            if tuple(a.shape) != (N, 3) or a.dtype != torch.float32 or a.device != dev:
+                raise ValueError(f"render_mesh: {name} must be [{N},3] float32 on {dev}, got {tuple(a.shape)} {a.dtype} on {a.device}")
+            sets.append(a)
+    fused = [a for a in sets if not a.requires_grad]
+    attrs = torch.cat(fused, dim=1).contiguous() if fused else None             # C = 3 or 6: both sets travel in one call
+    Cn = 0 if attrs is None else int(attrs.shape[1])
+    L = _lib.lib()
+    nbytes = L.f3dg_mesh_raster_workspace_bytes(V, F, H, W)
+    if nbytes == 0:
+        raise _lib.F3dgError(_lib.ERR_UNSUPPORTED, "f3dg_mesh_raster_workspace_bytes")
+    counts = (C.c_longlong * 7)()
+    with torch.no_grad(), torch.cuda.device(dev):
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        face_id = torch.empty((V, H, W), dtype=torch.int32, device=dev)
+        depth = torch.empty((V, H, W), dtype=torch.float32, device=dev)
+        bary = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev)
+        attrs_out = torch.empty((V, Cn, H, W), dtype=torch.float32, device=dev) if Cn else None
+        _lib.check(L.f3dg_mesh_raster(_stream(), _lib.ptr(ws), nbytes, N, F, _lib.ptr(vertices), _lib.ptr(faces), int(faces.dtype == torch.int32),
+                                      V, _lib.ptr(wv), fx, fy, H, W, float(z_near), _lib.RASTER_CULL[cull], Cn, _lib.ptr(attrs),
+                                      _lib.ptr(face_id), _lib.ptr(depth), _lib.ptr(bary), _lib.ptr(attrs_out), counts), "f3dg_mesh_raster")
+    planes, at = {}, 0
+    for name, a in (("color", vertex_colors), ("normal", vertex_normals)):
+        if a is None:
+            planes[name] = None
+        elif a.requires_grad:
+            planes[name] = interpolate_vertex_attributes(a, faces, face_id, bary)
+        else:
+            planes[name] = attrs_out[:, at:at + 3]
+            at += 3
+    if planes["normal"] is not None:
+        n = planes["normal"]
+        length = n.norm(dim=1, keepdim=True)
+        planes["normal"] = torch.where(length > 0, n / length.clamp(min=torch.finfo(torch.float32).tiny), torch.zeros_like(n))
+    names = ("rasterised", "near", "guard", "degenerate", "culled", "large", "covered")
+    return {"face_id": face_id, "depth": depth, "alpha": (face_id >= 0).to(torch.float32), "bary": bary, "color": planes["color"],
+            "normal": planes["normal"], "counts": {k: int(c) for k, c in zip(names, counts)}}
+
+
+@torch.no_grad()
+def mesh_depth_agreement(mesh_depth, mesh_alpha, render_depth, render_alpha, alpha_min=0.5):
+    """How far the depth of a drawn mesh (``render_mesh``'s ``depth`` / ``alpha``) lies from the depth the Gaussian rasteriser composited
+    (``render_views``' ``rendered_depth`` / ``rendered_alpha``), over the pixels both cover (alpha >= ``alpha_min``): a dict of ``mean``
+    and ``max`` |mesh depth - rendered depth| (NaN where no pixel is covered by both) and the counts ``n_both``, ``n_mesh``,
+    ``n_render``. All maps [V,H,W] or [V,1,H,W]. One host read."""
+    _require_hip(mesh_depth, mesh_alpha, render_depth, render_alpha)
+    md, rd = mesh_depth.reshape(-1).double(), render_depth.reshape(-1).double()
+    if md.shape != rd.shape or mesh_alpha.numel() != md.numel() or render_alpha.numel() != md.numel():
+        raise ValueError("mesh_depth_agreement: the four maps must hold the same pixels")
+    m, r = mesh_alpha.reshape(-1) >= alpha_min, render_alpha.reshape(-1) >= alpha_min
+    both = m & r
+    d = torch.where(both, (md - rd).abs(), torch.zeros_like(md))
+    nb = both.sum()
+    stats = torch.stack([d.sum() / nb, torch.where(nb > 0, d.max(), d.sum() / nb), nb.double(), m.sum().double(), r.sum().double()]).cpu().tolist()
+    return {"mean": stats[0], "max": stats[1], "n_both": int(stats[2]), "n_mesh": int(stats[3]), "n_render": int(stats[4])}
+
+
 def build_rotation(r):
     """visualize.py:42-63: rotation matrices [P,3,3] of (unnormalised) quaternions [P,4] (w, x, y, z), in its float32 operation order."""
     norm = torch.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + r[:, 2] * r[:, 2] + r[:, 3] * r[:, 3])

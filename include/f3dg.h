@@ -63,6 +63,10 @@
  *   f3dg_mesh_adjacency / f3dg_mesh_smooth / f3dg_mesh_vertex_normals
  *       vertex adjacency of a triangle mesh, Taubin smoothing and area-weighted vertex normals: not in the reference (its script
  *       exports what trimesh makes of the raw mesh): the semantics are this build's, defined below
+ *   f3dg_mesh_raster
+ *       an exact z-buffered triangle rasteriser over the renderer's cameras (face id, depth, barycentric weights, interpolated vertex
+ *       attributes per pixel): not in the reference (the texturing branch of visualize.py:520-537 is dead code and the mesh is never
+ *       drawn): the semantics are this build's, defined below
  *
  * Memory ownership mirrors the reference: outputs and the workspace are allocated and owned by the caller
  * (torch tensors on the Python side). Instead of growing buffers through callbacks in the middle of the call
@@ -874,6 +878,70 @@ int f3dg_mesh_smooth(void* stream, long long N, const int* nbr_start, const int*
                      float lambda, float mu, int iterations, float* scratch, float* vertices_out);
 int f3dg_mesh_vertex_normals(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, const void* faces,
                              int faces_int32, const float* vertices, float* normals);
+
+/* Mesh rasteriser: a triangle mesh drawn from the renderer's cameras with an exact integer coverage test and a 64-bit z-buffer
+ * (f3dg_mesh_raster.hip). Integer atomics only: every output is a function of the input alone and
+ * bit-reproducible. THE SEMANTICS ARE THIS PROJECT'S; tests/mesh_raster_truth.py restates them in float64 numpy. No clipping, no
+ * anti-aliasing, no gradients, no textures.
+ *
+ * Inputs. vertices [N,3] float32 (world space); faces [F,3] int64 (faces_int32 = 0) or int32 (1); world_views [V,4,4] float32 in the
+ *   renderer's row-vector convention (m_rc = world_views[v][r][c]); fx, fy > 0 in pixels (W / (2 tan(fov / 2)), H / (2 tan(fov / 2)) as
+ *   TSDFVolume.integrate forms them); z_near > 0; cull = F3DG_RASTER_CULL_NONE / _BACK / _FRONT; attrs [N,C] float32, 1 <= C <= 8, or
+ *   NULL with C = 0. An id outside [0, N) makes the call fail with F3DG_ERR_BAD_ARG: every id is range-checked on the device before
+ *   anything is indexed with it, and a refused mesh writes none of the outputs and nothing to h_counts.
+ * Every (view, face) PAIR falls into exactly one of five classes, tested in this order:
+ *   1. DEGENERATE by ids: two of the face's ids are equal. Nothing is projected.
+ *   2. Projection of each corner, float64 on the float32 inputs, in this operation order:
+ *        x = ((X m00 + Y m10) + Z m20) + m30,  y = ((X m01 + Y m11) + Z m21) + m31,  z = ((X m02 + Y m12) + Z m22) + m32,
+ *        u = ((fx x) / z + W / 2) - 0.5,  v = ((fy y) / z + H / 2) - 0.5      (W / 2 = (double)W / 2.0, exact)
+ *      so that pixel (i, j) -- column i, row j -- has its centre at u = i, v = j: the forward warp's convention and the renderer's.
+ *      NEAR / NON-FINITE: a corner with a non-finite x, y or z, with not (z > z_near), or with a non-finite u or v. No clipping.
+ *   3. GUARD BAND: a corner with not (|u| <= 16384 and |v| <= 16384), tested in floating point before anything becomes an integer.
+ *   4. Snapping: U = rint(256 u), V = rint(256 v), ties to even (|U|, |V| <= 2^22). Everything about coverage is integer from here.
+ *      Signed area A = (U1 - U0)(V2 - V0) - (V1 - V0)(U2 - U0). DEGENERATE (the same count as class 1): A == 0.
+ *   5. CULLED. v grows downwards, so a face whose corners run counter-clockwise in world space as seen from outside (its normal
+ *      (p1 - p0) x (p2 - p0) points at the camera) has A < 0 under a world_view with a proper rotation: A < 0 is FRONT.
+ *      _CULL_BACK drops A > 0, _CULL_FRONT drops A < 0.
+ *   What is left is RASTERISED (also when it covers no pixel centre).
+ * Coverage. If A < 0, corners 1 and 2 change places FOR THE TEST (o = (0, 2, 1), else o = (0, 1, 2)). For each edge a -> b of the oriented
+ *   triangle (o0 -> o1, o1 -> o2, o2 -> o0) and the pixel centre P = (256 i, 256 j):  E = (Ub - Ua)(Py - Va) - (Vb - Va)(Px - Ua)  in
+ *   int64. The pixel is covered iff for all three edges  E > 0, or E == 0 and (Vb - Va > 0 or (Vb - Va == 0 and Ub - Ua < 0)):  a centre
+ *   on the edge shared by two triangles belongs to exactly one of them, whatever their windings.
+ * Depth and weights at a covered pixel, float64 with one rounding to float32 at the end. w_k = the edge value of the oriented edge
+ *   opposite the face's OWN corner k (corner o0: edge o1 -> o2; o1: o2 -> o0; o2: o0 -> o1), lambda_k = (double)w_k / (double)|A| (both
+ *   integers are exact in a double), q_k = 1 / z_k, and in the face's own corner order
+ *        D = (lambda_0 q_0 + lambda_1 q_1) + lambda_2 q_2,   depth = (float)(1 / D),   beta_k = (lambda_k q_k) / D,
+ *        bary_k = (float)beta_k,   attr_c = (float)((a_0c beta_0 + a_1c beta_1) + a_2c beta_2)        (a_kc = (double)attrs[id_k][c]).
+ *   Only IEEE + - * / and rint: the kernels are bit-identical to the restatement.
+ * Visibility. A pixel holds one 64-bit key  bits(depth) << 32 | face  (empty: all ones); keys are combined under an unsigned 64-bit
+ *   atomicMin, so the nearest face wins and at equal float32 depth the least face id.
+ * Outputs, EVERY element assigned by an accepted call: face_id [V,H,W] int32 (-1 where empty), depth [V,H,W] float32 (0 where empty),
+ *   bary [V,3,H,W] float32 (0 where empty), attrs_out [V,C,H,W] float32 where attrs is given (0 where empty).
+ *   h_counts[0..6] = pairs rasterised, dropped near / non-finite, dropped by the guard band, degenerate, culled (these five sum to
+ *   V F), pairs queued as large (among the rasterised), covered pixels (face_id >= 0, all views).
+ * f3dg_mesh_raster: BLOCKING, one host read at the end (the counts and whether an id was out of range). workspace:
+ *   f3dg_mesh_raster_workspace_bytes(V, F, H, W) = 256 + align256(8 V H W) + align256(4 V F) bytes (a header, the keys, the queue of
+ *   the large pairs), 16-byte aligned, caller-owned. F == 0 is legal: every pixel is empty.
+ *   Method: one launch fills the keys; one thread per pair projects, snaps and takes the box of pixel centres i in [ceil(Umin / 256),
+ *   floor(Umax / 256)] (and rows likewise) cut to the image: an empty box ends there, a box of at most 64 centres is walked by the
+ *   thread, a larger one is queued (one integer atomic hands out the slot; the atomicMin erases the arrival order); a fixed grid reads
+ *   the queue's length from device memory and strides the lanes of a wave over every box of at most 512 centres and the 256 threads of a
+ *   workgroup over every larger one; one thread per pixel re-derives the winner's weights with the device function the scatter used
+ *   and writes every output. No float atomics, no thread waits on another, every loop is bounded by a box or by the queue.
+ * Refused before any HIP call, nothing written (h_counts included): F3DG_ERR_BAD_ARG for a NULL workspace, vertices, world_views,
+ *   face_id, depth, bary or h_counts, NULL faces where F > 0, attrs without attrs_out or attrs_out without attrs, C outside 0..8 or not
+ *   matching attrs (C == 0 iff attrs is NULL), N <= 0, F < 0, non-positive V, H or W, fx, fy or z_near not positive and finite, a cull
+ *   outside 0..2, a workspace off the 16-byte grid. F3DG_ERR_UNSUPPORTED for N or F at or above 2^31, H or W above 16384, V H W or V F at
+ *   or above 2^31. F3DG_ERR_WORKSPACE for workspace_bytes too small. f3dg_mesh_raster_workspace_bytes returns 0 for every size the call
+ *   refuses. */
+#define F3DG_RASTER_CULL_NONE 0
+#define F3DG_RASTER_CULL_BACK 1
+#define F3DG_RASTER_CULL_FRONT 2
+size_t f3dg_mesh_raster_workspace_bytes(long long V, long long F, long long H, long long W);
+int f3dg_mesh_raster(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, const float* vertices,
+                     const void* faces, int faces_int32, int V, const float* world_views, double fx, double fy, int H, int W,
+                     double z_near, int cull, int C, const float* attrs, int* face_id, float* depth, float* bary, float* attrs_out,
+                     long long* h_counts);
 
 /* ---- Which Gaussians matter: contribution statistics and the pruning of a set (f3dg_contribution.hip) -----------
  *
