@@ -24,7 +24,7 @@ from .gaussian_predictor import GaussianSplatPredictor_gtunet, splat_head, splat
 from .unet_gs import Unet_GS_gtunet  # noqa: E402,F401
 from .mesh import marching_tetrahedra, tetra_points, bisect_level_set, extract_mesh, extract_mesh_tsdf, mesh_components, clean_mesh  # noqa: E402,F401
 from .mesh import mesh_adjacency, smooth_mesh, vertex_normals  # noqa: E402,F401
-from .mesh import render_mesh, interpolate_vertex_attributes, mesh_depth_agreement  # noqa: E402,F401
+from .mesh import render_mesh, interpolate_vertex_attributes, mesh_depth_agreement, bake_vertex_colors  # noqa: E402,F401
 from .tsdf import TSDFVolume  # noqa: E402,F401
 from .frames import compose_frames, compose_orbit_frames, depth_range, colormap_lut  # noqa: E402,F401
 from .warp import forward_warp, relative_transforms  # noqa: E402,F401

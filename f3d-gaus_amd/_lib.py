@@ -15,6 +15,8 @@ GEOM_ALPHA_WEIGHT = 1
 MAX_PANELS, PANEL_RGB, PANEL_SIGNED, PANEL_COLORMAP = 8, 0, 1, 2
 TSDF_MAX_VIEWS = 128
 RASTER_CULL = {"none": 0, "back": 1, "front": 2}
+BAKE_MODE = {"blend": 0, "best": 1}
+BAKE_COUNTS = ("near", "outside", "uncovered", "occluded", "grazing", "masked", "used", "vertices_seen")
 
 
 class Panel(C.Structure):
@@ -139,6 +141,11 @@ SIGNATURES = {
     "f3dg_mesh_raster_workspace_bytes": (_sz, [_ll, _ll, _ll, _ll]),
     "f3dg_mesh_raster": (_i, [_p, _p, _sz, _ll, _ll, _p, _p, _i, _i, _p, C.c_double, C.c_double, _i, _i, C.c_double, _i, _i, _p, _p, _p, _p, _p,
                               C.POINTER(_ll)]),
+    # V N H W  /  stream ws ws_bytes | N vertices normals | V world_views fx fy H W z_near | C images face_id depth alpha alpha_min |
+    # depth_tol cos_min mode | colors weight n_used best_view | h_counts[8]
+    "f3dg_mesh_bake_workspace_bytes": (_sz, [_ll, _ll, _ll, _ll]),
+    "f3dg_mesh_bake_colors": (_i, [_p, _p, _sz, _ll, _p, _p, _ll, _p, C.c_double, C.c_double, _ll, _ll, C.c_double, _i, _p, _p, _p, _p,
+                                   C.c_double, C.c_double, C.c_double, _i, _p, _p, _p, _p, C.POINTER(_ll)]),
     # stream ws ws_bytes cap | n_views P W H tanx tany | stats final_T
     "f3dg_contribution": (_i, [_p, _p, _sz, _ll, _i, _i, _i, _i, _f, _f, _p, _p]),
     # P  /  stream ws ws_bytes P | stats keep min_touched min_max_weight min_sum_weight | h_kept  /  ... P n_kept | n_arrays srcs dsts row_floats (host) | kept_ids

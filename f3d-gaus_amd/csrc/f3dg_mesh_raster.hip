@@ -16,6 +16,7 @@
 // A face with an id out of range sets hdr->bad in raster_small_kernel; the later kernels return at once then, so a refused mesh writes
 // no output.
 #include "f3dg_common.h"
+#include "f3dg_mesh_project.h"
 
 namespace {
 
@@ -84,8 +85,6 @@ struct RasterTri {                  // a rasterised pair, set up
     int i0, i1, j0, j1;             // the box of pixel centres, cut to the image (empty when i1 < i0 or j1 < j0)
 };
 
-__device__ __forceinline__ bool rast_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }       // (false for a NaN)
-
 __device__ __forceinline__ int rast_ceil256(int a) { return (a + 255) >> 8; }       // ceil(a / 256), a of either sign
 __device__ __forceinline__ int rast_floor256(int a) { return a >> 8; }              // floor(a / 256)
 
@@ -108,12 +107,8 @@ __device__ int raster_setup(const RasterArgs& A, u32 view, u32 f, RasterTri& T)
     for (int k = 0; k < 3; k++) {
         const float* p = A.vertices + 3 * (size_t)T.id[k];
         const double X = (double)p[0], Y = (double)p[1], Z = (double)p[2];
-        const double x = ((X * (double)m[0] + Y * (double)m[4]) + Z * (double)m[8]) + (double)m[12];
-        const double y = ((X * (double)m[1] + Y * (double)m[5]) + Z * (double)m[9]) + (double)m[13];
-        const double z = ((X * (double)m[2] + Y * (double)m[6]) + Z * (double)m[10]) + (double)m[14];
-        u[k] = ((A.fx * x) / z + A.half_w) - 0.5;
-        v[k] = ((A.fy * y) / z + A.half_h) - 0.5;
-        near = near || !rast_finite(x) || !rast_finite(y) || !rast_finite(z) || !(z > A.z_near) || !rast_finite(u[k]) || !rast_finite(v[k]);
+        double x, y, z;
+        if (f3dg_mesh_project(X, Y, Z, m, A.fx, A.fy, A.half_w, A.half_h, A.z_near, x, y, z, u[k], v[k])) near = true;
         guard = guard || !(fabs(u[k]) <= RAST_GUARD && fabs(v[k]) <= RAST_GUARD);
         T.q[k] = 1.0 / z;
     }

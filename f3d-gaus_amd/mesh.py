@@ -460,6 +460,100 @@ def mesh_depth_agreement(mesh_depth, mesh_alpha, render_depth, render_alpha, alp
     return {"mean": stats[0], "max": stats[1], "n_both": int(stats[2]), "n_mesh": int(stats[3]), "n_render": int(stats[4])}
 
 
+@torch.no_grad()
+def _mean_edge_length(vertices, faces):
+    """The mean length of the three edges of every face, float64 (an edge shared by two faces counts twice). One host read."""
+    if faces.shape[0] == 0:
+        return 0.0
+    p = vertices.double()[faces.to(torch.int64)]                                # [F,3,3]
+    return float((p - p.roll(-1, dims=1)).norm(dim=2).mean())
+
+
+def bake_vertex_colors(vertices, faces, images, world_views, fov, *, vertex_normals=None, alpha=None, alpha_min=0.5, depth_tol=None,
+                       cos_min=0.1, mode='blend', cull='none', z_near=0.01, visibility=None):
+    """Colour the vertices of a mesh from the views (f3dg_mesh_bake_colors, csrc/f3dg_mesh_bake.hip; the definition is include/f3dg.h's):
+    every vertex of ``vertices`` [N,3] float32 is projected into every view of ``images`` [V,C,H,W] float32 (1 <= C <= 8; the resolution
+    is taken from it) under ``world_views`` [V,4,4] (or [V,1,4,4]) and ``fov`` (degrees or a pair ``(fx, fy)``, as ``render_mesh`` takes
+    them), tested against the mesh's own z-buffer, sampled bilinearly and combined over the views in ascending order. A (view, vertex)
+    sample is used unless the vertex is at or behind ``z_near``, projects outside the image, lands on a pixel no face covers, lies more
+    than ``depth_tol`` behind that pixel's depth (occluded), faces the camera with a cosine below ``cos_min`` (only with
+    ``vertex_normals`` [N,3]; its weight is then the squared cosine, 1 otherwise), or touches a tap with ``alpha`` [V,H,W] (or
+    [V,1,H,W]) below ``alpha_min`` or with a non-finite colour. ``mode``: 'blend' (the weighted mean of the used samples) or 'best' (the
+    sample of the largest weight, the earliest view at a tie). ``depth_tol=None`` takes the mean edge length of the mesh (float64 in
+    torch: one more host read). ``visibility``: a ``render_mesh`` result of this mesh from these cameras at this resolution to reuse;
+    when None, ``render_mesh(vertices, faces, world_views, fov, (H, W), cull=cull, z_near=z_near)`` is called. Returns a dict:
+        vertex_colors [N,C], weight [N]     the colour and the weight it carries (0 where no view saw the vertex)
+        n_used [N] int32, best_view [N] int32 (-1: none)
+        counts                               dict of (view, vertex) pairs: near, outside, uncovered, occluded, grazing, masked, used (they
+                                             sum to V N), and vertices_seen
+        visibility                           the ``render_mesh`` result that was used
+    Geometry and frames are data: ``vertices`` or ``images`` that require grad raise. One blocking host read; every output is a function
+    of the inputs alone: bit-reproducible."""
+    _no_grad_input(vertices, "bake_vertex_colors", "vertices")
+    _no_grad_input(images, "bake_vertex_colors", "images")
+    _require_hip(images, world_views)
+    faces = _faces_arg(faces, "bake_vertex_colors")
+    vertices = _vertices_arg(vertices, faces, "bake_vertex_colors")
+    if mode not in _lib.BAKE_MODE:
+        raise ValueError(f"bake_vertex_colors: mode must be one of {sorted(_lib.BAKE_MODE)}, got {mode!r}")
+    N, dev = int(vertices.shape[0]), vertices.device
+    if images.dim() != 4 or images.dtype != torch.float32 or images.device != dev or not 1 <= images.shape[1] <= 8:
+        raise ValueError(f"bake_vertex_colors: images must be [V,C,H,W] float32 with 1 <= C <= 8 on {dev}, got {tuple(images.shape)} "
+                         f"{images.dtype} on {images.device}")
+    images = images.contiguous()
+    V, Cn, H, W = (int(s) for s in images.shape)
+    wv = world_views.detach().reshape(-1, 4, 4).to(torch.float32).contiguous()
+    if N <= 0 or int(wv.shape[0]) != V or wv.device != dev:
+        raise ValueError(f"bake_vertex_colors: needs at least one vertex and one camera per image on {dev} (got {N} vertices, {V} images, "
+                         f"{int(wv.shape[0])} cameras on {wv.device})")
+    planes = {}
+    for name, a, shape in (("vertex_normals", vertex_normals, (N, 3)), ("alpha", alpha, (V, H, W))):
+        if a is not None:
+            _require_hip(a)
+            a = a.detach()
+            if name == "alpha" and a.dim() == 4 and a.shape[1] == 1:
+                a = a[:, 0]
+            if tuple(a.shape) != shape or a.dtype != torch.float32 or a.device != dev:
+                raise ValueError(f"bake_vertex_colors: {name} must be {list(shape)} float32 on {dev}, got {tuple(a.shape)} {a.dtype} on {a.device}")
+            a = a.contiguous()
+        planes[name] = a
+    if visibility is None:
+        visibility = render_mesh(vertices, faces, wv, fov, (H, W), cull=cull, z_near=z_near)
+    face_id, depth = visibility["face_id"], visibility["depth"]
+    if tuple(face_id.shape) != (V, H, W) or tuple(depth.shape) != (V, H, W) or face_id.dtype != torch.int32 or depth.dtype != torch.float32 \
+            or face_id.device != dev or depth.device != dev:
+        raise ValueError(f"bake_vertex_colors: visibility must hold face_id int32 and depth float32 of shape {[V, H, W]} on {dev}")
+    face_id, depth = face_id.contiguous(), depth.contiguous()
+    if depth_tol is None:
+        depth_tol = _mean_edge_length(vertices, faces)
+    fx, fy = _focal_pair(fov, H, W)
+    L = _lib.lib()
+    nbytes = L.f3dg_mesh_bake_workspace_bytes(V, N, H, W)
+    if nbytes == 0:
+        raise _lib.F3dgError(_lib.ERR_UNSUPPORTED, "f3dg_mesh_bake_workspace_bytes")
+    counts = (C.c_longlong * 8)()
+    with torch.no_grad(), torch.cuda.device(dev):
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        colors = torch.empty((N, Cn), dtype=torch.float32, device=dev)
+        weight = torch.empty((N,), dtype=torch.float32, device=dev)
+        n_used = torch.empty((N,), dtype=torch.int32, device=dev)
+        best_view = torch.empty((N,), dtype=torch.int32, device=dev)
+        _lib.check(L.f3dg_mesh_bake_colors(_stream(), _lib.ptr(ws), nbytes, N, _lib.ptr(vertices), _lib.ptr(planes["vertex_normals"]), V,
+                                           _lib.ptr(wv), fx, fy, H, W, float(z_near), Cn, _lib.ptr(images), _lib.ptr(face_id), _lib.ptr(depth),
+                                           _lib.ptr(planes["alpha"]), float(alpha_min), float(depth_tol), float(cos_min),
+                                           _lib.BAKE_MODE[mode], _lib.ptr(colors), _lib.ptr(weight), _lib.ptr(n_used), _lib.ptr(best_view),
+                                           counts), "f3dg_mesh_bake_colors")
+    return {"vertex_colors": colors, "weight": weight, "n_used": n_used, "best_view": best_view,
+            "counts": {k: int(c) for k, c in zip(_lib.BAKE_COUNTS, counts)}, "visibility": visibility}
+
+
+def _color_from_views(vertices, faces, normals, render, world_views, fov, depth_tol):
+    """The tail of both mesh routes: ``bake_vertex_colors`` of the rendered frames (``render_views(..., channels="rgb_depth_alpha",
+    epilogue=False)``) onto the final vertices."""
+    return bake_vertex_colors(vertices.detach().contiguous(), faces, render["render"].detach().contiguous(), world_views, fov,
+                              vertex_normals=normals, alpha=render["rendered_alpha"].detach(), depth_tol=depth_tol)
+
+
 def build_rotation(r):
     """visualize.py:42-63: rotation matrices [P,3,3] of (unnormalised) quaternions [P,4] (w, x, y, z), in its float32 operation order."""
     norm = torch.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + r[:, 2] * r[:, 2] + r[:, 3] * r[:, 3])
@@ -555,7 +649,7 @@ def bisect_level_set(sweep, end_points, end_sdf, n_steps=8):
 @torch.no_grad()
 def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, resolution=256, bounds=None, trunc=None, alpha_min=0.5,
                       min_component_faces=None, keep_largest=None, smooth_iterations=None, smooth_lambda=0.5, smooth_mu=-0.53,
-                      vertex_normals=False):
+                      vertex_normals=False, color_from_views=False):
     """The TSDF route to a coloured mesh of image ``bs`` of the Gaussian dict ``pc`` -- no tetrahedralisation from outside, nothing but
     this package (the semantics are this project's: ``f3dgaus_amd.tsdf``). All cameras are rendered in one
     launch sequence (``render_views(..., channels="rgb_depth_alpha", epilogue=False)``), depth, alpha and colour are fused into a
@@ -570,7 +664,12 @@ def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, 
 
     ``smooth_iterations`` (opt-in, after the clean-up): ``vertices`` becomes ``smooth_mesh``'s with ``smooth_lambda`` / ``smooth_mu`` and a
     pinned boundary. ``vertex_normals`` (opt-in, last): the dict gains ``vertex_normals`` [n,3], ready for
-    ``ply.save_mesh_ply(..., vertex_normals=m["vertex_normals"])``. With the defaults the dict is exactly what it was without them."""
+    ``ply.save_mesh_ply(..., vertex_normals=m["vertex_normals"])``. With the defaults the dict is exactly what it was without them.
+
+    ``color_from_views`` (opt-in, last of all): the rendered frames are baked onto the FINAL vertices (``bake_vertex_colors`` with the
+    rendered alpha, the final normals if they were asked for, and ``depth_tol`` of two voxels). ``vertex_colors`` becomes the baked colour
+    where a view saw the vertex and stays the volume's elsewhere; the dict gains ``vertex_colors_tsdf`` (the volume's colours) and
+    ``color_views`` [n] int32 (the views that coloured each vertex)."""
     from .gaussian_renderer import render_views
     from .tsdf import TSDFVolume
     xyz = pc["xyz"][bs]
@@ -610,12 +709,19 @@ def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, 
         m["vertices"] = v
         if n is not None:
             m["vertex_normals"] = n
+    if color_from_views and m["vertices"].shape[0]:
+        b = _color_from_views(m["vertices"], m["faces"], m.get("vertex_normals"), out, world_views, cfg['model']['fov'], 2 * voxel)
+        m["vertex_colors_tsdf"], m["color_views"] = m["vertex_colors"], b["n_used"]
+        m["vertex_colors"] = torch.where((b["n_used"] > 0)[:, None], b["vertex_colors"], m["vertex_colors"])
+    elif color_from_views:
+        m["vertex_colors_tsdf"], m["color_views"] = m["vertex_colors"], torch.zeros((0,), dtype=torch.int32, device=xyz.device)
     return m
 
 
 @torch.no_grad()
 def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, camera_centers, bg, cfg, n_binary_steps=8, sweep=None,
-                 min_component_faces=None, keep_largest=None, smooth_iterations=None, smooth_lambda=0.5, smooth_mu=-0.53, vertex_normals=False):
+                 min_component_faces=None, keep_largest=None, smooth_iterations=None, smooth_lambda=0.5, smooth_mu=-0.53, vertex_normals=False,
+                 color_from_views=False):
     """visualize.py:447-546 for image ``bs`` of the Gaussian dict ``pc``: alpha of ``points`` [n,3] over all cameras (one ``AlphaSweep``,
     built here unless one is handed in), marching tetrahedra of ``cells`` [F,4] (any tetrahedralisation of ``points``; the reference's
     is CGAL on the host) on sdf = alpha - 0.5, ``n_binary_steps`` bisection steps, and the scale filter
@@ -628,8 +734,12 @@ def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, c
     ``faces_clean``: ``clean_mesh`` with ``min_faces`` / ``keep_largest`` on ``vertices_filtered`` / ``faces_filtered``.
     ``smooth_iterations`` (opt-in, after the clean-up): ``vertices_smooth``, ``smooth_mesh`` with ``smooth_lambda`` / ``smooth_mu`` and a
     pinned boundary on the last mesh above (the clean one if there is one, the filtered one otherwise; its faces are that mesh's).
-    ``vertex_normals`` (opt-in, last): ``vertex_normals`` of that mesh, on the smoothed vertices if it was smoothed."""
-    from .gaussian_renderer import AlphaSweep
+    ``vertex_normals`` (opt-in, last): ``vertex_normals`` of that mesh, on the smoothed vertices if it was smoothed.
+    ``color_from_views`` (opt-in, last of all; what the dead texturing branch of visualize.py:520-537 would have done): the cameras are
+    rendered once (``render_views(..., channels="rgb_depth_alpha", epilogue=False)``) and baked onto that last mesh
+    (``bake_vertex_colors`` with the rendered alpha and the normals if they were asked for); the dict gains ``vertex_colors`` [n,3] (0 where
+    no view saw the vertex) and ``color_views`` [n] int32."""
+    from .gaussian_renderer import AlphaSweep, render_views
     _require_hip(points, points_scale, cells)
     own = sweep is None
     if own:
@@ -661,4 +771,14 @@ def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, c
             out["vertices_smooth"] = v
         if n is not None:
             out["vertex_normals"] = n
+    if color_from_views:
+        last = "smooth" if "vertices_smooth" in out else "clean" if "vertices_clean" in out else "filtered"
+        v, f = out["vertices_" + last], out["faces_" + ("clean" if "faces_clean" in out else "filtered")]
+        if v.shape[0]:
+            frames = render_views(pc, bs, world_views, full_projs, camera_centers, bg, cfg, channels="rgb_depth_alpha", epilogue=False)
+            b = _color_from_views(v, f, out.get("vertex_normals"), frames, world_views, cfg['model']['fov'], None)
+            out["vertex_colors"], out["color_views"] = b["vertex_colors"], b["n_used"]
+        else:
+            out["vertex_colors"] = torch.zeros((0, 3), dtype=torch.float32, device=v.device)
+            out["color_views"] = torch.zeros((0,), dtype=torch.int32, device=v.device)
     return out

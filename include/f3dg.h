@@ -67,6 +67,9 @@
  *       an exact z-buffered triangle rasteriser over the renderer's cameras (face id, depth, barycentric weights, interpolated vertex
  *       attributes per pixel): not in the reference (the texturing branch of visualize.py:520-537 is dead code and the mesh is never
  *       drawn): the semantics are this build's, defined below
+ *   f3dg_mesh_bake_colors / f3dg_mesh_bake_workspace_bytes
+ *       the views' colour put back on the mesh's vertices, each (view, vertex) sample tested against f3dg_mesh_raster's own z-buffer:
+ *       what the dead texturing branch of visualize.py:520-537 never did; the semantics are this build's, defined below
  *
  * Memory ownership mirrors the reference: outputs and the workspace are allocated and owned by the caller
  * (torch tensors on the Python side). Instead of growing buffers through callbacks in the middle of the call
@@ -942,6 +945,67 @@ int f3dg_mesh_raster(void* stream, void* workspace, size_t workspace_bytes, long
                      const void* faces, int faces_int32, int V, const float* world_views, double fx, double fy, int H, int W,
                      double z_near, int cull, int C, const float* attrs, int* face_id, float* depth, float* bary, float* attrs_out,
                      long long* h_counts);
+
+/* Vertex colour baking: the views' colour put back on a mesh, every (view, vertex) sample tested against the z-buffer f3dg_mesh_raster
+ * wrote for this mesh and these cameras (f3dg_mesh_bake.hip). THE SEMANTICS ARE THIS PROJECT'S;
+ * tests/mesh_bake_truth.py restates them in float64 numpy. No gradients, no UV atlas or per-face texture, no seam or exposure
+ * compensation between views, no clipping.
+ *
+ * Inputs. vertices [N,3] float32; normals [N,3] float32 or NULL; world_views [V,4,4] float32, row-vector convention as
+ *   f3dg_mesh_raster; fx, fy, z_near doubles, formed as for f3dg_mesh_raster; images [V,C,H,W] float32, 1 <= C <= 8; face_id [V,H,W]
+ *   int32 and depth [V,H,W] float32 as f3dg_mesh_raster wrote them for this mesh and these cameras; alpha [V,H,W] float32 or NULL;
+ *   alpha_min double; depth_tol double, >= 0 and finite; cos_min double in [0,1]; mode F3DG_BAKE_BLEND (0) or F3DG_BAKE_BEST (1).
+ * Projection: f3dg_mesh_raster's to the bit (one device function serves both), float64 on the float32 inputs with no contraction:
+ *        x = ((X m00 + Y m10) + Z m20) + m30, likewise y and z;  u = ((fx x) / z + W / 2) - 0.5,  v = ((fy y) / z + H / 2) - 0.5;
+ *   pixel centres sit at integer u, v.
+ * Every (view, vertex) PAIR lands in exactly one of seven counted classes, tested in this order:
+ *   1. NEAR: any of x, y, z, u, v is not finite, or not (z > z_near).
+ *   2. OUTSIDE: not (0 <= u <= W - 1 and 0 <= v <= H - 1).
+ *   3. UNCOVERED: with i = (int)rint(u), j = (int)rint(v) (ties to even), face_id[view][j][i] < 0.
+ *   4. OCCLUDED: not (z - (double)depth[view][j][i] <= depth_tol).
+ *   5. GRAZING (only with normals): n_c = ((nx m0c + ny m1c) + nz m2c) for c = 0, 1, 2;  g = -((n_0 x + n_1 y) + n_2 z);
+ *      nn = (n_0 n_0 + n_1 n_1) + n_2 n_2;  pp = (x x + y y) + z z;  the pair is grazing iff nn is not finite, or not (nn > 0), or
+ *      not (g > 0), or not (g g >= cm2 (nn pp)), with cm2 = cos_min cos_min formed on the host. Otherwise w = (g g) / (nn pp), which is
+ *      cos^2 of the angle between the normal and the ray to the camera; no square root is taken. Without normals w = 1 and nothing is
+ *      grazing.
+ *   6. MASKED: the taps are i0 = (int)floor(u), i1 = min(i0 + 1, W - 1), j0 = (int)floor(v), j1 = min(j0 + 1, H - 1); masked iff alpha
+ *      is given and not ((double)alpha >= alpha_min) at any of the four taps, or any of the 4 C colour taps is not finite.
+ *   7. USED: the sample, float64, with a = u - i0, b = v - j0 and cxy the tap at column ix, row jy:
+ *        top = c00 + a (c10 - c00),   bot = c01 + a (c11 - c01),   s_c = top + b (bot - top).
+ * Per vertex, over its used samples in ASCENDING VIEW ORDER (the order of the sum is part of the definition):
+ *   the best sample is the first used one, replaced by a later one iff that one's w > the best's w (the largest w, the earliest view
+ *   at a tie);
+ *   BLEND: Sw = Sw + w and S_c = S_c + w s_c from 0, float64, product then sum;  colors[i][c] = (float)(S_c / Sw),  weight[i] = (float)Sw;
+ *   BEST:  colors[i][c] = (float)s_c of the best sample,  weight[i] = (float)w of it;
+ *   both:  n_used[i] = the number of used samples,  best_view[i] = the view of the best sample.
+ *   A vertex with no used sample gets colors = 0, weight = 0, n_used = 0, best_view = -1.
+ * Outputs, EVERY element assigned by an accepted call: colors [N,C] float32, weight [N] float32, n_used [N] int32, best_view [N] int32.
+ *   h_counts[0..7] = pairs near, outside, uncovered, occluded, grazing, masked, used (these seven sum to V N), then the vertices with
+ *   n_used > 0.
+ * Only IEEE + - * /, rint and floor in float64 and one rounding to float32 per output; no float atomics: the outputs are a function of
+ *   the inputs alone and equal the restatement bit for bit.
+ * f3dg_mesh_bake_colors: BLOCKING, one host read at the end (the counts). workspace: f3dg_mesh_bake_workspace_bytes(V, N, H, W) = 256
+ *   bytes for every accepted size (the header of counters; the kernel stages its samples in LDS and keeps its sums in registers),
+ *   16-byte aligned, caller-owned.
+ *   Method: one launch. A wave takes 16 vertices x a slice of 4 consecutive views, one pair per lane; every lane classifies its pair
+ *   and leaves (w, s_c) in LDS; one lane per vertex folds the slice in ascending view order into registers, and the same wave walks
+ *   the vertex's slices in ascending order, so no partial sum is re-associated. The matrices are widened to double once per workgroup,
+ *   128 views at a time, in a table the workgroup refills between two barriers: V is not limited by it. One integer atomicAdd per wave
+ *   and class. No thread waits on another wave; every loop is bounded by V.
+ * Refused on the host before any launch, nothing written (h_counts included): F3DG_ERR_BAD_ARG for a NULL workspace, vertices,
+ *   world_views, images, face_id, depth, colors, weight, n_used, best_view or h_counts (normals and alpha may be NULL), a non-positive
+ *   N, V, H or W, C outside 1..8, fx, fy or z_near not finite or <= 0, depth_tol negative or not finite, cos_min outside [0,1] or NaN,
+ *   a NaN alpha_min when alpha is given, a mode outside {0, 1}, a workspace off the 16-byte grid. F3DG_ERR_UNSUPPORTED for H or W above
+ *   16384, or N, V, V N or V H W at or above 2^31. F3DG_ERR_WORKSPACE for workspace_bytes too small.
+ *   f3dg_mesh_bake_workspace_bytes returns 0 for every size the call refuses. */
+#define F3DG_BAKE_BLEND 0
+#define F3DG_BAKE_BEST 1
+size_t f3dg_mesh_bake_workspace_bytes(long long V, long long N, long long H, long long W);
+int f3dg_mesh_bake_colors(void* stream, void* workspace, size_t workspace_bytes, long long N, const float* vertices, const float* normals,
+                          long long V, const float* world_views, double fx, double fy, long long H, long long W, double z_near,
+                          int C, const float* images, const int* face_id, const float* depth, const float* alpha, double alpha_min,
+                          double depth_tol, double cos_min, int mode, float* colors, float* weight, int* n_used, int* best_view,
+                          long long* h_counts);
 
 /* ---- Which Gaussians matter: contribution statistics and the pruning of a set (f3dg_contribution.hip) -----------
  *
