@@ -24,6 +24,8 @@ namespace {
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
+typedef unsigned short u16;
+typedef unsigned char u8;
 
 // ------------------------------------------------------------------------------------------------ scan
 // Three-kernel scan of n u32 values: per-block sums -> scan of block sums (one workgroup) -> per-block scan.
@@ -138,13 +140,6 @@ struct ShiftDigit {
     u32 mask = 255u;        // (a pass over fewer than 8 bits: the tile passes split their bits evenly)
     __device__ __forceinline__ u32 operator()(u32 k) const { return (k >> shift) & mask; }
 };
-// third and LAST pass of a view's depth sort when all its keys lie within 2^24 of kbase (a multiple of 2^16: the low 16 bits of
-// key - kbase are the key's own, which passes 0 and 1 sorted). Keys of Gaussians that touch no tile (~0) land in digit 255; they
-// produce no instances, so their place in the order is irrelevant.
-struct CompactDigit {
-    u32 kbase;
-    __device__ __forceinline__ u32 operator()(u32 k) const { const u32 d = (k - kbase) >> 16; return d < 255u ? d : 255u; }
-};
 
 template <typename K, typename DIGIT, bool MINMAX = false>
 __device__ __forceinline__ void hist_chunk(const K* __restrict__ keys, const SegChunk& ck, const DIGIT digit, u32* __restrict__ hist,
@@ -200,11 +195,35 @@ struct ScatterShared {
     u32 sval[F3DG_SORT_CHUNK];
 };
 
-// IOTA: the payload of the input is its position inside the segment (first pass of the depth sort)
-template <typename K, bool IOTA, typename DIGIT>
-__device__ __forceinline__ void scatter_chunk(const K* __restrict__ keys_in, const u32* __restrict__ vals_in, K* __restrict__ keys_out,
-                                              u32* __restrict__ vals_out, const SegChunk& ck, const DIGIT digit,
-                                              const u32* __restrict__ offsets /* exclusive scan of hist */, ScatterShared& sh, K* skey)
+// the key a pass hands to the next one: as it is, or without the bits that no later pass reads (compact views of the depth sort)
+struct KeepKey {
+    __device__ __forceinline__ u32 operator()(u32 k) const { return k; }
+};
+// 32 -> 16 bits behind pass 0 of a compact view: bits 8..23 of key - kbase (every key that touches a tile is below 2^24 there); the
+// key ~0 of a Gaussian that touches no tile becomes 0xFFFF, digit 255 of both later passes as before
+struct Narrow16 {
+    u32 kbase;
+    __device__ __forceinline__ u32 operator()(u32 k) const { return k == 0xFFFFFFFFu ? 0xFFFFu : (k - kbase) >> 8; }
+};
+// 16 -> 8 bits behind pass 1 of a compact view: what is left is the digit of pass 2
+struct Narrow8 {
+    __device__ __forceinline__ u32 operator()(u32 k) const { return k >> 8; }
+};
+
+// The entry of the scanned histogram that holds the first output position of digit threadIdx.x of a chunk (F3DG_BLOCK = 256 digits).
+__device__ __forceinline__ u64 chunk_offset_entry(const SegChunk& ck) { return ck.obase + (u64)threadIdx.x * ck.cps + ck.c; }
+
+// IOTA: the payload of the input is its position inside the segment (first pass of the depth sort).
+// K is the key type read (and staged in LDS: the digit is taken from it), KO the one written, narrow(key). keys_in is indexed like
+// vals_in, by seg_base + position in the segment, and keys_out like vals_out, by the position the scan gives: for keys narrower than
+// 32 bits the caller passes pointers moved to where that index finds the segment's keys (gsort_keys).
+// goff is offsets[chunk_offset_entry(ck)], which the caller loads BEFORE the call: the address depends on the chunk alone, so the
+// round trip runs beside the key loads and the ranking instead of standing alone between two barriers. A persistent caller names its
+// next chunk (next, or null): that chunk's entry is asked for ahead of the write-out and returned in goff.
+template <typename K, typename KO, bool IOTA, typename DIGIT, typename NARROW>
+__device__ __forceinline__ void scatter_chunk(const K* __restrict__ keys_in, const u32* __restrict__ vals_in, KO* __restrict__ keys_out,
+                                              u32* __restrict__ vals_out, const SegChunk& ck, const DIGIT digit, const NARROW narrow,
+                                              const u32* __restrict__ offsets /* exclusive scan of hist */, u32& goff, const SegChunk* next, ScatterShared& sh, K* skey)
 {
     // the chunk is digit-sorted inside LDS (stable), then written out in coalesced runs
     const u32 n = ck.n;
@@ -256,7 +275,7 @@ __device__ __forceinline__ void scatter_chunk(const K* __restrict__ keys_in, con
         const u32 tot = c0 + c1 + c2 + c3;
         const u32 excl = block_scan_exclusive<F3DG_BLOCK / 64>(tot, sh.wtot);
         sh.lbase[d] = excl;
-        sh.gdelta[d] = offsets[ck.obase + (u64)d * ck.cps + ck.c] - excl;
+        sh.gdelta[d] = goff - excl;
         sh.cnt[0][d] = excl;
         sh.cnt[1][d] = excl + c0;
         sh.cnt[2][d] = excl + c0 + c1;
@@ -274,22 +293,29 @@ __device__ __forceinline__ void scatter_chunk(const K* __restrict__ keys_in, con
         }
     }
     __syncthreads();
+    if (next) goff = offsets[chunk_offset_entry(*next)];
     for (u32 slot = threadIdx.x; slot < in_block; slot += F3DG_BLOCK) {
         const K k = skey[slot];
         const u32 d = digit((u32)k);
         const u32 pos = sh.gdelta[d] + slot;          // global position (the scan spans all segments)
-        if (keys_out) keys_out[pos] = k;
+        if (keys_out) keys_out[pos] = (KO)narrow((u32)k);
         vals_out[pos] = sh.sval[slot];
     }
 }
 
 // ---- equal segments of seg_len elements (the per-view depth sort of the Gaussians): one chunk per workgroup.
-// Pass 1 also finds every chunk's key range, reduced to every view's [kmin, kmax] (minmax[2 v], [2 v + 1]) by gsort_range_kernel. A view whose
-// range fits 2^24 above kbase = kmin & ~0xFFFF is "compact": its third pass sorts by (key - kbase) >> 16 and is its last, the fourth
-// returns at once -- histogram, per-view scan and scatter; only under the general scan, which spans all views, its histogram is a
-// stand-in with the right sum so that the scan keeps the other views' positions --, and the view's order is the OUTPUT OF PASS 2
-// (see gsort_perm_is_pass2). Depth ranges within a factor of 2-4 -- object-centric cameras -- are compact; others take the four
-// plain passes.
+// Pass 0, which reads every key cold anyway, also finds every chunk's key range, reduced to every view's [kmin, kmax] (minmax[2 v],
+// [2 v + 1]) by gsort_range_kernel before the pass's scatter runs. A view whose range fits 2^24 above kbase = kmin & ~0xFFFF is
+// "compact": its third pass sorts by (key - kbase) >> 16 and is its last, the fourth returns at once -- histogram, per-view scan and
+// scatter; only under the general scan, which spans all views, its histogram is a stand-in with the right sum so that the scan keeps
+// the other views' positions --, and the view's order is the OUTPUT OF PASS 2 (see gsort_gather_rects_kernel). Depth ranges within a
+// factor of 2-4 -- object-centric cameras -- are compact; others take the four plain passes.
+//
+// A compact view's keys also lose, pass by pass, the bytes that no later pass reads: pass 0 writes (key - kbase) >> 8 in 16 bits
+// (Narrow16; kbase is a multiple of 2^16, so bits 8..15 are the key's own, the digit of pass 1), pass 1 writes the top 8 of those
+// (Narrow8), which IS the digit of pass 2, and pass 2 writes no keys. The digits are the ones of the 32-bit keys, so the order is
+// the same element for element. The narrow keys of view v lie at the start of the view's own P * 4 bytes of the key array, which a
+// non-compact view of the same call fills with 32-bit keys: one launch per pass serves both, a workgroup branches on its view.
 __device__ __forceinline__ SegChunk fixed_chunk(u32 seg_len, u32 cps)
 {
     u32 seg, c;
@@ -297,6 +323,22 @@ __device__ __forceinline__ SegChunk fixed_chunk(u32 seg_len, u32 cps)
     SegChunk ck;
     ck.seg_base = (u64)seg * seg_len; ck.obase = (u64)seg * 256u * cps; ck.n = seg_len; ck.cps = cps; ck.c = c; ck.seg = seg;
     return ck;
+}
+
+// the chunk with its segment's first key counted in units of K from the base of the (u32) key array: what hist_chunk, whose aligned
+// vectors are counted from that base, takes for narrow keys
+template <typename K>
+__device__ __forceinline__ SegChunk narrow_chunk(SegChunk ck)
+{
+    ck.seg_base *= 4u / (u32)sizeof(K);
+    return ck;
+}
+// the key array as keys of type K, moved so that the index of the payload arrays (seg_base + position in the segment, which is also
+// the output position the scan gives) finds the segment's narrow keys
+template <typename K>
+__device__ __forceinline__ K* gsort_keys(const u32* keys, const SegChunk& ck)
+{
+    return reinterpret_cast<K*>(const_cast<u32*>(keys)) + ck.seg_base * (4u / (u32)sizeof(K) - 1u);
 }
 
 __device__ __forceinline__ bool gsort_compact(const u32* __restrict__ minmax, u32 view, u32& kbase)
@@ -313,17 +355,17 @@ gsort_hist_kernel(const u32* __restrict__ keys, u32 seg_len, u32 cps, u32* __res
 {
     __shared__ u32 h[F3DG_BLOCK / 64][256];
     const SegChunk ck = fixed_chunk(seg_len, cps);
-    if constexpr (PASS == 0) {
-        hist_chunk<u32, ShiftDigit>(keys, ck, ShiftDigit{0}, hist, h);
-    } else if constexpr (PASS == 1) {        // (pass 1 reads the keys from the cache; pass 0 reads them cold)
-        hist_chunk<u32, ShiftDigit, true>(keys, ck, ShiftDigit{8}, hist, h, chunk_minmax + 2 * ((size_t)ck.seg * cps + ck.c));
+    if constexpr (PASS == 0) {               // (no view's range is known yet: the digit is the low byte of the 32-bit key either way)
+        hist_chunk<u32, ShiftDigit, true>(keys, ck, ShiftDigit{0}, hist, h, chunk_minmax + 2 * ((size_t)ck.seg * cps + ck.c));
     } else {
         u32 kbase;
         const bool compact = gsort_compact(minmax, ck.seg, kbase);
         if (!compact) {
             hist_chunk<u32, ShiftDigit>(keys, ck, ShiftDigit{8 * PASS}, hist, h);
+        } else if constexpr (PASS == 1) {
+            hist_chunk<u16, ShiftDigit>(reinterpret_cast<const u16*>(keys), narrow_chunk<u16>(ck), ShiftDigit{0}, hist, h);
         } else if constexpr (PASS == 2) {
-            hist_chunk<u32, CompactDigit>(keys, ck, CompactDigit{kbase}, hist, h);
+            hist_chunk<u8, ShiftDigit>(reinterpret_cast<const u8*>(keys), narrow_chunk<u8>(ck), ShiftDigit{0}, hist, h);
         } else if (standin) {
             const u64 base = (u64)ck.c * F3DG_SORT_CHUNK;
             const u32 in_chunk = (u32)((ck.n - base) < (u64)F3DG_SORT_CHUNK ? (ck.n - base) : (u64)F3DG_SORT_CHUNK);
@@ -368,20 +410,24 @@ gsort_scatter_kernel(const u32* __restrict__ keys_in, const u32* __restrict__ va
                      u32* __restrict__ vals_out, u32 seg_len, u32 cps, const u32* __restrict__ offsets, const u32* __restrict__ minmax)
 {
     __shared__ ScatterShared sh;
-    __shared__ u32 skey[F3DG_SORT_CHUNK];
+    __shared__ u32 skey[F3DG_SORT_CHUNK];          // (keys of the type the pass reads: a narrow pass uses the front of it)
     const SegChunk ck = fixed_chunk(seg_len, cps);
-    if constexpr (PASS == 0) {           // the payload of the input is its position inside the segment
-        scatter_chunk<u32, true, ShiftDigit>(keys_in, vals_in, keys_out, vals_out, ck, ShiftDigit{0}, offsets, sh, skey);
+    u32 goff = offsets[chunk_offset_entry(ck)];
+    u32 kbase;
+    const bool compact = gsort_compact(minmax, ck.seg, kbase);
+    // (the keys are not read again after a view's LAST pass -- pass 2 of a compact view, pass 3 otherwise --: it does not write them)
+    if (!compact) {
+        scatter_chunk<u32, u32, PASS == 0, ShiftDigit, KeepKey>(keys_in, vals_in, PASS == 3 ? (u32*)nullptr : keys_out, vals_out, ck, ShiftDigit{8 * PASS},
+                                                                KeepKey{}, offsets, goff, nullptr, sh, skey);
+    } else if constexpr (PASS == 0) {    // the payload of the input is its position inside the segment
+        scatter_chunk<u32, u16, true, ShiftDigit, Narrow16>(keys_in, vals_in, gsort_keys<u16>(keys_out, ck), vals_out, ck, ShiftDigit{0}, Narrow16{kbase},
+                                                            offsets, goff, nullptr, sh, skey);
     } else if constexpr (PASS == 1) {
-        scatter_chunk<u32, false, ShiftDigit>(keys_in, vals_in, keys_out, vals_out, ck, ShiftDigit{8}, offsets, sh, skey);
-    } else {
-        u32 kbase;
-        const bool compact = gsort_compact(minmax, ck.seg, kbase);
-        // (the keys are not read again after a view's LAST pass -- pass 2 of a compact view, pass 3 otherwise --: it does not write them)
-        if (!compact)
-            scatter_chunk<u32, false, ShiftDigit>(keys_in, vals_in, PASS == 3 ? (u32*)nullptr : keys_out, vals_out, ck, ShiftDigit{8 * PASS}, offsets, sh, skey);
-        else if constexpr (PASS == 2)
-            scatter_chunk<u32, false, CompactDigit>(keys_in, vals_in, (u32*)nullptr, vals_out, ck, CompactDigit{kbase}, offsets, sh, skey);
+        scatter_chunk<u16, u8, false, ShiftDigit, Narrow8>(gsort_keys<u16>(keys_in, ck), vals_in, gsort_keys<u8>(keys_out, ck), vals_out, ck, ShiftDigit{0},
+                                                           Narrow8{}, offsets, goff, nullptr, sh, reinterpret_cast<u16*>(skey));
+    } else if constexpr (PASS == 2) {
+        scatter_chunk<u8, u8, false, ShiftDigit, KeepKey>(gsort_keys<u8>(keys_in, ck), vals_in, (u8*)nullptr, vals_out, ck, ShiftDigit{0}, KeepKey{},
+                                                          offsets, goff, nullptr, sh, reinterpret_cast<u8*>(skey));
     }
 }
 
@@ -510,18 +556,27 @@ radix2_hist_var_kernel(const K* __restrict__ keys, SegTable st, int shift, u32 m
         hist_chunk<K, ShiftDigit>(keys, ck, ShiftDigit{shift, mask}, hist, h);
 }
 
+// (four waves per SIMD is what the LDS allows; the registers are held to it, 128, now that the next chunk's offset is carried along)
 template <typename K>
-__global__ void __launch_bounds__(F3DG_BLOCK)
+__global__ void __launch_bounds__(F3DG_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4)))
 radix2_scatter_var_kernel(const K* __restrict__ keys_in, const u32* __restrict__ vals_in, K* __restrict__ keys_out,
                           u32* __restrict__ vals_out, SegTable st, int shift, u32 mask, const u32* __restrict__ offsets)
 {
     __shared__ ScatterShared sh;
     __shared__ K skey[F3DG_SORT_CHUNK];
-    u32 k = 0;
-    SegChunk ck;
-    for (u32 f = blockIdx.x >> 3; var_chunk(st, f, k, ck); f += gridDim.x >> 3) {
-        scatter_chunk<K, false, ShiftDigit>(keys_in, vals_in, keys_out, vals_out, ck, ShiftDigit{shift, mask}, offsets, sh, skey);
+    const u32 stride = gridDim.x >> 3;
+    u32 k = 0, f = blockIdx.x >> 3;
+    SegChunk ck, next;
+    bool live = var_chunk(st, f, k, ck);
+    u32 goff = live ? offsets[chunk_offset_entry(ck)] : 0u;
+    while (live) {
+        // the next chunk is looked up first: its entry of the offsets is asked for while this chunk is written out
+        u32 kn = k;
+        const bool more = var_chunk(st, f + stride, kn, next);
+        scatter_chunk<K, K, false, ShiftDigit, KeepKey>(keys_in, vals_in, keys_out, vals_out, ck, ShiftDigit{shift, mask}, KeepKey{}, offsets, goff,
+                                                        more ? &next : (const SegChunk*)nullptr, sh, skey);
         __syncthreads();          // the LDS staging area is reused by the next chunk
+        ck = next; k = kn; f += stride; live = more;
     }
 }
 
@@ -554,13 +609,17 @@ gsort_gather_rects_kernel(int P, u32* __restrict__ gv0, u32* __restrict__ gv1, c
     const int k0 = (int)(chunk * F3DG_BLOCK * ITEMS + threadIdx.x);
     u32 id[ITEMS];
     uint2 r[ITEMS];
+    // (positions past P read the view's last one, P - 1, and are masked afterwards: loads under a condition become branches with a
+    // wait each, and the gathers would go out one after the other)
 #pragma unroll
-    for (int i = 0; i < ITEMS; i++) { const int k = k0 + i * F3DG_BLOCK; id[i] = k < P ? perm[vb + k] : 0u; }
+    for (int i = 0; i < ITEMS; i++) { const int k = k0 + i * F3DG_BLOCK; id[i] = perm[vb + (k < P ? k : P - 1)]; }
 #pragma unroll
-    for (int i = 0; i < ITEMS; i++) { const int k = k0 + i * F3DG_BLOCK; r[i] = k < P ? rects[vb + id[i]] : make_uint2(0u, 0u); }
+    for (int i = 0; i < ITEMS; i++) r[i] = rects[vb + id[i]];
 #pragma unroll
     for (int i = 0; i < ITEMS; i++) {
         const int k = k0 + i * F3DG_BLOCK;
+        const u32 live = k < P ? 0xFFFFFFFFu : 0u;
+        r[i].x &= live; r[i].y &= live;
         if (k < P) {
             rx[vb + k] = r[i].x;
             ry[vb + k] = r[i].y;
@@ -609,9 +668,8 @@ duplicate_sorted_kernel(int P, int tile_bits, int grid_x, const u32* __restrict_
     u32 cnt = 0, x = 0, y = 0, g = 0;
     if (k < P) {
         const size_t pos = (size_t)v * P + k;
-        x = rx[pos]; y = ry[pos];
+        x = rx[pos]; y = ry[pos]; g = perm[pos];         // (g is used where cnt != 0 only, but asked for with the rectangle, not behind it)
         cnt = rect_instances(x, y);
-        if (cnt) g = perm[pos];
     }
     // a thread's run starts off0 instances into the range, which holds n: exclusive prefix and total of cnt over the workgroup
     u32 n;
@@ -762,10 +820,11 @@ static int binning_tail(hipStream_t s, int V, int P, int grid_x, int T, int tile
         rc = f3dg_launch_scan_inclusive(s, hist, hist, (unsigned long long)256 * gblocks, scan_tmp, L.scan_tmp_elems, 1, nullptr);        \
         if (rc != F3DG_OK) return rc;                                                                                                      \
     }                                                                                                                                      \
+    if (PASS == 0)     /* the views' key ranges, from the chunks' that the histogram found: every scatter asks gsort_compact */           \
+        F3DG_KLAUNCH(gsort_range_kernel, dim3(V), dim3(64), 0, s, cps, chunk_minmax, minmax);                                            \
     F3DG_KLAUNCH((gsort_scatter_kernel<PASS>), dim3(gblocks), dim3(F3DG_BLOCK), 0, s, gk[IN], gv[IN], gk[OUT], gv[OUT], (u32)P, cps, hist, minmax)
     F3DG_GSORT_PASS(0, 0, 1);
     F3DG_GSORT_PASS(1, 1, 0);
-    F3DG_KLAUNCH(gsort_range_kernel, dim3(V), dim3(64), 0, s, cps, chunk_minmax, minmax);
     F3DG_GSORT_PASS(2, 0, 1);
     F3DG_GSORT_PASS(3, 1, 0);
 #undef F3DG_GSORT_PASS
