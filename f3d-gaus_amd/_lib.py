@@ -166,6 +166,8 @@ SIGNATURES = {
     "f3dg_backward_pairs": (_i, [_p, _p, C.POINTER(_ll)]),
     "f3dg_debug_timing": (_i, [C.POINTER(C.c_ulonglong), _i]),
     "f3dg_debug_export": (_i, [_p, _p, _i, _i, _i, _i, _ll, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    # stream ws | P W H n_views cap | cull rects chunk_boxes
+    "f3dg_debug_export_cull": (_i, [_p, _p, _i, _i, _i, _i, _ll, _p, _p, _p]),
 }
 
 _LIB = None

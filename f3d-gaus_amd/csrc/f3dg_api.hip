@@ -774,3 +774,27 @@ extern "C" int f3dg_debug_export(void* stream, const void* workspace, int P, int
 #undef CP
     return F3DG_OK;
 }
+
+// ---- the projection's own conservative culling data (f3dg_preprocess.hip), for the tests that hold it to a plain reference pair by
+// pair: the ellipse plane, the tile rectangles with their half-tile hints, and the small-call path's 64-Gaussian chunk boxes. Any
+// pointer may be NULL. BLOCKING.
+extern "C" int f3dg_debug_export_cull(void* stream, const void* workspace, int P, int W, int H, int n_views, long long max_rendered,
+                                      float* cull /*[V*P*4]*/, unsigned* rects /*[V*P*2]*/, unsigned* chunk_boxes /*[V*ceil(P/64)*2]*/)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (!workspace || P < 0 || W <= 0 || H <= 0 || n_views <= 0 || max_rendered < 0) return F3DG_ERR_BAD_ARG;
+    const F3dgLayout L = f3dg_layout(P, W, H, n_views, max_rendered);
+    const char* ws = static_cast<const char*>(workspace);
+    const size_t VP = (size_t)n_views * P;
+    F3dgHeader h;
+    F3DG_HIP_CHECK(hipMemcpyAsync(&h, ws + L.header, sizeof h, hipMemcpyDeviceToHost, s));
+    F3DG_HIP_CHECK(hipStreamSynchronize(s));
+    // the chunk boxes are written by the projection of a small-path call only (and the layout reserves them for its shapes only)
+    if (chunk_boxes && (!h.small_path || L.small_cap == 0)) return F3DG_ERR_STATE;
+    if (cull && VP) F3DG_HIP_CHECK(hipMemcpyAsync(cull, ws + L.cull, VP * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    if (rects && VP) F3DG_HIP_CHECK(hipMemcpyAsync(rects, ws + L.rects, VP * sizeof(uint2), hipMemcpyDeviceToDevice, s));
+    if (chunk_boxes && VP)
+        F3DG_HIP_CHECK(hipMemcpyAsync(chunk_boxes, ws + L.small_boxes, (size_t)n_views * ((P + 63) / 64) * sizeof(uint2), hipMemcpyDeviceToDevice, s));
+    F3DG_HIP_CHECK(hipStreamSynchronize(s));
+    return F3DG_OK;
+}

@@ -1157,6 +1157,21 @@ int f3dg_debug_export(void* stream, const void* workspace, int P, int W, int H, 
                       unsigned* offsets, unsigned char* clamped, unsigned long long* keys_sorted,
                       unsigned* point_list, unsigned* ranges, float* final_T, unsigned* n_contrib, float* depths);
 
+/* Test/inspection hook, BLOCKING: the projection's own conservative culling data of the last forward on this workspace, copied to device
+ * buffers of the caller (any pointer may be NULL). Same shape arguments as f3dg_debug_export.
+ *   cull [V*P*4]   the conservative alpha >= 1/255 ellipse (cx, cy, a, b) in pixel-index coordinates; its c is slot 15 of `rec`, the
+ *                  pre-test constant K slot 11. "everything" is a = b = c = 0; "never" is the centre (-1e9, -1e9) with a = c = 1e30.
+ *                  A SAVE_AUX call writes this plane and the record for every pair; an INFERENCE call writes them only for the (view,
+ *                  Gaussian) pairs that are in a tile list -- the other rows hold whatever the workspace held before.
+ *   rects [V*P*2]  the tile rectangle (min | max << 16 per axis, 15-bit tile coordinates, max exclusive; 0, 0: in no tile) after tile
+ *                  culling, with the half-tile hints F3DG_RECT_SKIP_LO (bit 15) / F3DG_RECT_SKIP_HI (bit 31) of each word. ALWAYS written,
+ *                  for every pair, by every call.
+ *   chunk_boxes [V*ceil(P/64)*2]  small-call path only: the union of the rectangles of each 64 consecutive Gaussians, hint bits
+ *                  stripped ("everything", 0 | 0x7FFF << 16, for a view's last partial chunk). Asking for it on a workspace whose last
+ *                  forward did not take the small-call path returns F3DG_ERR_STATE. */
+int f3dg_debug_export_cull(void* stream, const void* workspace, int P, int W, int H, int n_views, long long max_rendered,
+                           float* cull, unsigned* rects, unsigned* chunk_boxes);
+
 /* Kept for callers of earlier versions: h_out8[8] was the phase timing of an instrumented compositing kernel. No kernel is
  * instrumented any more: it returns zeros. */
 int f3dg_debug_timing(unsigned long long* h_out8, int reset);

@@ -54,6 +54,10 @@ def test_workspace_arithmetic_and_host_side_errors(f3d):
     assert rc == _lib.ERR_WORKSPACE
     assert L.f3dg_splat_head(null, 0, 32, 32, *([null] * 5), 1.0, 1024, 0, *([null] * 7)) == _lib.ERR_BAD_ARG
     assert L.f3dg_mark_visible(null, 5, null, null, null, null) == _lib.ERR_BAD_ARG
+    # the culling-data export is declared, bound, and refuses a missing workspace or a non-shape before it touches the device
+    assert "f3dg_debug_export_cull" in _declared() and "f3dg_debug_export_cull" in _lib.SIGNATURES
+    assert L.f3dg_debug_export_cull(null, null, 10, 64, 64, 1, 100, null, null, null) == _lib.ERR_BAD_ARG
+    assert L.f3dg_debug_export_cull(null, one, 10, 0, 64, 1, 100, null, null, null) == _lib.ERR_BAD_ARG
 
 
 def test_python_api_errors_without_gpu(f3d):

@@ -1,7 +1,7 @@
 """How much of the conservative ellipse (csrc/f3dg_preprocess.hip: cull_conic + conservative_ellipse) is margin? For one C2-recipe view the
 area of every visible Gaussian's ellipse -- the number of (pixel, entry) pairs phase 1 lets into phase 2 is proportional to it -- with
 the margins as built and with each of them reduced, against the exact level set alpha >= 1/255 (no margin at all). numpy float64
-restatement of the device code's formulas; needs the oracle. Test infrastructure only.
+restatement of the device code's formulas (the conic itself: tests/cull_truth.py conic_restated, shared with the tests); needs the oracle. Test infrastructure only.
 
   python tests/tools/ellipse_margin_model.py [sigma0]
 """
@@ -12,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
+from cull_truth import conic_restated
 from helpers import make_scene, run_oracle
 
 S0 = float(sys.argv[1]) if len(sys.argv) > 1 else 0.01
@@ -42,12 +43,7 @@ def areas(k_extra, d_scale, s_rel, s_px, local=False):
         Xl, Yl = np.minimum(np.abs(cx0) + 0.1 * X, X), np.minimum(np.abs(cy0) + 0.1 * Y, Y)
     else:
         Xl, Yl = X, Y
-    A = np.abs(vg[:, 0]) * Xl * Xl + 2 * np.abs(vg[:, 1]) * Xl * Yl + 2 * np.abs(vg[:, 2]) * Xl + np.abs(vg[:, 3]) * Yl * Yl + 2 * np.abs(vg[:, 4]) * Yl + np.abs(vg[:, 5])
-    Bn = np.abs(vg[:, 6]) * Xl + np.abs(vg[:, 7]) * Yl + np.abs(vg[:, 8])
-    D = d_scale * 1.1 * u * (6.0 * cK * A + 7.0 * Bn * Bn)
-    B0, B1, B2 = vg[:, 6], vg[:, 7], vg[:, 8]
-    m00, m01, m02 = cK * vg[:, 0] - B0 * B0, cK * vg[:, 1] - B0 * B1, cK * vg[:, 2] - B0 * B2
-    m11, m12, m22 = cK * vg[:, 3] - B1 * B1, cK * vg[:, 4] - B1 * B2, cK * vg[:, 5] - B2 * B2 - D
+    m00, m01, m02, m11, m12, m22, _ = conic_restated(vg, thr, Xl, Yl, k_extra, d_scale)      # the shared float64 restatement of cull_conic
     D22 = m00 * m11 - m01 * m01
     good = (cK > 0) & (m00 > 0) & (m11 > 0) & (D22 > 1e-9 * np.abs(m00 * m11))
     cx, cy = (m01 * m12 - m02 * m11) / D22, (m01 * m02 - m00 * m12) / D22
