@@ -80,9 +80,9 @@ splat_head_kernel(int HW, const float* __restrict__ net_out, const float* __rest
     const SplatPos pos = splat_position(net, ray_dirs, M, HW, n, d);
     float X = pos.X, Y = pos.Y;
     const float Z = pos.Z;
-    if (squre_clip < 10.0f) {
-        X = fminf(fmaxf(X, -squre_clip), squre_clip);
-        Y = fminf(fmaxf(Y, -squre_clip), squre_clip);
+    if (squre_clip < 10.0f) {       // clamp_(-c, c): NaN stays NaN as in torch (fminf / fmaxf would return the bound for it)
+        X = X < -squre_clip ? -squre_clip : (X > squre_clip ? squre_clip : X);
+        Y = Y < -squre_clip ? -squre_clip : (Y > squre_clip ? squre_clip : Y);
     }
 
     const size_t o = (size_t)b * (size_t)n_total + (size_t)n_offset + n;

@@ -484,6 +484,43 @@ def allocate_gaussians(B, N, device):
     return {k: torch.empty((B, N) + _KEY_SHAPE[k], dtype=torch.float32, device=device) for k in GAUSSIAN_KEYS}
 
 
+def _check_splat_head_inputs(net_out, depth, ray_dirs, view_to_world, cam_quat, where=""):
+    """The kernel indexes every input by (B, H, W) of ``net_out`` alone: a wrong shape is refused here, before any launch."""
+    if net_out.dim() != 4 or net_out.shape[1] != 23:
+        raise RuntimeError("splat head expects the 23-channel with-offset / SH-degree-1 layout [3,1,3,4,3,9]")
+    B, _, H, W = net_out.shape
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"{where}net_out must be a non-empty [B, 23, H, W], got {tuple(net_out.shape)}")
+    if tuple(depth.shape) != (B, 1, H, W):
+        raise ValueError(f"{where}depth must be [{B}, 1, {H}, {W}] like net_out, got {tuple(depth.shape)}")
+    if ray_dirs.numel() != 3 * H * W:
+        raise ValueError(f"{where}ray_dirs must be [1, 3, {H}, {W}] ({3 * H * W} values), got {tuple(ray_dirs.shape)}")
+    if view_to_world.numel() != 16 * B or cam_quat.numel() != 4 * B:
+        raise ValueError(f"{where}view_to_world must be [{B}, 4, 4] and cam_quat [{B}, 4], got {tuple(view_to_world.shape)} and "
+                         f"{tuple(cam_quat.shape)}")
+
+
+def _check_gaussian_buffers(out, B, HW, n_offset, device):
+    """``out``: the seven aggregated buffers [B, n_total, ...] the kernel writes rows n_offset .. n_offset + HW of. Returns n_total."""
+    missing = [k for k in GAUSSIAN_KEYS if k not in out]
+    if missing:
+        raise ValueError(f"aggregated buffers lack {missing}")
+    if out["xyz"].dim() < 2:
+        raise ValueError(f"aggregated buffer 'xyz' must be [B, n_total, 3], got {tuple(out['xyz'].shape)}")
+    n_total = int(out["xyz"].shape[1])
+    for k in GAUSSIAN_KEYS:
+        t = out[k]
+        if not (t.is_contiguous() and t.dtype == torch.float32):
+            raise RuntimeError(f"aggregated buffer '{k}' must be contiguous float32 [B, n_total, ...]")
+        if tuple(t.shape) != (B, n_total) + _KEY_SHAPE[k]:
+            raise ValueError(f"aggregated buffer '{k}' must be {(B, n_total) + _KEY_SHAPE[k]}, got {tuple(t.shape)}")
+        if t.device != device:
+            raise RuntimeError(f"aggregated buffer '{k}' is on {t.device}, net_out on {device}")
+    if int(n_offset) != n_offset or not 0 <= n_offset <= n_total - HW:
+        raise ValueError(f"n_offset must satisfy 0 <= n_offset <= n_total - H*W = {n_total - HW}, got {n_offset}")
+    return n_total
+
+
 def _splat_head_call(net_out, depth, ray_dirs, v2w, quat, squre_clip, out, n_total, n_offset):
     """The raw kernel call on prepared (contiguous float32, same device) tensors."""
     B, _, H, W = net_out.shape
@@ -532,13 +569,16 @@ def splat_head(net_out, depth, ray_dirs, view_to_world, cam_quat, squre_clip=100
 
     Differentiable in ``net_out`` and ``depth`` (f3dg_splat_head_backward) when grad mode is on and one of them requires grad; the
     cameras and ``ray_dirs`` get no gradient, and the in-place form (``out=``) is for inference only."""
+    _check_splat_head_inputs(net_out, depth, ray_dirs, view_to_world, cam_quat)
     B, Cc, H, W = net_out.shape
-    if Cc != 23:
-        raise RuntimeError("splat head expects the 23-channel with-offset / SH-degree-1 layout [3,1,3,4,3,9]")
     device = net_out.device
+    HW = H * W
+    if out is not None:
+        _check_gaussian_buffers(out, B, HW, n_offset, device)
+    elif n_offset != 0:
+        raise ValueError(f"n_offset = {n_offset} needs the aggregated buffers it points into (out=)")
     if device.type != "cuda":
         raise RuntimeError("f3dgaus_amd splat head needs tensors on a HIP device (no CPU fallback)")
-    HW = H * W
     grad_on = torch.is_grad_enabled()
     if grad_on:
         for name, t in (("ray_dirs", ray_dirs), ("view_to_world", view_to_world), ("cam_quat", cam_quat)):
@@ -556,11 +596,7 @@ def splat_head(net_out, depth, ray_dirs, view_to_world, cam_quat, squre_clip=100
         return dict(zip(GAUSSIAN_KEYS, _SplatHead.apply(net_out, depth, ray_dirs, v2w, quat, float(squre_clip))))
     if out is None:
         out = allocate_gaussians(B, HW, device)
-    n_total = out["xyz"].shape[1]
-    for k in GAUSSIAN_KEYS:
-        t = out[k]
-        if not (t.is_contiguous() and t.dtype == torch.float32 and t.shape[0] == B and t.shape[1] == n_total):
-            raise RuntimeError(f"aggregated buffer '{k}' must be contiguous float32 [B, n_total, ...]")
+    n_total = _check_gaussian_buffers(out, B, HW, n_offset, device)
     return _splat_head_call(net_out, depth, ray_dirs, v2w, quat, squre_clip, out, n_total, n_offset)
 
 
@@ -623,15 +659,15 @@ def splat_head_merge(net_outs, depths, ray_dirs, view_to_worlds, cam_quats, squr
     K = len(net_outs)
     if K == 0 or not (len(depths) == len(view_to_worlds) == len(cam_quats) == K):
         raise RuntimeError("splat_head_merge needs the same non-zero number of net_outs, depths, view_to_worlds and cam_quats")
+    _check_splat_head_inputs(net_outs[0], depths[0], ray_dirs, view_to_worlds[0], cam_quats[0], "pass 0: ")
     B, Cc, H, W = net_outs[0].shape
-    if Cc != 23:
-        raise RuntimeError("splat head expects the 23-channel with-offset / SH-degree-1 layout [3,1,3,4,3,9]")
     device = net_outs[0].device
+    for k in range(1, K):
+        if tuple(net_outs[k].shape) != (B, 23, H, W):
+            raise RuntimeError(f"pass {k}: net_out must be [{B}, 23, {H}, {W}] and depth [{B}, 1, {H}, {W}] like pass 0's")
+        _check_splat_head_inputs(net_outs[k], depths[k], ray_dirs, view_to_worlds[k], cam_quats[k], f"pass {k}: ")
     if device.type != "cuda":
         raise RuntimeError("f3dgaus_amd splat head needs tensors on a HIP device (no CPU fallback)")
-    for k in range(K):
-        if tuple(net_outs[k].shape) != (B, 23, H, W) or depths[k].numel() != B * H * W:
-            raise RuntimeError(f"pass {k}: net_out must be [{B}, 23, {H}, {W}] and depth [{B}, 1, {H}, {W}] like pass 0's")
     grad_on = torch.is_grad_enabled()
     if grad_on:
         named = [("ray_dirs", ray_dirs)] + [(f"view_to_worlds[{k}]", t) for k, t in enumerate(view_to_worlds)] + [

@@ -51,13 +51,34 @@ def focal2fov_torch(focal, pixels):
 
 
 def _epilogue(raster, world_view, W, H, FoVx, FoVy, want_normal=True, want_depth_normal=True, out=None):
-    """raster [V,9,H,W], world_view [V,4,4] (row-vector convention). Returns (normal_world, depth_normal) [V,3,H,W]; `out`: a pair of
-    such tensors to fill instead of new ones."""
+    """raster [V,9,H,W] float32 on a HIP device, world_view [V,4,4] (row-vector convention). Returns (normal_world, depth_normal)
+    [V,3,H,W]; `out`: a pair of such tensors (or None for a map that is not wanted) to fill instead of new ones. The kernel indexes by
+    V, H, W alone, so every shape is checked here, before the launch: ValueError for a wrong shape or dtype, RuntimeError for a
+    tensor that is not on the raster's HIP device."""
+    W, H = int(W), int(H)
+    if raster.dim() != 4 or raster.shape[1] != 9 or tuple(raster.shape[2:]) != (H, W) or raster.shape[0] < 1:
+        raise ValueError(f"raster must be [V, 9, {H}, {W}] (image_height x image_width), got {tuple(raster.shape)}")
+    if raster.dtype != torch.float32:
+        raise ValueError(f"raster must be float32, got {raster.dtype}")
     V = raster.shape[0]
+    if world_view.numel() != 16 * V:
+        raise ValueError(f"world_view must hold {V} 4x4 matrices ({16 * V} values), got {tuple(world_view.shape)}")
+    if out is not None:
+        if len(out) != 2:
+            raise ValueError("out must be a pair (normal_world, depth_normal)")
+        for name, t in zip(("normal_world", "depth_normal"), out):
+            if t is None:
+                continue
+            if tuple(t.shape) != (V, 3, H, W) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"out {name} must be a contiguous float32 [{V}, 3, {H}, {W}], got {t.dtype} {tuple(t.shape)}")
+            if t.device != raster.device:
+                raise RuntimeError(f"out {name} is on {t.device}, the raster on {raster.device}")
+    if raster.device.type != "cuda":
+        raise RuntimeError("the render epilogue needs its raster on a HIP device (no CPU fallback)")
     device = raster.device
     wv = world_view.reshape(V, 16)
-    if wv.dtype != torch.float32 or not wv.is_contiguous():
-        wv = wv.float().contiguous()
+    if wv.dtype != torch.float32 or not wv.is_contiguous() or wv.device != device:
+        wv = wv.to(device=device, dtype=torch.float32).contiguous()
     fx = W / (2 * math.tan(FoVx / 2.))
     fy = H / (2 * math.tan(FoVy / 2.))
     if out is not None:
@@ -133,11 +154,12 @@ def depths_to_points(world_view_transform, image_width, image_height, FoVx, FoVy
 
 def depth_to_normal(world_view_transform, image_width, image_height, FoVx, FoVy, depth):
     """Central-difference normal map [H,W,3] of a depth map [1,H,W], border = 0 (:898-909). Uses the fused kernel."""
-    H, W = depth.shape[-2], depth.shape[-1]
+    H, W = int(image_height), int(image_width)
+    if depth.dim() < 2 or tuple(depth.shape[-2:]) != (H, W) or depth.numel() != H * W:
+        raise ValueError(f"depth must be [1, {H}, {W}] (image_height x image_width), got {tuple(depth.shape)}")
     raster = torch.zeros((1, 9, H, W), dtype=torch.float32, device=depth.device)
     raster[0, 6] = depth.reshape(H, W)
-    _, dn = _epilogue(raster, world_view_transform.reshape(1, 4, 4), image_width, image_height, FoVx, FoVy,
-                      want_normal=False)
+    _, dn = _epilogue(raster, world_view_transform.reshape(1, 4, 4), W, H, FoVx, FoVy, want_normal=False)
     return dn[0].permute(1, 2, 0)
 
 
