@@ -23,7 +23,7 @@ from .gaussian_renderer import (render_predicted_more_v2_gof, render_predicted_m
 from .gaussian_predictor import GaussianSplatPredictor_gtunet, splat_head, splat_head_merge  # noqa: E402,F401
 from .unet_gs import Unet_GS_gtunet  # noqa: E402,F401
 from .mesh import marching_tetrahedra, tetra_points, bisect_level_set, extract_mesh, extract_mesh_tsdf, mesh_components, clean_mesh  # noqa: E402,F401
-from .mesh import mesh_adjacency, smooth_mesh, vertex_normals  # noqa: E402,F401
+from .mesh import mesh_adjacency, smooth_mesh, vertex_normals, simplify_mesh  # noqa: E402,F401
 from .mesh import render_mesh, interpolate_vertex_attributes, mesh_depth_agreement, bake_vertex_colors  # noqa: E402,F401
 from .tsdf import TSDFVolume  # noqa: E402,F401
 from .frames import compose_frames, compose_orbit_frames, depth_range, colormap_lut  # noqa: E402,F401

@@ -16,6 +16,9 @@ MAX_PANELS, PANEL_RGB, PANEL_SIGNED, PANEL_COLORMAP = 8, 0, 1, 2
 TSDF_MAX_VIEWS = 128
 RASTER_CULL = {"none": 0, "back": 1, "front": 2}
 BAKE_MODE = {"blend": 0, "best": 1}
+SIMPLIFY_PLACEMENT = {"root": 0, "mean": 1, "quadric": 2}
+SIMPLIFY_COUNTS = ("clusters", "used_clusters", "degenerate", "collapsed", "duplicate", "kept", "max_cluster")
+SIMPLIFY_MAX_ATTRS = 64
 BAKE_COUNTS = ("near", "outside", "uncovered", "occluded", "grazing", "masked", "used", "vertices_seen")
 
 
@@ -137,6 +140,11 @@ SIGNATURES = {
     "f3dg_mesh_smooth": (_i, [_p, _ll, _p, _p, _p, _p, _f, _f, _i, _p, _p]),
     # stream ws ws_bytes | N F faces faces_int32 | vertices normals
     "f3dg_mesh_vertex_normals": (_i, [_p, _p, _sz, _ll, _ll, _p, _i, _p, _p]),
+    # N F  /  stream ws ws_bytes | N F vertices faces faces_int32 | origin(host [3] float64) cell | h_counts[8]
+    # /  ... faces_int32 | placement C attrs adj_ws adj_ws_bytes | n_vertices_out n_faces_out | vertices_out faces_out attrs_out vertex_map cluster_root cluster_size
+    "f3dg_mesh_simplify_workspace_bytes": (_sz, [_ll, _ll]),
+    "f3dg_mesh_simplify_count": (_i, [_p, _p, _sz, _ll, _ll, _p, _p, _i, C.POINTER(C.c_double), C.c_double, C.POINTER(_ll)]),
+    "f3dg_mesh_simplify_emit": (_i, [_p, _p, _sz, _ll, _ll, _p, _p, _i, _i, _i, _p, _p, _sz, _ll, _ll, _p, _p, _p, _p, _p, _p]),
     # V F H W  /  stream ws ws_bytes | N F vertices faces faces_int32 | V world_views fx fy H W z_near cull | C attrs | face_id depth bary attrs_out | h_counts[7]
     "f3dg_mesh_raster_workspace_bytes": (_sz, [_ll, _ll, _ll, _ll]),
     "f3dg_mesh_raster": (_i, [_p, _p, _sz, _ll, _ll, _p, _p, _i, _i, _p, C.c_double, C.c_double, _i, _i, C.c_double, _i, _i, _p, _p, _p, _p, _p,

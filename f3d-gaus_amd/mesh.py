@@ -340,6 +340,110 @@ def vertex_normals(vertices, faces, adjacency=None):
     return normals
 
 
+@torch.no_grad()
+def simplify_mesh(vertices, faces, cell_size=None, *, grid_resolution=None, origin=None, placement="quadric", vertex_colors=None,
+                  adjacency=None):
+    """Reduce the mesh ``vertices`` [N,3] float32 / ``faces`` [F,3] (int64 or int32) by uniform-grid vertex clustering
+    (f3dg_mesh_simplify_count / _emit, csrc/f3dg_mesh_simplify.hip; the definition is include/f3dg.h's): the vertices of one grid cell
+    become one vertex, faces whose corners no longer lie in three distinct cells go, of the faces that name the same three cells the
+    first stays (whatever the winding), and the result is compacted. Exactly one of ``cell_size`` (world units) and ``grid_resolution``
+    (the cell is the longest side of the vertices' box divided by it, in float64) must be given; ``origin`` (three numbers) is the
+    grid's corner, the per-axis minimum of the vertices when None (one host read). ``placement``:
+        'root'       the cell's least vertex id, copied bit for bit. With a small cell this is grid welding: positions equal to the bit
+                     always merge, positions within ``cell_size`` of each other merge unless a cell boundary runs between them
+        'mean'       the members' mean
+        'quadric'    the minimiser of the regularised quadric of the members' faces, within one cell of the mean (the mean otherwise):
+                     planar regions stay at the mean, edges and corners are kept sharp
+    ``vertex_colors`` [N,C] float32 (C <= 64) are averaged over the members. ``adjacency``: a ``mesh_adjacency`` of THESE faces (only
+    'quadric' reads it), built here otherwise. Returns a dict:
+        vertices [n,3], faces [f,3] int64, vertex_colors [n,C] or None
+        vertex_map [N] int64         the new id of every old vertex, -1 where no surviving face uses its cell
+        cluster_root [n] int64, cluster_size [n] int64     the least old id and the number of old vertices of every new vertex
+        counts                       dict: clusters, used_clusters (n), degenerate, collapsed, duplicate, kept (f) faces -- the four sum
+                                     to F --, max_cluster
+    Not edge-collapse decimation: no error bound, no topology or manifold preservation. The result is data: an input that requires
+    grad raises; bit-reproducible. A non-finite vertex, a vertex more than 2^21 cells from ``origin`` (or below it) and a face with an
+    id outside [0, N) raise. One blocking host read in the library."""
+    if placement not in _lib.SIMPLIFY_PLACEMENT:
+        raise ValueError(f"simplify_mesh: placement must be one of {sorted(_lib.SIMPLIFY_PLACEMENT)}, got {placement!r}")
+    if (cell_size is None) == (grid_resolution is None):
+        raise ValueError("simplify_mesh: give exactly one of cell_size and grid_resolution")
+    if cell_size is not None and not (float(cell_size) > 0.0 and math.isfinite(float(cell_size))):
+        raise ValueError(f"simplify_mesh: cell_size must be positive and finite, got {cell_size}")
+    if grid_resolution is not None and not 1 <= int(grid_resolution) < (1 << 21):
+        raise ValueError(f"simplify_mesh: grid_resolution must be in [1, 2^21), got {grid_resolution}")
+    if origin is not None:
+        origin = [float(x) for x in origin]
+        if len(origin) != 3 or not all(math.isfinite(x) for x in origin):
+            raise ValueError(f"simplify_mesh: origin must be three finite numbers, got {origin}")
+    _no_grad_input(vertices, "simplify_mesh", "vertices")
+    _no_grad_input(vertex_colors, "simplify_mesh", "vertex_colors")
+    faces = _faces_arg(faces, "simplify_mesh")
+    vertices = _vertices_arg(vertices, faces, "simplify_mesh")
+    N, F, dev = int(vertices.shape[0]), int(faces.shape[0]), vertices.device
+    Cn = 0
+    if vertex_colors is not None:
+        _require_hip(vertex_colors)
+        if vertex_colors.dim() != 2 or vertex_colors.shape[0] != N or vertex_colors.dtype != torch.float32 or vertex_colors.device != dev \
+                or not 1 <= vertex_colors.shape[1] <= _lib.SIMPLIFY_MAX_ATTRS:
+            raise ValueError(f"simplify_mesh: vertex_colors must be [{N},C] float32 with 1 <= C <= {_lib.SIMPLIFY_MAX_ATTRS} on {dev}, got "
+                             f"{tuple(vertex_colors.shape)} {vertex_colors.dtype} on {vertex_colors.device}")
+        vertex_colors = vertex_colors.contiguous()
+        Cn = int(vertex_colors.shape[1])
+    i64 = lambda *shape: torch.empty(shape, dtype=torch.int64, device=dev)
+    if N == 0:
+        if F:
+            raise ValueError("simplify_mesh: faces over an empty vertex set")
+        return {"vertices": vertices.clone(), "faces": i64(0, 3), "vertex_colors": None if vertex_colors is None else vertex_colors.clone(),
+                "vertex_map": i64(0), "cluster_root": i64(0), "cluster_size": i64(0), "counts": dict.fromkeys(_lib.SIMPLIFY_COUNTS, 0)}
+    if origin is None or grid_resolution is not None:
+        box = torch.stack([vertices.amin(dim=0), vertices.amax(dim=0)]).double().cpu()
+        lo, hi = box[0].tolist(), box[1].tolist()
+        if not all(math.isfinite(a) and math.isfinite(b) for a, b in zip(lo, hi)):
+            raise ValueError("simplify_mesh: a vertex coordinate is not finite")
+        if origin is None:
+            origin = lo
+    if grid_resolution is not None:
+        cell = max(b - a for a, b in zip(lo, hi)) / int(grid_resolution)
+        if not cell > 0.0:
+            raise ValueError("simplify_mesh: grid_resolution needs vertices that span a box (all of them coincide)")
+    else:
+        cell = float(cell_size)
+    L = _lib.lib()
+    nbytes = L.f3dg_mesh_simplify_workspace_bytes(N, F)
+    if nbytes == 0:
+        raise _lib.F3dgError(_lib.ERR_UNSUPPORTED, "f3dg_mesh_simplify_workspace_bytes")
+    counts = (C.c_longlong * 8)()
+    is32 = int(faces.dtype == torch.int32)
+    with torch.cuda.device(dev):
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        _lib.check(L.f3dg_mesh_simplify_count(_stream(), _lib.ptr(ws), nbytes, N, F, _lib.ptr(vertices), _lib.ptr(faces), is32,
+                                              (C.c_double * 3)(*origin), cell, counts), "f3dg_mesh_simplify_count")
+        n, f = int(counts[1]), int(counts[5])
+        out_v = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        out_c = torch.empty((n, Cn), dtype=torch.float32, device=dev) if Cn else None
+        out_f, vertex_map, cluster_root, cluster_size = i64(f, 3), torch.full((N,), -1, dtype=torch.int64, device=dev), i64(n), i64(n)
+        if n > 0:
+            adj_ws = None
+            if placement == "quadric":
+                adjacency = _adjacency_for(adjacency, faces, N, "simplify_mesh")
+                if int(adjacency["faces"].shape[0]) != F or adjacency["faces"].dtype != faces.dtype:
+                    raise ValueError("simplify_mesh: the adjacency was built on other faces")
+                adj_ws = adjacency["workspace"]
+            _lib.check(L.f3dg_mesh_simplify_emit(_stream(), _lib.ptr(ws), nbytes, N, F, _lib.ptr(vertices), _lib.ptr(faces), is32,
+                                                 _lib.SIMPLIFY_PLACEMENT[placement], Cn, _lib.ptr(vertex_colors), _lib.ptr(adj_ws),
+                                                 0 if adj_ws is None else adj_ws.numel(), n, f, _lib.ptr(out_v), _lib.ptr(out_f), _lib.ptr(out_c),
+                                                 _lib.ptr(vertex_map), _lib.ptr(cluster_root), _lib.ptr(cluster_size)), "f3dg_mesh_simplify_emit")
+    return {"vertices": out_v, "faces": out_f, "vertex_colors": out_c, "vertex_map": vertex_map, "cluster_root": cluster_root,
+            "cluster_size": cluster_size, "counts": {k: int(c) for k, c in zip(_lib.SIMPLIFY_COUNTS, counts)}}
+
+
+def _simplify_step(vertices, faces, vertex_colors, simplify_cell, simplify_placement):
+    """The opt-in simplification of both mesh routes, between the clean-up and the smoothing: ``simplify_mesh``'s dict."""
+    return simplify_mesh(vertices.detach(), faces, simplify_cell, placement=simplify_placement,
+                         vertex_colors=None if vertex_colors is None else vertex_colors.detach())
+
+
 def _smooth_and_normals(vertices, faces, smooth_iterations, smooth_lambda, smooth_mu, want_normals):
     """The tail of both mesh routes: (vertices, normals or None) after the opt-in smoothing and normals."""
     adjacency = None
@@ -649,7 +753,7 @@ def bisect_level_set(sweep, end_points, end_sdf, n_steps=8):
 @torch.no_grad()
 def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, resolution=256, bounds=None, trunc=None, alpha_min=0.5,
                       min_component_faces=None, keep_largest=None, smooth_iterations=None, smooth_lambda=0.5, smooth_mu=-0.53,
-                      vertex_normals=False, color_from_views=False):
+                      vertex_normals=False, color_from_views=False, simplify_cell=None, simplify_placement="quadric"):
     """The TSDF route to a coloured mesh of image ``bs`` of the Gaussian dict ``pc`` -- no tetrahedralisation from outside, nothing but
     this package (the semantics are this project's: ``f3dgaus_amd.tsdf``). All cameras are rendered in one
     launch sequence (``render_views(..., channels="rgb_depth_alpha", epilogue=False)``), depth, alpha and colour are fused into a
@@ -661,6 +765,11 @@ def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, 
     ``min_component_faces`` / ``keep_largest`` (opt-in; with both None the dict is exactly ``extract``'s): ``clean_mesh`` with ``min_faces``
     / ``keep_largest`` on the extracted mesh. ``vertices`` / ``faces`` / ``vertex_colors`` are then the cleaned ones and ``components``
     holds ``vertex_ids`` (rows of ``interp_v``), ``face_component`` and ``component_sizes``.
+
+    ``simplify_cell`` (opt-in, after the clean-up and before everything below, which then acts on the simplified mesh):
+    ``simplify_mesh`` with that cell size in world units (a few voxels; ``origin`` the vertices' minimum) and ``simplify_placement``.
+    ``vertices`` / ``faces`` / ``vertex_colors`` are then the simplified ones and ``simplify`` holds ``vertex_map`` (from the cleaned
+    mesh's ids, or the extracted mesh's without a clean-up), ``cluster_root`` and ``counts``.
 
     ``smooth_iterations`` (opt-in, after the clean-up): ``vertices`` becomes ``smooth_mesh``'s with ``smooth_lambda`` / ``smooth_mu`` and a
     pinned boundary. ``vertex_normals`` (opt-in, last): the dict gains ``vertex_normals`` [n,3], ready for
@@ -704,6 +813,10 @@ def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, 
         c = clean_mesh(m["vertices"], m["faces"], m["vertex_colors"], min_faces=min_component_faces, keep_largest=keep_largest)
         m.update(vertices=c["vertices"], faces=c["faces"], vertex_colors=c["vertex_colors"],
                  components={k: c[k] for k in ("vertex_ids", "face_component", "component_sizes")})
+    if simplify_cell is not None:
+        s = _simplify_step(m["vertices"], m["faces"], m["vertex_colors"], simplify_cell, simplify_placement)
+        m.update(vertices=s["vertices"], faces=s["faces"], vertex_colors=s["vertex_colors"],
+                 simplify={k: s[k] for k in ("vertex_map", "cluster_root", "counts")})
     if smooth_iterations is not None or vertex_normals:
         v, n = _smooth_and_normals(m["vertices"], m["faces"], smooth_iterations, smooth_lambda, smooth_mu, vertex_normals)
         m["vertices"] = v
@@ -721,7 +834,7 @@ def extract_mesh_tsdf(pc, bs, world_views, full_projs, camera_centers, bg, cfg, 
 @torch.no_grad()
 def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, camera_centers, bg, cfg, n_binary_steps=8, sweep=None,
                  min_component_faces=None, keep_largest=None, smooth_iterations=None, smooth_lambda=0.5, smooth_mu=-0.53, vertex_normals=False,
-                 color_from_views=False):
+                 color_from_views=False, simplify_cell=None, simplify_placement="quadric"):
     """visualize.py:447-546 for image ``bs`` of the Gaussian dict ``pc``: alpha of ``points`` [n,3] over all cameras (one ``AlphaSweep``,
     built here unless one is handed in), marching tetrahedra of ``cells`` [F,4] (any tetrahedralisation of ``points``; the reference's
     is CGAL on the host) on sdf = alpha - 0.5, ``n_binary_steps`` bisection steps, and the scale filter
@@ -732,8 +845,11 @@ def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, c
                                                                                update_faces leave, :545-546)
     With ``min_component_faces`` or ``keep_largest`` set (opt-in; the keys above are untouched) the dict also carries ``vertices_clean`` /
     ``faces_clean``: ``clean_mesh`` with ``min_faces`` / ``keep_largest`` on ``vertices_filtered`` / ``faces_filtered``.
+    ``simplify_cell`` (opt-in, after the clean-up): ``vertices_simplified`` / ``faces_simplified``, ``simplify_mesh`` with that cell size
+    (world units) and ``simplify_placement`` on the last mesh above (the clean one if there is one, the filtered one otherwise), and
+    ``simplify`` (``vertex_map`` from that mesh's ids, ``cluster_root``, ``counts``). Everything below then acts on the simplified mesh.
     ``smooth_iterations`` (opt-in, after the clean-up): ``vertices_smooth``, ``smooth_mesh`` with ``smooth_lambda`` / ``smooth_mu`` and a
-    pinned boundary on the last mesh above (the clean one if there is one, the filtered one otherwise; its faces are that mesh's).
+    pinned boundary on the last mesh above (the simplified, the clean or the filtered one, in that order; its faces are that mesh's).
     ``vertex_normals`` (opt-in, last): ``vertex_normals`` of that mesh, on the smoothed vertices if it was smoothed.
     ``color_from_views`` (opt-in, last of all; what the dead texturing branch of visualize.py:520-537 would have done): the cameras are
     rendered once (``render_views(..., channels="rgb_depth_alpha", epilogue=False)``) and baked onto that last mesh
@@ -764,16 +880,21 @@ def extract_mesh(pc, bs, points, points_scale, cells, world_views, full_projs, c
     if min_component_faces is not None or keep_largest is not None:
         c = clean_mesh(out["vertices_filtered"], out["faces_filtered"], min_faces=min_component_faces, keep_largest=keep_largest)
         out["vertices_clean"], out["faces_clean"] = c["vertices"], c["faces"]
+    mesh = "clean" if "vertices_clean" in out else "filtered"            # the mesh the opt-in steps below act on
+    if simplify_cell is not None:
+        s = _simplify_step(out["vertices_" + mesh], out["faces_" + mesh], None, simplify_cell, simplify_placement)
+        out["vertices_simplified"], out["faces_simplified"] = s["vertices"], s["faces"]
+        out["simplify"] = {k: s[k] for k in ("vertex_map", "cluster_root", "counts")}
+        mesh = "simplified"
     if smooth_iterations is not None or vertex_normals:
-        last = "clean" if "vertices_clean" in out else "filtered"
+        last = mesh
         v, n = _smooth_and_normals(out["vertices_" + last], out["faces_" + last], smooth_iterations, smooth_lambda, smooth_mu, vertex_normals)
         if smooth_iterations is not None:
             out["vertices_smooth"] = v
         if n is not None:
             out["vertex_normals"] = n
     if color_from_views:
-        last = "smooth" if "vertices_smooth" in out else "clean" if "vertices_clean" in out else "filtered"
-        v, f = out["vertices_" + last], out["faces_" + ("clean" if "faces_clean" in out else "filtered")]
+        v, f = out["vertices_" + ("smooth" if "vertices_smooth" in out else mesh)], out["faces_" + mesh]
         if v.shape[0]:
             frames = render_views(pc, bs, world_views, full_projs, camera_centers, bg, cfg, channels="rgb_depth_alpha", epilogue=False)
             b = _color_from_views(v, f, out.get("vertex_normals"), frames, world_views, cfg['model']['fov'], None)

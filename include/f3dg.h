@@ -63,6 +63,9 @@
  *   f3dg_mesh_adjacency / f3dg_mesh_smooth / f3dg_mesh_vertex_normals
  *       vertex adjacency of a triangle mesh, Taubin smoothing and area-weighted vertex normals: not in the reference (its script
  *       exports what trimesh makes of the raw mesh): the semantics are this build's, defined below
+ *   f3dg_mesh_simplify_count / f3dg_mesh_simplify_emit
+ *       mesh reduction by uniform-grid vertex clustering with root, mean or quadric placement (grid welding at a small cell): not in
+ *       the reference: the semantics are this build's, defined below
  *   f3dg_mesh_raster
  *       an exact z-buffered triangle rasteriser over the renderer's cameras (face id, depth, barycentric weights, interpolated vertex
  *       attributes per pixel): not in the reference (the texturing branch of visualize.py:520-537 is dead code and the mesh is never
@@ -881,6 +884,84 @@ int f3dg_mesh_smooth(void* stream, long long N, const int* nbr_start, const int*
                      float lambda, float mu, int iterations, float* scratch, float* vertices_out);
 int f3dg_mesh_vertex_normals(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, const void* faces,
                              int faces_int32, const float* vertices, float* normals);
+
+/* Mesh simplification: uniform-grid vertex clustering (Rossignac-Borrel) with three placements of the representative vertex, the removal
+ * of collapsed and duplicate faces, and the compaction of the result (f3dg_mesh_simplify.hip). Integer
+ * atomics only and no float atomics: every output is a function of the input alone and bit-reproducible. THE SEMANTICS ARE THIS
+ * PROJECT'S; tests/mesh_simplify_truth.py restates them in float64 numpy and the kernels equal it to the bit. Not edge-collapse
+ * decimation: no error bound, no topology or manifold preservation, no tolerance-exact weld across cell boundaries, no gradients.
+ *
+ * Inputs. vertices [N,3] float32, faces [F,3] int64 (faces_int32 = 0) or int32 (1), 0 < N < 2^31, 0 <= F < 2^31; origin: 3 float64 ON
+ *   THE HOST, finite; cell > 0, float64, finite; attrs [N,C] float32, 1 <= C <= F3DG_SIMPLIFY_MAX_ATTRS, or NULL with C = 0; placement =
+ *   F3DG_SIMPLIFY_ROOT / _MEAN / _QUADRIC.
+ * Cell. Per axis k, c_k = floor(((double)v_k - origin_k) / cell): one IEEE subtraction, one division, floor. 0 <= c_k < 2^21 is required.
+ *   The KEY of a vertex is  c_x | c_y << 21 | c_z << 42.
+ * Refusals found on the device. A non-finite coordinate, a cell index outside [0, 2^21), a face id outside [0, N): the count fails with
+ *   F3DG_ERR_BAD_ARG. All three are found by the FIRST kernel, before anything is indexed with an id, and every later kernel returns on
+ *   the flag: a refused mesh writes nothing but the workspace, and nothing to h_counts. One host read in the call.
+ * Clusters. Vertices with equal keys form a CLUSTER. Its ROOT is its least vertex id; its MEMBERS are taken in ascending vertex id
+ *   wherever an order matters. (Every vertex is in a cluster, whether a face uses it or not.)
+ * Faces. A face with two equal input ids is DEGENERATE. Any other face whose three corners do not fall into three distinct clusters is
+ *   COLLAPSED. Of the remaining faces those with the same SET of three clusters are DUPLICATES of one another, whatever their winding:
+ *   the least face id among them SURVIVES (is KEPT), the others are counted as duplicates. Survivors keep their input order and their
+ *   own winding. F = degenerate + collapsed + duplicate + kept, exactly.
+ * Output vertices. The clusters that a surviving face uses, numbered by ascending root: n of them. vertex_map [N] int64 maps an old id
+ *   to the new id of its cluster, -1 where the cluster is used by no surviving face. cluster_root [n] int64 and cluster_size [n] int64
+ *   are the root and the number of members of each output vertex. faces_out [f,3] int64 in the new numbering.
+ * Placement. Float64 from the float32 inputs, IEEE + - * / only, no contraction, sums taken one term at a time from 0.0 in the order
+ *   named, one rounding to float32 at the end.
+ *   ROOT: the root vertex's coordinates, copied bit for bit. With a small cell this is grid welding: positions that are equal to the bit
+ *     always share a cell and are merged, while positions within `cell` of each other may straddle a cell boundary and stay apart.
+ *   MEAN: pm = (sum of (double)p_m over the members, ascending) / (double)count, per coordinate; the vertex is (float)pm.
+ *   QUADRIC: from pm. Walk the members in ascending order; for each member walk the entries of its sorted incidence row (above:
+ *     f3dg_mesh_adjacency) with succ == 1, IN ROW ORDER -- the set and order f3dg_mesh_vertex_normals sums, so a face with k corners in
+ *     the cluster is taken k times. For each such face, with its corners p0 p1 p2 in the face's own order, u = p1 - p0, w = p2 - p0:
+ *       n = (uy wz - uz wy, uz wx - ux wz, ux wy - uy wx)                 (unnormalised: no sqrt anywhere, the weight is area^2)
+ *       r = (nx (pmx - p0x) + ny (pmy - p0y)) + nz (pmz - p0z)
+ *       Axx += nx nx, Axy += nx ny, Axz += nx nz, Ayy += ny ny, Ayz += ny nz, Azz += nz nz;   gx += r nx, gy += r ny, gz += r nz
+ *     Then tr = (Axx + Ayy) + Azz, mu = (0.001 tr) / 3, and (A + mu I) D = -g is solved by the adjugate:
+ *       a = Axx + mu, d = Ayy + mu, h = Azz + mu, b = Axy, c = Axz, e = Ayz
+ *       c00 = d h - e e, c01 = c e - b h, c02 = b e - c d, c11 = a h - c c, c12 = b c - a e, c22 = a d - b b
+ *       det = (a c00 + b c01) + c c02
+ *       Dx = -((c00 gx + c01 gy) + c02 gz) / det,  Dy = -((c01 gx + c11 gy) + c12 gz) / det,  Dz = -((c02 gx + c12 gy) + c22 gz) / det
+ *     D = 0 (the mean) unless tr > 0 and finite, det > 0 and finite, and every |D_k| <= cell (a D_k that is not finite fails that).
+ *     The vertex is (float)(pm + D) per coordinate. The regulariser makes the system positive definite and leaves the unconstrained
+ *     directions at the mean: a planar cluster stays at its mean, an edge cluster moves onto the edge, a corner cluster onto the corner.
+ * Attributes. attrs_out[row][c] = (float)((sum of (double)attrs[m][c] over the members, ascending) / (double)count), for every placement.
+ * f3dg_mesh_simplify_count: BLOCKING, one host read. workspace: f3dg_mesh_simplify_workspace_bytes(N, F) bytes, 16-byte aligned,
+ *   caller-owned. h_counts[0..7] = clusters, used clusters (n), degenerate, collapsed, duplicate and kept (f) faces, members of the
+ *   largest cluster, 0. F == 0 is legal: the clusters are counted, n = f = 0.
+ *   Method: a least-id hash set (an open-addressed table of 32-bit ids, empty = 0xFFFFFFFF, a power of two of at least 16 and at least
+ *   twice the items; an empty slot is claimed by compare-and-swap, an occupied one is joined by atomicMin when the OWNER's key,
+ *   recomputed from the inputs, is the item's; a slot's key never changes) over the vertices under their cell keys, then a member CSR
+ *   by count / scan / scatter / row sort (rows of at most 32 by one thread, longer ones by a 1024-thread workgroup, a bitonic network
+ *   in LDS up to 4,096 members and in place beyond), then the same hash set over the faces that are neither degenerate nor collapsed
+ *   under the sorted triple of their corners' roots (a face survives iff the lookup returns itself), then the flags, block counts and
+ *   scans of the compaction. No thread waits on another's write; every loop is bounded.
+ * f3dg_mesh_simplify_emit: after a count that returned F3DG_OK, same workspace, sizes, vertices and faces; no host read. The cell is the
+ *   count's. n_vertices_out / n_faces_out are the capacities of the output arrays (the count's n and f): rows beyond them are not
+ *   written. vertices_out [n,3] float32, faces_out [f,3] int64, attrs_out [n,C] float32 (NULL with C = 0), vertex_map [N], cluster_root
+ *   [n], cluster_size [n] int64. With _QUADRIC, adjacency_workspace is the workspace of an f3dg_mesh_adjacency of these faces that
+ *   returned F3DG_OK (NULL and 0 otherwise; 6 F < 2^31 then). On a workspace that holds no completed count of a mesh of these sizes,
+ *   or, with _QUADRIC, an adjacency workspace that holds no completed build of them, NOTHING is written (as f3dg_mesh_vertex_normals).
+ * Refused before any HIP call, nothing written (h_counts included): F3DG_ERR_BAD_ARG for a NULL workspace, vertices, origin, h_counts,
+ *   faces (where F > 0; always for the emit), vertices_out, faces_out, vertex_map, cluster_root or cluster_size, attrs or attrs_out with
+ *   C > 0, the adjacency workspace with _QUADRIC; N <= 0, F < 0, F == 0 for the emit; a cell that is not positive and finite, an origin
+ *   that is not finite; a placement other than the three; C outside [0, F3DG_SIMPLIFY_MAX_ATTRS]; non-positive n_vertices_out or
+ *   n_faces_out; a workspace off the 16-byte grid, an int64 output off the 8-byte grid; an output that is another output, an input or
+ *   a workspace. F3DG_ERR_UNSUPPORTED for N or F at or above 2^31 (with _QUADRIC: 6 F at or above 2^31); F3DG_ERR_WORKSPACE for
+ *   workspace_bytes or adjacency_workspace_bytes too small. f3dg_mesh_simplify_workspace_bytes returns 0 for every size the calls refuse. */
+#define F3DG_SIMPLIFY_ROOT 0
+#define F3DG_SIMPLIFY_MEAN 1
+#define F3DG_SIMPLIFY_QUADRIC 2
+#define F3DG_SIMPLIFY_MAX_ATTRS 64
+size_t f3dg_mesh_simplify_workspace_bytes(long long N, long long F);
+int f3dg_mesh_simplify_count(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, const float* vertices,
+                             const void* faces, int faces_int32, const double* origin, double cell, long long* h_counts);
+int f3dg_mesh_simplify_emit(void* stream, void* workspace, size_t workspace_bytes, long long N, long long F, const float* vertices,
+                            const void* faces, int faces_int32, int placement, int C, const float* attrs, const void* adjacency_workspace,
+                            size_t adjacency_workspace_bytes, long long n_vertices_out, long long n_faces_out, float* vertices_out,
+                            long long* faces_out, float* attrs_out, long long* vertex_map, long long* cluster_root, long long* cluster_size);
 
 /* Mesh rasteriser: a triangle mesh drawn from the renderer's cameras with an exact integer coverage test and a 64-bit z-buffer
  * (f3dg_mesh_raster.hip). Integer atomics only: every output is a function of the input alone and
